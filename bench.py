@@ -18,13 +18,17 @@ EVERY rank in a second barrier-bracketed region and reported as config.host_rout
 scaling (feeder cores, pinned bandwidth, PCIe, NUMA), never `value`.  Every rank pins itself to the
 CPUs of its GPU's NUMA node before it allocates its page-locked buffers.
 
-One JSON line on rank 0 with the driver's keys plus
+One JSON line on rank 0 with the driver's keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run
+sets up, warms up, times --steps steps once and prints that line; --dump-outputs DIR also writes the last step's result.
+--full adds the median of three timed regions and everything else this file measures:
   roofline     : dominant kernel (trunk conv3x3 64->64) vs the dense fp16 MFMA peak, from HIP
                  events recorded on the engine's own stream inside the timed region
   cpu_baseline : the CPU oracle ("port": ncnn is not installable here) on a bounded sample
+  the host route (E) and PCIe rates above, per-rank records, and the parity probes against the CPU oracle
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -548,6 +552,25 @@ def pinned_budget_check(world, ranks_here, h, w, scale, depth=3):
     return needed, avail
 
 
+DUMP_MAX_VALUES = 1 << 23      # 32 MB of float32: --dump-outputs stays under 64 MB
+
+
+def dump_output(path, img):
+    """--dump-outputs: the last step's u8 result as <path>/output.npy in float32, whole when it has at most DUMP_MAX_VALUES
+    values, else every k-th value of the flattened array from a seeded offset -- k the smallest stride that keeps it within the
+    cap and shares no factor with the row length, so that the sample walks over every column and channel.  The same shape
+    gives the same sample, so two builds' files compare value for value."""
+    flat = img.reshape(-1)
+    if flat.size > DUMP_MAX_VALUES:
+        row = img.shape[1] * img.shape[2]
+        k = -(-flat.size // DUMP_MAX_VALUES)
+        while math.gcd(k, row) != 1:
+            k += 1
+        img = flat[int(np.random.default_rng(20261015).integers(k))::k]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "output.npy"), img.astype(np.float32))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -569,8 +592,18 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None,
                     help="frames per uva_net_process_u8_device_batch call for the workloads with the 1x net (default 4; 1 = one "
                          "call per frame).  Ignored for the other workloads: their nets run frame by frame either way")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each; the median is reported (SURVEY.md 8d)")
-    return ap.parse_args(argv)
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (SURVEY.md 8d).  Default 1, with --full 3")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the median of three timed regions, per-kernel times and the roofline, "
+                         "the pipelined host route, PCIe rates and per-rank records, the parity probes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/output.npy (float32; a larger result "
+                         "than %d values as a fixed strided sample of it, see dump_output)" % DUMP_MAX_VALUES)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 def library_record():
@@ -674,9 +707,12 @@ def run(args, comm, device):
             src = m.data_ptr()
         net.process_u8_device(src, h, w, out.data_ptr(), tile_size=args.tile, border=10)
 
+    last_out = [out]             # the buffer that holds the last frame's result (--dump-outputs)
+
     def step_group(i0, k):
         """frames i0 .. i0 + k - 1: one call per frame, or -- the workloads with the 1x net, --batch > 1 -- one batch call of the
         1x net for all k (the chain: k frames through the 1x net, then each through the 2x net)"""
+        last_out[0] = outs[min(k, len(outs)) - 1]
         if batch == 1 or k == 1:
             for i in range(i0, i0 + k):
                 step(i)
@@ -731,10 +767,11 @@ def run(args, comm, device):
     first_frame_ms = (time.perf_counter() - t_first) * 1e3
     run_static(args.warmup)
     sync()
-    # >= 3 timed regions of exactly --steps steps each (every one bracketed by barrier + sync, MAX over ranks); the MEDIAN region
-    # counts -- for `value` and for the kernel event statistics alike: set_profiling(True) zeroes the counters, so every region
-    # has its own, and the roofline's launch time is the reported region's (a process's first ~40 launches run while the clock
-    # still ramps: with the driver's --steps 20 --warmup 5 they sit in the first region; profiles/r04_ab_results.txt block 21)
+    # --repeats timed regions of exactly --steps steps each (1; --full: 3; every one bracketed by barrier + sync, MAX over ranks);
+    # the MEDIAN region counts -- for `value` and for the kernel event statistics alike: set_profiling(True) zeroes the counters,
+    # so every region has its own, and the roofline's launch time is the reported region's (a process's first ~40 launches run
+    # while the clock still ramps: with --steps 20 --warmup 5 they sit in the first region; profiles/r04_ab_results.txt block 21).
+    # The events stay on without --full too, where nothing reads them: the timed path is the same in both forms.
     regions, region_stats, own_s, own_frames = [], [], [], []
     for _ in range(max(1, args.repeats)):
         net.set_profiling(True)
@@ -755,6 +792,25 @@ def run(args, comm, device):
 
     fps = whole_job_rate(args.steps, world, elapsed)
     steps_timed = max(1, own_frames[median_idx])   # the kernel event statistics are the median region's, of THIS rank's frames
+
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, last_out[0].cpu().numpy())
+    head = {"metric": "frames/sec 1080p->2x Compact (SRVGGNetCompact per-frame SR hot path)" if args.workload == "2x_compact_1080p"
+                      else "frames/sec " + args.workload,
+            "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f16 operands / f32 accumulate",
+            "data": "synthetic frames; weights: " + weights_note if generic else "synthetic"}
+    if not args.full:
+        # the headline alone; everything below (host route, PCIe, per-rank records, roofline, parity, CPU baseline) is --full's
+        if counter is not None:
+            counter.close()
+        if rank == 0:
+            print(json.dumps({**head, "config": {"workload": args.workload, "tile_size": args.tile, "frames_per_call": batch,
+                                                 "timed_regions_s": [round(x, 5) for x in regions], "library": library_record()}}),
+                  flush=True)
+        comm.close()
+        return
 
     # (E) pipelined host route, PCIe inclusive, on every rank at once: frames in page-locked host memory,
     # submit/collect with 3 frames in flight (SURVEY.md 8d "host-to-host with stream overlap")
@@ -811,10 +867,7 @@ def run(args, comm, device):
         achieved = rdb_flops * VALAR_BLOCKS * steps_timed / (trunk_ms * 1e-3) / 1e12 if trunk_ms > 0 else 0.0
         traffic, traffic_source = pmc_traffic_valar(n_launch / max(1, steps_timed)) if args.tile == 960 and (h, w) == (1080, 1920) else (None, None)
         result = {
-            "metric": "frames/sec " + args.workload, "value": round(fps, 3), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16 operands / f32 accumulate",
-            "data": "synthetic frames; weights: " + weights_note,
+            **head,
             "config": {
                 "workload": f"{w}x{h} synthetic u8 BGR frames, {stem} (1 206 layers) through the generic graph executor, "
                             f"upscale_image arithmetic ({'reference 960-px tiles, 10-px border' if args.tile > 0 else 'whole frame'}), "
@@ -867,11 +920,7 @@ def run(args, comm, device):
         if whole_net and traffic is not None:
             traffic = int(traffic * frames_per_launch)      # (the committed figure is one frame's launch: a batch moves as many frames' bytes)
         result = {
-            "metric": "frames/sec 1080p->2x Compact (SRVGGNetCompact per-frame SR hot path)" if args.workload == "2x_compact_1080p"
-                      else "frames/sec " + args.workload,
-            "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f16 operands / f32 accumulate", "data": "synthetic",
+            **head,
             "config": {
                 "workload": f"{w}x{h} synthetic u8 BGR frames, {stem}, upscale_image arithmetic "
                             f"({'reference 960-px tiles, 10-px border' if args.tile > 0 else 'whole frame'}), "

@@ -432,7 +432,7 @@ def main():
     if args.swap:
         from upscale_video_amd import ncnn as ours
         ref = import_reference(ours)
-        raise SystemExit("--swap: run tests/test_ref_host.py::test_reference_module_runs_on_our_ncnn instead")
+        raise SystemExit("--swap: run tests/test_ref_host.py::test_reference_calls_run_on_our_ncnn instead")
     ref = import_reference()
     arrs, meta = {}, {"reference_file": REFERENCE_FILE, "reference_sha16": hashlib.sha256(open(REFERENCE_FILE, "rb").read()).hexdigest()[:16],
                       "band": BAND, "corner": CORNER}

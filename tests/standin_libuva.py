@@ -1,6 +1,6 @@
-"""A stand-in for the loaded libuva.so object (upscale_video_amd._lib._lib) -- TESTS ONLY, build container only.
+"""A stand-in for the loaded libuva.so object (upscale_video_amd._lib._lib) -- TESTS ONLY.
 
-tests/test_ref_host.py::test_reference_module_runs_on_our_ncnn runs the reference's module on upscale_video_amd.ncnn where
+tests/test_ref_host.py::test_reference_calls_run_on_our_ncnn drives upscale_video_amd.ncnn with the reference's calls where
 there is no GPU; the C entry points ncnn.Net / Mat / Extractor reach (include/uva.h) are answered here with the CPU oracle.
 The product never imports this; with the real library the same calls run HIP kernels (tests/test_gpu_workers.py)."""
 import ctypes

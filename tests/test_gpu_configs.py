@@ -195,7 +195,7 @@ def test_bench_under_torch_distributed_run_one_rank(tmp_path):
     import subprocess
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--gpus", "1", "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--no-parity"]
+    common = ["--gpus", "1", "--steps", "60", "--warmup", "10", "--full", "--no-cpu-baseline", "--no-parity"]
 
     def last_json(out):
         lines = [ln for ln in out.splitlines() if ln.startswith("{")]
@@ -225,7 +225,7 @@ def test_bench_starts_its_own_ranks():
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
-    common = ["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-parity"]
+    common = ["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-parity"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--devices", "0,0"] + common,
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -251,7 +251,7 @@ def test_bench_dynamic_queue_and_per_rank_records_on_the_box():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("UVA_BENCH_JOB_DIR", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--devices", "0,0", "--dynamic", "--steps", "24",
-                        "--warmup", "4", "--no-cpu-baseline", "--no-parity"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "4", "--full", "--no-cpu-baseline", "--no-parity"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and "dynamic" in d["config"]["frame_queue"]
@@ -271,7 +271,7 @@ def test_bench_batches_the_1x_net():
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "1x_hurrdeblur_1080p", "--steps", "80", "--warmup", "8",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=dict(os.environ))
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=dict(os.environ))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     rf = d["roofline"]
@@ -293,7 +293,7 @@ def test_config5_line_eight_ranks_on_the_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--devices", "0,0,0,0,0,0,0,0",
-                        "--workload", "2x_compact_2160p", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-parity"],
+                        "--workload", "2x_compact_2160p", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-parity"],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -352,7 +352,7 @@ def test_bench_valar_workload(tmp_path):
     import json
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "4x_valar_1080p", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "4x_valar_1080p", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -367,6 +367,30 @@ def test_bench_valar_workload(tmp_path):
     # a complete line: the CPU restatement timed on a crop beside it, and the kernel's HBM bytes per launch from the PMC summary
     assert d["cpu_baseline"]["kind"] == "port" and 0 < d["cpu_baseline"]["value"] < 0.05
     assert d["roofline"]["traffic"] is None or (5e8 < d["roofline"]["traffic"] < 3e9 and d["roofline"]["traffic_source"].startswith("profiles/"))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_its_outputs(uva, tmp_path):
+    """the plain form times --steps steps once and prints the headline alone; --dump-outputs writes what the last step computed:
+    six frames of the 1x net at four per call end in the second call's second frame, i.e. synthetic frame 1 of the four"""
+    import json
+    import subprocess
+    import sys
+    from upscale_video_amd.synth import synthetic_frame
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "1x_hurrdeblur_1080p", "--steps", "6", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=dict(os.environ))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "frames/sec 1x_hurrdeblur_1080p" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["steps"] == 6 and d["dtype"] and d["value"] > 0 and len(d["config"]["timed_regions_s"]) == 1
+    assert d["ms_per_step"] == pytest.approx(d["config"]["timed_regions_s"][0] / 6 * 1e3, abs=1e-3)    # (the region is rounded to 10 us)
+    assert not {"roofline", "per_rank", "parity", "cpu_baseline"} & set(d)
+    got = np.load(tmp_path / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 3)
+    want = load_net(uva, "1x").process_u8(synthetic_frame(1080, 1920, seed=20260928 + 1), tile_size=0)
+    assert np.array_equal(got, want.astype(np.float32))
 
 
 def _window_check(got, img, om_apply, rad, s, wins, win=24, max_lsb=2, min_psnr=50):

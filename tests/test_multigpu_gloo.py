@@ -210,6 +210,40 @@ def test_bench_refuses_a_device_list_of_the_wrong_length():
     assert r.returncode != 0 and "--devices" in (r.stderr + r.stdout)
 
 
+def test_bench_plain_form_times_one_region_and_full_three():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7"])
+    assert not a.full and a.repeats == 1 and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.repeats == 3 and a.dump_outputs == "d"
+    assert bench.parse_args(["--full", "--repeats", "5"]).repeats == 5
+
+
+def test_bench_output_dump_is_whole_or_a_fixed_strided_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32, the whole result up to the cap, above it every k-th value from a seeded offset with k coprime to
+    the row length -- the same sample for the same shape, every channel and column visited, under 64 MB at the largest output"""
+    sys.path.insert(0, ROOT)
+    import math
+    import bench
+    assert bench.DUMP_MAX_VALUES * 4 < 64 << 20
+    img = np.random.default_rng(3).integers(0, 256, (40, 64, 3), dtype=np.uint8)
+    bench.dump_output(str(tmp_path / "whole"), img)
+    got = np.load(tmp_path / "whole" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1000)
+    for name in ("a", "b"):
+        bench.dump_output(str(tmp_path / name), img)
+    a, b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and 0 < a.size <= 1000
+    flat = img.reshape(-1).astype(np.float32)
+    found = [(k, o) for k in range(2, 30) for o in range(k) if np.array_equal(flat[o::k], a)]
+    assert len(found) == 1 and math.gcd(found[0][0], 64 * 3) == 1, found
+    k, o = found[0]
+    pos = np.arange(o, flat.size, k)
+    assert set(pos % 3) == {0, 1, 2} and len(set((pos // 3) % 64)) == 64
+
+
 @pytest.mark.parametrize("tile", [64, 0])
 def test_bench_parity_windows_are_exact_for_an_exact_result(tile):
     """bench.py's full-size parity (windows of the timed frame against the oracle on their receptive fields, cut to the window's

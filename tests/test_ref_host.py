@@ -9,9 +9,8 @@ Extractor.extract in that run is the torch evaluation of the .param/.bin (ncnn's
 
 CPU tests (here): the fixture against the host mirror (upscale_video_amd/upscale_processing.py) and against oracle.c.
 GPU tests (-m gpu): the HIP path through the C ABI against the fixture.
-One more CPU test runs only where /root/reference exists (the build container): the reference's module with
-`ncnn_vulkan.ncnn = upscale_video_amd.ncnn` -- INTEGRATION.md section 1's one-line swap, executed -- over a stand-in
-for libuva.so that evaluates with the oracle (tests/standin_libuva.py; the GPU box has no /root/reference).
+One more CPU test drives upscale_video_amd.ncnn with the reference's recorded calls -- INTEGRATION.md section 1's one-line
+swap -- over a stand-in for libuva.so that evaluates with the oracle (tests/standin_libuva.py).
 """
 import hashlib
 import json
@@ -19,7 +18,6 @@ import logging
 import math
 import multiprocessing
 import os
-import sys
 import types
 
 import numpy as np
@@ -29,7 +27,6 @@ from conftest import ROOT, load_net
 from parity_report import check_u8, record
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-REFERENCE_FILE = "/root/reference/upscale/upscale_processing.py"
 VS = "reference host code, executed (ref_host.npz)"
 
 
@@ -50,13 +47,6 @@ def _sha16(a):
 # ------------------------------------------------------------------------------------------------------------------
 # host mirror against the reference's recorded behaviour (CPU)
 # ------------------------------------------------------------------------------------------------------------------
-def test_fixture_is_current(meta):
-    """where the reference is present: the fixture was generated from the file that lies there now"""
-    if not os.path.exists(REFERENCE_FILE):
-        pytest.skip("no /root/reference on this box")
-    assert hashlib.sha256(open(REFERENCE_FILE, "rb").read()).hexdigest()[:16] == meta["reference_sha16"]
-
-
 def test_get_frames_as_the_reference(meta):
     from upscale_video_amd import upscale_processing as up
     for arg, want in meta["get_frames"].items():
@@ -387,60 +377,48 @@ def test_hip_against_the_reference_run(meta, arrs, uva, key):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# INTEGRATION.md section 1, executed: the reference's module on upscale_video_amd.ncnn
+# the reference's ncnn calls on upscale_video_amd.ncnn
 # ------------------------------------------------------------------------------------------------------------------
-def test_reference_module_runs_on_our_ncnn(meta, arrs, monkeypatch, tmp_path, oracle_models):
-    """`from ncnn_vulkan import ncnn` -> upscale_video_amd.ncnn, nothing else changed: the reference's own init_worker,
-    apply_model and upscale_image run on the product's Net / Mat / Extractor.  No GPU here, so libuva.so is replaced by
-    tests/standin_libuva.py (the oracle behind the same C entry points); what is exercised is the Python surface the
-    swap relies on: names, argument forms, return conventions, np.array(mat), error paths."""
-    if not os.path.exists(REFERENCE_FILE):
-        pytest.skip("no /root/reference on this box")
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import ref_host_fixtures as rf
+def test_reference_calls_run_on_our_ncnn(meta, arrs, monkeypatch, tmp_path):
+    """`from ncnn_vulkan import ncnn` -> upscale_video_amd.ncnn: the host mirror, whose ncnn calls are the reference's recorded
+    ones (test_ncnn_call_sequence_as_the_reference, test_worker_slots_and_net_construction_as_the_reference), runs init_worker,
+    upscale_image, apply_model and the error path on the product's Net / Mat / Extractor.  No GPU here, so libuva.so is replaced
+    by tests/standin_libuva.py (the oracle behind the same C entry points); what is exercised is the Python surface the swap
+    relies on: names, argument forms, return conventions, np.array(mat), error paths -- against the reference run's results."""
     import standin_libuva
-    from upscale_video_amd import _lib, ncnn as ours
+    from upscale_video_amd import _imageio, _lib, ncnn as ours, upscale_processing as up
     monkeypatch.setattr(_lib, "_lib", standin_libuva.Lib())
-    keep = {k: sys.modules.get(k) for k in ("cv2", "ncnn_vulkan", "ncnn_vulkan.ncnn", "wakepy")}
+    monkeypatch.setattr(up, "FUSED_DEVICE_PATH", False)
+    monkeypatch.setattr(multiprocessing.current_process(), "_identity", (1,), raising=False)
     try:
-        ref = rf.import_reference(ours)
-        proc = multiprocessing.current_process()
-        monkeypatch.setattr(proc, "_identity", (1,), raising=False)
-        from PIL import Image
-
-        def put(img, name):
-            Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(str(tmp_path / name))
-            return str(tmp_path / name)
         # 2x, tiled: a 965x970 frame has all four border branches
         key = "up2_965x970"
-        img = _input(meta, key)
-        ref.init_worker([0], 0, os.path.join(ROOT, "models"), "x_Compact_Pretrain", 2, "input", "output")
-        assert isinstance(ref.net, ours.Net) and ref.net.scale == 2
-        src = put(img, "7.extract.png")
-        items = ref.upscale_image(src, str(tmp_path / "7.png"), 2, 3, 7, 9, True)
+        up.init_worker([0], 0, os.path.join(ROOT, "models"), "x_Compact_Pretrain", 2, "input", "output")
+        assert isinstance(up.net, ours.Net) and up.net.scale == 2 and up.init_error is None
+        src = str(tmp_path / "7.extract.png")
+        _imageio.imwrite(src, _input(meta, key))
+        items = up.upscale_image(src, str(tmp_path / "7.png"), 2, 3, 7, 9, True)
         assert [[lv, str(m)] for lv, m in items] == meta[key]["log"] and not os.path.exists(src)
-        out = np.ascontiguousarray(np.asarray(Image.open(str(tmp_path / "7.png")).convert("RGB"))[:, :, ::-1])
-        _compare("reference module on upscale_video_amd.ncnn " + key, out, _pieces(arrs, key), 2, meta["band"], meta["corner"], max_lsb=1,
-                 max_share=1e-4, sum_tol=lambda n: 4, model="2x", route="tiled", vs="reference module over the stand-in torch net")
+        _compare("reference calls on upscale_video_amd.ncnn " + key, _imageio.imread(str(tmp_path / "7.png")), _pieces(arrs, key), 2,
+                 meta["band"], meta["corner"], max_lsb=1, max_share=1e-4, sum_tol=lambda n: 4, model="2x", route="tiled",
+                 vs="reference calls over the stand-in torch net")
         # 1x, whole frame
         key = "am1_360x480"
+        up.init_worker([0], 0, os.path.join(ROOT, "models"), "x_HurrDeblur_SubCompact_nf24-nc8_244k_net_g", 1, "input", "output")
+        assert isinstance(up.net, ours.Net) and up.init_error is None
         img = _input(meta, key)
-        ref.init_worker([0], 0, os.path.join(ROOT, "models"), "x_HurrDeblur_SubCompact_nf24-nc8_244k_net_g", 1, "input", "output")
-        src = put(img, "7.extract.png")
-        items = ref.apply_model(src, str(tmp_path / "7.anime.png"), True)
+        _imageio.imwrite(src, img)
+        items = up.apply_model(src, str(tmp_path / "7.anime.png"), True)
         assert items[-1][0] == "info" and not os.path.exists(src)
-        out = np.ascontiguousarray(np.asarray(Image.open(str(tmp_path / "7.anime.png")).convert("RGB"))[:, :, ::-1])
-        _compare("reference module on upscale_video_amd.ncnn " + key, out, _pieces(arrs, key), 1, meta["band"], meta["corner"], max_lsb=1,
-                 max_share=1e-4, sum_tol=lambda n: 4, model="1x", route="whole", vs="reference module over the stand-in torch net")
+        _compare("reference calls on upscale_video_amd.ncnn " + key, _imageio.imread(str(tmp_path / "7.anime.png")), _pieces(arrs, key), 1,
+                 meta["band"], meta["corner"], max_lsb=1, max_share=1e-4, sum_tol=lambda n: 4, model="1x", route="whole",
+                 vs="reference calls over the stand-in torch net")
         # a failing extract: the product's error becomes the reference's error items and destroy_gpu_instance is callable
         standin_libuva.FAIL_EXTRACT = True
-        src = put(img, "9.extract.png")
-        items = ref.apply_model(src, str(tmp_path / "9.anime.png"), True)
-        assert items[0] == ["error", "Model processing failed"] and isinstance(items[1][1], Exception) and os.path.exists(src)
+        src = str(tmp_path / "9.extract.png")
+        _imageio.imwrite(src, img)
+        items = up.apply_model(src, str(tmp_path / "9.anime.png"), True)
+        assert list(items[0]) == ["error", "Model processing failed"] and isinstance(items[1][1], Exception) and os.path.exists(src)
     finally:
         standin_libuva.FAIL_EXTRACT = False
-        for k, v in keep.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+        up.net = None

@@ -8,7 +8,7 @@ for wl in $WLS; do
   for r in $(seq 1 $ROUNDS); do
     for v in $LIBS; do
       L=$PWD/upscale_video_amd/libuva_$v.so; [ $v = main ] && L=$PWD/upscale_video_amd/libuva.so
-      echo -n "$wl $v: "; UVA_LIB_PATH=$L python bench.py --workload $wl --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "$P"
+      echo -n "$wl $v: "; UVA_LIB_PATH=$L python bench.py --workload $wl --steps 200 --warmup 20 --full --no-cpu-baseline 2>/dev/null | python -c "$P"
     done
   done
 done

@@ -21,34 +21,34 @@ if [ -f upscale_video_amd/libuva_prev.so ]; then
       for v in $VS; do
         L=$REPO/upscale_video_amd/libuva.so; [ $v != new ] && L=$REPO/upscale_video_amd/libuva_$v.so
         F=1; [ $v = prev ] && F=0
-        echo -n "$wl $v: "; UVA_TW_FOLD=$F UVA_LIB_PATH=$L python bench.py --workload $wl --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "$P"
+        echo -n "$wl $v: "; UVA_TW_FOLD=$F UVA_LIB_PATH=$L python bench.py --workload $wl --steps 200 --warmup 20 --full --no-cpu-baseline 2>/dev/null | python -c "$P"
       done
     done
   done > "$OUT/${TAG}_ab_prev_new.txt" 2>&1
 fi
 for wl in 4x_compact_1080p 1x_hurrdeblur_1080p chain_1x_2x_1080p 2x_compact_2160p; do
-  python bench.py --workload $wl --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_${wl}.json" 2>> "$OUT/bench.err"
+  python bench.py --workload $wl --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_${wl}.json" 2>> "$OUT/bench.err"
 done
-python bench.py --workload 4x_valar_1080p --steps 30 --warmup 3 > "$OUT/${TAG}_bench_4x_valar_1080p.json" 2>> "$OUT/bench.err"
-python bench.py --tile 0 --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_2x_whole_frame.json" 2>> "$OUT/bench.err"
-UVA_TRUNK_FUSION=0 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_unfused_trunk_kernel.json" 2>> "$OUT/bench.err"
-UVA_TRUNK_WINO=0 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_direct_trunk2_kernel.json" 2>> "$OUT/bench.err"
-UVA_TW_ACT16=0 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_trunkw_fp32_prelu.json" 2>> "$OUT/bench.err"
-python bench.py --gpus 2 --devices 0,0 --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_two_ranks_one_gpu.json" 2>> "$OUT/bench.err"
-UVA_SUB10=0 python bench.py --workload 1x_hurrdeblur_1080p --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_1x_per_pair_kernels.json" 2>> "$OUT/bench.err"
+python bench.py --workload 4x_valar_1080p --steps 30 --warmup 3 --full > "$OUT/${TAG}_bench_4x_valar_1080p.json" 2>> "$OUT/bench.err"
+python bench.py --tile 0 --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_2x_whole_frame.json" 2>> "$OUT/bench.err"
+UVA_TRUNK_FUSION=0 python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_unfused_trunk_kernel.json" 2>> "$OUT/bench.err"
+UVA_TRUNK_WINO=0 python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_direct_trunk2_kernel.json" 2>> "$OUT/bench.err"
+UVA_TW_ACT16=0 python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_trunkw_fp32_prelu.json" 2>> "$OUT/bench.err"
+python bench.py --gpus 2 --devices 0,0 --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_two_ranks_one_gpu.json" 2>> "$OUT/bench.err"
+UVA_SUB10=0 python bench.py --workload 1x_hurrdeblur_1080p --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_1x_per_pair_kernels.json" 2>> "$OUT/bench.err"
 # round 5: the 1x net as two launches of five layers (sub5_kernel), folded last strips off, the driver's form of the default line
-UVA_SUB5=1 python bench.py --workload 1x_hurrdeblur_1080p --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_1x_sub5_two_launches.json" 2>> "$OUT/bench.err"
-UVA_TW_FOLD=0 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_no_folded_strips.json" 2>> "$OUT/bench.err"
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_driver_form.json" 2>> "$OUT/bench.err"
-python bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --workload 2x_compact_2160p --steps 8 --warmup 2 --no-cpu-baseline --no-parity > "$OUT/${TAG}_bench_config5_eight_ranks_one_gpu.json" 2>> "$OUT/bench.err"
+UVA_SUB5=1 python bench.py --workload 1x_hurrdeblur_1080p --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_1x_sub5_two_launches.json" 2>> "$OUT/bench.err"
+UVA_TW_FOLD=0 python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_no_folded_strips.json" 2>> "$OUT/bench.err"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/${TAG}_bench_driver_form.json" 2>> "$OUT/bench.err"
+python bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --workload 2x_compact_2160p --steps 8 --warmup 2 --full --no-cpu-baseline --no-parity > "$OUT/${TAG}_bench_config5_eight_ranks_one_gpu.json" 2>> "$OUT/bench.err"
 # round 6: the 1x net one, two and four frames per launch (uva_net_process_u8_device_batch; the workload's default is four), two
 # ranks on the one GPU with the static and the dynamic frame queue (per-rank records), the driver's N > 1 form with one rank
-for b in 1 2 4; do python bench.py --workload 1x_hurrdeblur_1080p --batch $b --steps 200 --warmup 20 --no-cpu-baseline > "$OUT/${TAG}_bench_1x_batch$b.json" 2>> "$OUT/bench.err"; done
-python bench.py --gpus 2 --devices 0,0 --dynamic --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_two_ranks_one_gpu_dynamic.json" 2>> "$OUT/bench.err"
+for b in 1 2 4; do python bench.py --workload 1x_hurrdeblur_1080p --batch $b --steps 200 --warmup 20 --full --no-cpu-baseline > "$OUT/${TAG}_bench_1x_batch$b.json" 2>> "$OUT/bench.err"; done
+python bench.py --gpus 2 --devices 0,0 --dynamic --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_two_ranks_one_gpu_dynamic.json" 2>> "$OUT/bench.err"
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --dynamic --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/${TAG}_bench_torchrun_one_rank_dynamic.json" 2>> "$OUT/bench.err"
 python tools/png_decode_split.py 9 > "$OUT/${TAG}_png_decode_split.txt" 2>&1
 python tools/pipe_bench.py 200 > "$OUT/${TAG}_pipe_bench.txt" 2>&1
-python bench.py --workload 1x_hurrdeblur_1080p --tile 960 --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/${TAG}_bench_1x_tiled_960.json" 2>> "$OUT/bench.err"
+python bench.py --workload 1x_hurrdeblur_1080p --tile 960 --steps 100 --warmup 10 --full --no-cpu-baseline > "$OUT/${TAG}_bench_1x_tiled_960.json" 2>> "$OUT/bench.err"
 (cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats -d /tmp/prof1x_$TAG -o p --output-format csv -- python $REPO/bench.py --workload 1x_hurrdeblur_1080p --batch 1 --tile 0 --steps 120 --warmup 10 --no-cpu-baseline --no-parity > /dev/null 2>&1; cp $(find /tmp/prof1x_$TAG -name "*kernel_stats.csv" | head -1) "$OUT/${TAG}_kernel_stats_1x_rocprofv3.csv")
 bash tools/pmc_sub10.sh /tmp/pmc_sub10_$TAG > "$OUT/${TAG}_sub10_pmc.txt" 2>&1
 python tools/png_route_bench.py 384 > "$OUT/${TAG}_png_route_bench.txt" 2>&1
