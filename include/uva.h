@@ -40,7 +40,9 @@ extern "C" {
                                13: + uva_denoise_u8_device, uva_denoise_synchronize;
                                14: + uva_net_device, uva_debug_sub5_rows (sub5_kernel: the 1x net as two launches of five layers);
                                15: + uva_net_process_u8_device_batch (several frames of one geometry per call; the 1x net takes up to
-                                   eight per launch), uva_debug_sub10_rows_batch */
+                                   eight per launch), uva_debug_sub10_rows_batch;
+                               15 + pixel formats: + uva_pix_frame_bytes, uva_net_submit_pix, uva_pix_convert, uva_pix_convert_device
+                                   (additive: every entry point of 15 is unchanged) */
 
 typedef struct uva_net uva_net;
 
@@ -121,6 +123,43 @@ int uva_net_collect_u8(uva_net* net, long long ticket);
 /* Page-locked host memory for frames handed to the two calls above (no staging copy). */
 void* uva_host_alloc(size_t bytes);
 void uva_host_free(void* p);
+
+/* ---- raw-video pixel formats (csrc/uva_pixfmt.hip; the arithmetic: DESIGN.md section 7.3) ------------------- */
+
+/* ffmpeg's rawvideo layouts, dense planes without row padding, chroma cw = ceil(w/2) x ch = ceil(h/2):
+ *   UVA_PIX_BGR24    u8 [h][w][3] (what every _u8 call above takes)                 3wh bytes
+ *   UVA_PIX_YUV420P  Y u8 [h][w], then U [ch][cw], then V [ch][cw]                  wh + 2 cw ch
+ *   UVA_PIX_NV12     Y u8 [h][w], then [ch][cw][2] interleaved U, V                 wh + 2 cw ch
+ *   UVA_PIX_P010LE   nv12's layout in little-endian 16-bit words, value << 6        2 (wh + 2 cw ch)
+ * colour = UVA_CSP_BT601 or UVA_CSP_BT709, | UVA_RANGE_FULL for full ("pc") range instead of limited ("tv": Y 16-235,
+ * C 16-240, x4 at 10 bits).  BGR -> Y'CbCr: fixed-point textbook formulas, chroma of a 2x2 block from the block's sums;
+ * Y'CbCr -> BGR: chroma replicated over its 2x2 block.  The reference's frames are untagged rgb24 PNGs, which ffmpeg merges
+ * as BT.601 limited range (upscale/upscale_processing.py:604-640): colour 0. */
+#define UVA_PIX_BGR24 0
+#define UVA_PIX_YUV420P 1
+#define UVA_PIX_NV12 2
+#define UVA_PIX_P010LE 3
+#define UVA_CSP_BT601 0
+#define UVA_CSP_BT709 1
+#define UVA_RANGE_FULL 2
+/* Bytes of one dense h x w frame of `fmt`; 0 for an unknown format or a size <= 0. */
+size_t uva_pix_frame_bytes(int fmt, int h, int w);
+/* uva_net_submit_u8 with a pixel format on either end, collected by uva_net_collect_u8: `in` holds one dense frame of
+ * in_fmt (h x w), `out` receives one dense frame of out_fmt (h*s x w*s).  The packed frame is copied to the device, converted
+ * to u8 BGR in front of the net and the net's u8 result converted to out_fmt behind it, both on the net's stream; the packed
+ * result is copied back.  Slots, streams, the 3 frames in flight and the pinned / pageable rules are uva_net_submit_u8's.
+ * BGR24 on both ends gives uva_net_submit_u8's bytes. */
+long long uva_net_submit_pix(uva_net* net, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
+                             int tile_size, int border);
+/* Host to host on HIP device `device`, synchronous: one dense h x w frame of in_fmt -> out_fmt (through u8 BGR when neither
+ * is BGR24; a copy when both are equal).  For tests, a lane whose first stage is `-m n=K` (the denoise stage takes host BGR)
+ * and `-s 1` without a net. */
+int uva_pix_convert(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour);
+/* The same with d_in / d_out resident in `device`'s HBM, asynchronous on the conversion's own stream; `after` / `before`
+ * (may be null) as in uva_denoise_u8_device.  The frame is done once uva_net_synchronize(before) or a later uva_pix_convert
+ * on the same device (same stream) has returned. */
+int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out, int out_fmt, int h, int w, int colour,
+                           uva_net* after, uva_net* before);
 
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 

@@ -18,6 +18,8 @@ SYMBOLS = [
     "uva_net_wait_for", "uva_net_submit_u8", "uva_net_collect_u8", "uva_host_alloc", "uva_host_free",
     "uva_net_debug_read_activation", "uva_net_set_profiling", "uva_net_kernel_stats",
     "uva_net_debug_packed_weights", "uva_last_error", "uva_abi_version",
+    # 15 + pixel formats (additive; an older ABI-15 build lacks them: load() then declares what it has, see UVA_ALLOW_OLD_ABI)
+    "uva_pix_frame_bytes", "uva_net_submit_pix", "uva_pix_convert", "uva_pix_convert_device",
 ]
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -71,6 +73,10 @@ def load():
     decl("uva_net_submit_u8", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i], ctypes.c_longlong)
     decl("uva_net_submit_u8_png", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i], ctypes.c_longlong)
     decl("uva_png_workspace_bytes", [c_i, c_i], c_sz)
+    decl("uva_pix_frame_bytes", [c_i, c_i, c_i], c_sz)
+    decl("uva_net_submit_pix", [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i], ctypes.c_longlong)
+    decl("uva_pix_convert", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i])
+    decl("uva_pix_convert_device", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p])
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

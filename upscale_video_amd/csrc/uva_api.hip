@@ -10,6 +10,7 @@
 #include "uva_generic.hip.h"
 #include "uva_kernels.hip.h"
 #include "uva_model.h"
+#include "uva_pixfmt.h"
 #include "uva_png.hip.h"
 #include "uva_wino.h"
 #include "uva_sub5.h"
@@ -186,7 +187,8 @@ struct uva_net {
         long long ticket = -1;
         uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;   // h_*: pinned staging
         uint8_t* d_png = nullptr;        // the PNG encoder's blocks: [meta][slots], then [the blocks packed end to end]
-        size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0, d_png_cap = 0;
+        uint8_t *d_pin = nullptr, *d_pout = nullptr;   // uva_net_submit_pix: the packed frames (d_in / d_out hold their BGR)
+        size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0, d_png_cap = 0, d_pin_cap = 0, d_pout_cap = 0;
         uint8_t* png_ws = nullptr;       // PNG submit: the caller's workspace, how many packed bytes went there with the
         size_t png_sent = 0;             // frame's download, and the frame size (collect fetches the rest, if any)
         int png_h = 0, png_w = 0;
@@ -244,6 +246,8 @@ struct uva_net {
             if (ps.d_in) (void)hipFree(ps.d_in);
             if (ps.d_out) (void)hipFree(ps.d_out);
             if (ps.d_png) (void)hipFree(ps.d_png);
+            if (ps.d_pin) (void)hipFree(ps.d_pin);
+            if (ps.d_pout) (void)hipFree(ps.d_pout);
             if (ps.h_in) (void)hipHostFree(ps.h_in);
             if (ps.h_out) (void)hipHostFree(ps.h_out);
             if (ps.ev_h2d) (void)hipEventDestroy(ps.ev_h2d);
@@ -2155,6 +2159,80 @@ int check_dims(const uva_net* n, int h, int w)
 
 }  // namespace
 
+// ---- raw-video pixel formats outside a net (uva_pix_convert, uva_pix_convert_device; csrc/uva_pixfmt.hip) -----------
+namespace {
+
+struct PixCtx {                          // per device: the conversions' own stream and buffers
+    hipStream_t stream = nullptr;
+    uint8_t *d_in = nullptr, *d_mid = nullptr, *d_out = nullptr;
+    size_t in_cap = 0, mid_cap = 0, out_cap = 0;
+};
+std::mutex g_pix_mu;
+PixCtx g_pix[16];
+
+void pix_release_all()
+{
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    for (int d = 0; d < 16; ++d) {
+        PixCtx& c = g_pix[d];
+        if (!c.stream) continue;
+        (void)hipSetDevice(d);
+        (void)hipStreamSynchronize(c.stream);
+        for (uint8_t* p : {c.d_in, c.d_mid, c.d_out})
+            if (p) (void)hipFree(p);
+        (void)hipStreamDestroy(c.stream);
+        c = PixCtx();
+    }
+}
+
+int pix_ctx(int device, PixCtx** out)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail("no HIP device available: libuva has no CPU path");
+    if (device < 0 || device >= count || device >= 16) return fail("HIP device " + std::to_string(device) + " does not exist");
+    HIP_TRY(hipSetDevice(device));
+    PixCtx& c = g_pix[device];
+    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    *out = &c;
+    return 0;
+}
+
+// uva_pix_convert_device is asynchronous: frames queued on the stream may still use a buffer about to be replaced
+int pix_grow(PixCtx& c, uint8_t** p, size_t* cap, size_t bytes)
+{
+    if (*cap >= bytes) return 0;
+    if (*cap) HIP_TRY(hipStreamSynchronize(c.stream));
+    return grow_dev(p, cap, bytes);
+}
+
+int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, int w, int colour)
+{
+    if (!in || !out) return fail("null frame pointer");
+    if (h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image size");
+    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) return fail("unknown pixel format");
+    if (colour & ~PIX_COLOUR_MASK) return fail("bad colour word");
+    return 0;
+}
+
+// d_in (in_fmt) -> d_out (out_fmt) on the context's stream, through u8 BGR in d_mid when neither end is BGR24
+int pix_convert_launch(PixCtx& c, const uint8_t* d_in, int in_fmt, uint8_t* d_out, int out_fmt, int h, int w, int colour)
+{
+    if (in_fmt == out_fmt) {
+        HIP_TRY(hipMemcpyAsync(d_out, d_in, pix_frame_bytes(in_fmt, h, w), hipMemcpyDeviceToDevice, c.stream));
+    } else if (in_fmt == PIX_BGR24) {
+        HIP_TRY(launch_pix_from_bgr(c.stream, out_fmt, colour, d_in, d_out, h, w));
+    } else if (out_fmt == PIX_BGR24) {
+        HIP_TRY(launch_pix_to_bgr(c.stream, in_fmt, colour, d_in, d_out, h, w));
+    } else {
+        if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(PIX_BGR24, h, w))) return 1;
+        HIP_TRY(launch_pix_to_bgr(c.stream, in_fmt, colour, d_in, c.d_mid, h, w));
+        HIP_TRY(launch_pix_from_bgr(c.stream, out_fmt, colour, c.d_mid, d_out, h, w));
+    }
+    return 0;
+}
+
+}  // namespace
+
 // ---- `-m n=K`: non-local-means denoise (upscale/upscale_processing.py:350-361) -------------------------
 namespace {
 
@@ -2532,6 +2610,7 @@ void uva_destroy_gpu_instance(void)
     }
     denoise_release_all();
     png_release_all();
+    pix_release_all();
 }
 
 uva_net* uva_net_create(void)
@@ -2745,10 +2824,13 @@ void uva_host_free(void* p)
 
 }  // extern "C"
 namespace {
-// uva_net_submit_u8 (png_ws == nullptr: the result frame goes to `out`) and uva_net_submit_u8_png (the result frame stays
-// in HBM, its PNG deflate blocks go to the page-locked workspace png_ws)
+// uva_net_submit_u8 (png_ws == nullptr: the result frame goes to `out`), uva_net_submit_u8_png (the result frame stays
+// in HBM, its PNG deflate blocks go to the page-locked workspace png_ws) and uva_net_submit_pix (in_fmt / out_fmt other than
+// BGR24: the dense packed frame goes to d_pin and is converted into d_in on the net's stream, d_out is converted into d_pout
+// behind the net and d_pout comes back)
 long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out, size_t out_stride,
-                    int tile_size, int border, void* png_ws, size_t png_ws_bytes)
+                    int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
+                    int colour = 0)
 {
     if (check_dims(n, h, w)) return -1;
     if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
@@ -2760,6 +2842,9 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     if (png_ws) out_stride = out_row;
     if (in_stride < in_row || out_stride < out_row) { fail("row stride too small"); return -1; }
     const size_t in_bytes = in_row * h, out_bytes = out_row * (size_t)h * s;
+    const bool pin = in_fmt != PIX_BGR24, pout = out_fmt != PIX_BGR24;
+    const size_t pin_bytes = pix_frame_bytes(in_fmt, h, w), pout_bytes = pix_frame_bytes(out_fmt, h * s, w * s);
+    if (pout_bytes > (size_t)INT_MAX) { fail("result frame of 2 GB or more"); return -1; }
     uva_net::PipeSlot* free_slot = nullptr;
     for (auto& c : n->pipe)
         if (!c.busy) { free_slot = &c; break; }
@@ -2775,6 +2860,7 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
             tryhip(hipEventCreateWithFlags(&ps.ev_d2h, hipEventDisableTiming), "hipEventCreate")) return -1;
     }
     if (grow_dev(&ps.d_in, &ps.d_in_cap, in_bytes) || grow_dev(&ps.d_out, &ps.d_out_cap, out_bytes)) return -1;
+    if ((pin && grow_dev(&ps.d_pin, &ps.d_pin_cap, pin_bytes)) || (pout && grow_dev(&ps.d_pout, &ps.d_pout_cap, pout_bytes))) return -1;
     if (png_ws) {
         if (uva_png_workspace_bytes(h * s, w * s) == 0) { fail("PNG encoder: frame width out of range"); return -1; }
         if (png_ws_bytes < png_workspace_bytes(h * s, w * s)) { fail("PNG workspace too small"); return -1; }
@@ -2782,17 +2868,25 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     }
     // H2D: straight from the caller's buffer when it is pinned (uva_host_alloc / hipHostMalloc /
     // hipHostRegister), through this slot's pinned staging buffer otherwise
+    // (a packed frame goes as one row of pin_bytes)
     const uint8_t* src = in;
     size_t src_stride = in_stride;
+    const size_t h2d_row = pin ? pin_bytes : in_row;
+    const int h2d_rows = pin ? 1 : h;
     if (!is_pinned_host(in)) {
-        if (grow_host(&ps.h_in, &ps.h_in_cap, in_bytes)) return -1;
-        for (int y = 0; y < h; ++y) std::memcpy(ps.h_in + y * in_row, in + y * in_stride, in_row);
-        src = ps.h_in; src_stride = in_row;
+        if (grow_host(&ps.h_in, &ps.h_in_cap, pin ? pin_bytes : in_bytes)) return -1;
+        if (pin) std::memcpy(ps.h_in, in, pin_bytes);
+        else
+            for (int y = 0; y < h; ++y) std::memcpy(ps.h_in + y * in_row, in + y * in_stride, in_row);
+        src = ps.h_in; src_stride = h2d_row;
     }
-    if (tryhip(hipMemcpy2DAsync(ps.d_in, in_row, src, src_stride, in_row, h, hipMemcpyHostToDevice, n->s_h2d), "H2D") ||
+    if (tryhip(hipMemcpy2DAsync(pin ? ps.d_pin : ps.d_in, h2d_row, src, pin ? h2d_row : src_stride, h2d_row, h2d_rows,
+                                hipMemcpyHostToDevice, n->s_h2d), "H2D") ||
         tryhip(hipEventRecord(ps.ev_h2d, n->s_h2d), "hipEventRecord") ||
         tryhip(hipStreamWaitEvent(n->stream, ps.ev_h2d, 0), "hipStreamWaitEvent")) return -1;
+    if (pin && tryhip(launch_pix_to_bgr(n->stream, in_fmt, colour, ps.d_pin, ps.d_in, h, w), "pix_to_bgr")) return -1;
     if (uva_net_process_u8_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
+    if (pout && tryhip(launch_pix_from_bgr(n->stream, out_fmt, colour, ps.d_out, ps.d_pout, h * s, w * s), "pix_from_bgr")) return -1;
     // png: the deflate kernel follows the net on its stream and leaves the blocks in HBM, packed end to end by a second
     // (device-to-device) kernel: 0.15 ms per 4K frame together
     if (png_ws && (png_launch(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png) ||
@@ -2818,20 +2912,28 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     size_t dst_stride = out_stride;
     ps.user_out = nullptr;
     ps.png_ws = nullptr;
+    // what comes down: the BGR rows of d_out, or the packed frame d_pout -- as "rows" of one byte, so that a band is a byte
+    // range (collect copies it with one memcpy)
+    const uint8_t* d_src = pout ? ps.d_pout : ps.d_out;
+    const size_t dl_bytes = pout ? pout_bytes : out_bytes;
     if (!is_pinned_host(out)) {
-        if (grow_host(&ps.h_out, &ps.h_out_cap, out_bytes)) return -1;
+        if (grow_host(&ps.h_out, &ps.h_out_cap, dl_bytes)) return -1;
         dst = ps.h_out; dst_stride = out_row;
-        ps.user_out = out; ps.user_out_stride = out_stride; ps.out_row = out_row; ps.out_rows = h * s;
+        ps.user_out = out; ps.user_out_stride = pout ? 1 : out_stride; ps.out_row = pout ? 1 : out_row;
+        ps.out_rows = pout ? (int)pout_bytes : h * s;
     }
     if (ps.user_out) {
-        const int rows = h * s, per = (rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
+        const int rows = ps.out_rows, per = (rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
+        const size_t row = ps.out_row;
         for (int k = 0; k < uva_net::PipeSlot::BANDS; ++k) {
             if (!ps.ev_band[k] && tryhip(hipEventCreateWithFlags(&ps.ev_band[k], hipEventDisableTiming), "hipEventCreate")) return -1;
             const int r0 = std::min(rows, k * per), nr = std::min(rows, r0 + per) - r0;
-            if (nr > 0 && tryhip(hipMemcpyAsync(dst + (size_t)r0 * out_row, ps.d_out + (size_t)r0 * out_row, (size_t)nr * out_row,
+            if (nr > 0 && tryhip(hipMemcpyAsync(dst + (size_t)r0 * row, d_src + (size_t)r0 * row, (size_t)nr * row,
                                                 hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return -1;
             if (tryhip(hipEventRecord(ps.ev_band[k], n->s_d2h), "hipEventRecord")) return -1;
         }
+    } else if (pout) {
+        if (tryhip(hipMemcpyAsync(dst, d_src, dl_bytes, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return -1;
     } else if (tryhip(hipMemcpy2DAsync(dst, dst_stride, ps.d_out, out_row, out_row, (size_t)h * s, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) {
         return -1;
     }
@@ -2854,6 +2956,63 @@ long long uva_net_submit_u8_png(uva_net* n, const uint8_t* in, int h, int w, siz
 {
     if (!png_ws) { fail("null PNG workspace"); return -1; }
     return submit_u8(n, in, h, w, in_stride, nullptr, 0, tile_size, border, png_ws, png_ws_bytes);
+}
+
+size_t uva_pix_frame_bytes(int fmt, int h, int w) { return pix_frame_bytes(fmt, h, w); }
+
+int uva_pix_convert(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
+{
+    if (pix_check(in, in_fmt, out, out_fmt, h, w, colour)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
+    if (pix_convert_launch(*c, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out, int out_fmt, int h, int w, int colour,
+                           uva_net* after, uva_net* before)
+{
+    if (pix_check(d_in, in_fmt, d_out, out_fmt, h, w, colour)) return 1;
+    for (uva_net* n : {after, before})
+        if (n) {
+            if (ensure_device(n)) return 1;
+            if (n->device != device) return fail("uva_pix_convert_device: the net is on another device");
+        }
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    if (after) {                 // what `after` has been asked to do so far (it wrote d_in, or still reads d_out) comes first
+        SyncEventScope ev(after);
+        if (!ev.e) return 1;
+        HIP_TRY(hipEventRecord(ev.e, after->stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, ev.e, 0));
+    }
+    if (pix_convert_launch(*c, (const uint8_t*)d_in, in_fmt, (uint8_t*)d_out, out_fmt, h, w, colour)) return 1;
+    if (before) {                // ... and whatever `before` is asked to do from now on comes after this frame
+        SyncEventScope ev(before);
+        if (!ev.e) return 1;
+        HIP_TRY(hipEventRecord(ev.e, c->stream));
+        HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
+    }
+    return 0;
+}
+
+long long uva_net_submit_pix(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
+                             int tile_size, int border)
+{
+    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
+    if (colour & ~PIX_COLOUR_MASK) { fail("bad colour word"); return -1; }
+    if (check_dims(n, h, w)) return -1;
+    const int s = uva_net_scale(n);
+    if (s <= 0) { fail("net has no graph"); return -1; }
+    return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3, (uint8_t*)out, (size_t)w * s * 3, tile_size, border, nullptr, 0,
+                     in_fmt, out_fmt, colour);
 }
 
 size_t uva_png_workspace_bytes(int h, int w)

@@ -115,6 +115,59 @@ def png_encode_u8(img_bgr, gpu=0, workspace=None):
     return bytes(ws.file_bytes())
 
 
+# ---- raw-video pixel formats (include/uva.h UVA_PIX_*) -----------------------------------------
+PIX_FORMATS = {"bgr24": 0, "yuv420p": 1, "nv12": 2, "p010le": 3}     # ffmpeg's -pix_fmt names
+COLORSPACES = {"bt601": 0, "bt709": 1}                              # ffmpeg's -colorspace names
+COLOR_RANGES = {"tv": 0, "pc": 2}                                   # ffmpeg's -color_range names (limited, full)
+
+
+def pix_frame_bytes(fmt, h, w):
+    """bytes of one dense h x w rawvideo frame of `fmt` (chroma planes ceil(w/2) x ceil(h/2); include/uva.h uva_pix_frame_bytes)"""
+    if fmt not in PIX_FORMATS:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS)))
+    if h <= 0 or w <= 0:
+        raise ValueError("frame size must be positive")
+    c = 2 * ((w + 1) // 2) * ((h + 1) // 2)
+    return {"bgr24": 3 * w * h, "yuv420p": w * h + c, "nv12": w * h + c, "p010le": 2 * (w * h + c)}[fmt]
+
+
+def colour_word(colour="bt601", color_range="tv"):
+    """the C ABI's colour argument: UVA_CSP_* | UVA_RANGE_FULL"""
+    if colour not in COLORSPACES:
+        raise ValueError("unknown colorspace %r (%s)" % (colour, ", ".join(COLORSPACES)))
+    if color_range not in COLOR_RANGES:
+        raise ValueError("unknown color range %r (%s)" % (color_range, ", ".join(COLOR_RANGES)))
+    return COLORSPACES[colour] | COLOR_RANGES[color_range]
+
+
+def pix_empty(fmt, h, w, alloc=None):
+    """a buffer for one h x w frame of `fmt`: u8 [h][w][3] for bgr24, a flat u8 array of pix_frame_bytes otherwise.
+    `alloc(shape)` -> u8 array (default np.empty; pinned_empty for page-locked memory)"""
+    alloc = alloc or (lambda shape: np.empty(shape, np.uint8))
+    return alloc((h, w, 3)) if fmt == "bgr24" else alloc((pix_frame_bytes(fmt, h, w),))
+
+
+def _pix_frame(buf, fmt, h, w, what):
+    a = np.ascontiguousarray(buf)
+    if a.nbytes != pix_frame_bytes(fmt, h, w):
+        raise ValueError("%s holds %d bytes, a %dx%d %s frame has %d" % (what, a.nbytes, w, h, fmt, pix_frame_bytes(fmt, h, w)))
+    return a
+
+
+def convert_pix(buf, h, w, in_fmt, out_fmt, colour="bt601", color_range="tv", out=None, gpu=0):
+    """One dense h x w frame of in_fmt -> out_fmt on HIP device `gpu`, host to host, synchronous (include/uva.h
+    uva_pix_convert).  Returns `out` (u8 [h][w][3] for bgr24, flat u8 otherwise; allocated when None)."""
+    cw = colour_word(colour, color_range)
+    src = _pix_frame(buf, in_fmt, h, w, "input")
+    if out is None:
+        out = pix_empty(out_fmt, h, w)
+    if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(out_fmt, h, w):
+        raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, h, w))
+    _lib.check(_lib.load().uva_pix_convert(int(gpu), src.ctypes.data, PIX_FORMATS[in_fmt], out.ctypes.data, PIX_FORMATS[out_fmt],
+                                           h, w, cw))
+    return out
+
+
 class Ticket:
     """One frame in flight on the pipelined host route; keeps its buffers alive."""
 
@@ -304,8 +357,38 @@ class Net:
             raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
         return Ticket(t, img, out)
 
+    def submit_pix(self, buf, h, w, in_fmt, out=None, out_fmt="bgr24", colour="bt601", color_range="tv", tile_size=0, border=0):
+        """submit_u8 with a rawvideo pixel format on either end (include/uva.h uva_net_submit_pix): `buf` holds one dense
+        h x w frame of in_fmt, the result is one dense (h*s) x (w*s) frame of out_fmt; both conversions run on the GPU around
+        the net.  `out`: optional preallocated result buffer of pix_frame_bytes(out_fmt, h*s, w*s) bytes (pix_empty; pinned
+        memory avoids the staging copy).  Returns a Ticket that collect_u8 takes."""
+        for f in (in_fmt, out_fmt):
+            if f not in PIX_FORMATS:
+                raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(PIX_FORMATS)))
+        cw = colour_word(colour, color_range)
+        s = self.scale
+        if s <= 0:
+            raise _lib.UvaError("net has no graph: load_param/load_model failed or were not called")
+        src = _pix_frame(buf, in_fmt, h, w, "input")
+        if out is None:
+            out = pix_empty(out_fmt, h * s, w * s)
+        if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(out_fmt, h * s, w * s):
+            raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, h * s, w * s))
+        t = self._L.uva_net_submit_pix(self._h, src.ctypes.data, PIX_FORMATS[in_fmt], h, w, out.ctypes.data, PIX_FORMATS[out_fmt], cw,
+                                       int(tile_size), int(border))
+        if t < 0:
+            raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
+        return Ticket(t, src, out)
+
+    def convert_pix_device(self, d_in, h, w, in_fmt, d_out, out_fmt, colour="bt601", color_range="tv", after=None):
+        """A conversion of a frame in HBM queued IN FRONT of this net (include/uva.h uva_pix_convert_device), like
+        denoise_u8_device: `after` (a net, or None) comes first, this net's next work waits for the frame."""
+        _lib.check(self._L.uva_pix_convert_device(self.device_index, ctypes.c_void_p(d_in), PIX_FORMATS[in_fmt], ctypes.c_void_p(d_out),
+                                                  PIX_FORMATS[out_fmt], h, w, colour_word(colour, color_range),
+                                                  after._h if after is not None else None, self._h))
+
     def collect_u8(self, ticket):
-        """Waits for the frame of `ticket` and returns its u8 result array (submit_u8) or its PNG workspace
+        """Waits for the frame of `ticket` and returns its u8 result array (submit_u8, submit_pix) or its PNG workspace
         (submit_u8_png)."""
         _lib.check(self._L.uva_net_collect_u8(self._h, ticket.id))
         return ticket.out

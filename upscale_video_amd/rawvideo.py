@@ -1,4 +1,4 @@
-"""rawvideo.py -- stream bgr24 frames through the MI355X engine.
+"""rawvideo.py -- stream raw video frames through the MI355X engine.
 
 The reference moves every frame through PNG files on both sides of the net (ffmpeg writes
 `%d.extract.png`, upscale/upscale_processing.py:203-255; workers imread / imwrite, :263,288,487,519;
@@ -8,6 +8,17 @@ This module is the same per-frame arithmetic fed by a raw pipe instead, ffmpeg i
     ffmpeg -i in.mkv -f rawvideo -pix_fmt bgr24 - \\
       | python -m upscale_video_amd.rawvideo -W 1920 -H 1080 -s 2 \\
       | ffmpeg -f rawvideo -pix_fmt bgr24 -s 3840x2160 -r 24 -i - out.mkv
+
+or, with the colour conversion on the GPU and half the pipe bytes (--in-pix-fmt / --out-pix-fmt: bgr24, yuv420p, nv12,
+p010le; --colorspace bt601|bt709, --color-range tv|pc, default bt601 / tv: DESIGN.md section 7.3):
+
+    ffmpeg -i in.mkv -f rawvideo -pix_fmt yuv420p - \\
+      | python -m upscale_video_amd.rawvideo -W 1920 -H 1080 -s 2 --in-pix-fmt yuv420p --out-pix-fmt p010le \\
+      | ffmpeg -f rawvideo -pix_fmt p010le -s 3840x2160 -r 24 -i - -c:v libx265 out.mkv
+
+The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
+conversions run on the net's stream around its kernels); nets in between pass u8 BGR.  A leading `-m n=K` stage converts
+its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
 
 Frames go through Net.submit_u8 / collect_u8 (include/uva.h): page-locked rings on the host, H2D copy,
 kernels and D2H copy of consecutive frames overlapped on three streams.  `-m a` runs the reference's
@@ -49,6 +60,23 @@ MODEL_FILES = {  # upscale/upscale_processing.py:880-916
 PIPE_DEPTH = 3   # include/uva.h: at most 3 frames in flight per net
 
 
+class PixFormats:
+    """the raw-video formats of a stream's two ends and the colour arithmetic between them (ncnn.PIX_FORMATS etc.)"""
+
+    def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv"):
+        for f in (in_fmt, out_fmt):
+            if f not in ncnn.PIX_FORMATS:
+                raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(ncnn.PIX_FORMATS)))
+        ncnn.colour_word(colour, color_range)              # (checks both names)
+        self.in_fmt, self.out_fmt, self.colour, self.color_range = in_fmt, out_fmt, colour, color_range
+
+    def frame_bytes(self, h, w, out=False):
+        return ncnn.pix_frame_bytes(self.out_fmt if out else self.in_fmt, h, w)
+
+
+BGR = PixFormats()
+
+
 def load_net(stem, gpu, model_path):
     net = ncnn.Net()
     net.opt.use_vulkan_compute = True
@@ -76,14 +104,15 @@ def read_exact(f, view):
 class Stage:
     """One net with its own ring of page-locked result buffers and up to PIPE_DEPTH frames in flight."""
 
-    def __init__(self, net, h, w, tile_size, alloc):
+    def __init__(self, net, h, w, tile_size, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR):
         self.net, self.tile = net, tile_size
+        self.h, self.w, self.in_fmt, self.out_fmt, self.pix = h, w, in_fmt, out_fmt, pix
         s = net.scale
         # A result buffer stays in use while its frame is in flight here (<= depth frames) and then
         # while the consumer holds it -- the next stage reads it as pinned input until that stage's
         # collect (<= depth frames), or the writer thread (queue of 2 + 1 being written).  Frames stay
         # in order, so 2*depth + 2 buffers can never wrap onto a live one.
-        self.outs = [alloc((h * s, w * s, 3)) for _ in range(2 * PIPE_DEPTH + 2)]
+        self.outs = [ncnn.pix_empty(out_fmt, h * s, w * s, alloc) for _ in range(2 * PIPE_DEPTH + 2)]
         self.n = 0
         self.inflight = []
 
@@ -93,7 +122,13 @@ class Stage:
     def submit(self, frame):
         out = self.outs[self.n % len(self.outs)]
         self.n += 1
-        self.inflight.append(self.net.submit_u8(frame, out=out, tile_size=self.tile, border=TILE_BORDER if self.tile else 0))
+        border = TILE_BORDER if self.tile else 0
+        if self.in_fmt == self.out_fmt == "bgr24":
+            self.inflight.append(self.net.submit_u8(frame, out=out, tile_size=self.tile, border=border))
+        else:
+            self.inflight.append(self.net.submit_pix(frame, self.h, self.w, self.in_fmt, out=out, out_fmt=self.out_fmt,
+                                                     colour=self.pix.colour, color_range=self.pix.color_range,
+                                                     tile_size=self.tile, border=border))
 
     def collect(self):
         return self.net.collect_u8(self.inflight.pop(0))
@@ -102,15 +137,20 @@ class Stage:
 class DenoiseStage:
     """`-m n=K` (apply_denoise, upscale/upscale_processing.py:350-354) as a stage of a lane: cv2.fastNlMeansDenoisingColored's
     arithmetic on the lane's GPU (include/uva.h uva_denoise_u8), host frame in, host frame out like the nets' stages -- the call
-    takes about a millisecond per 1080p frame and releases the interpreter lock, the nets behind it keep their frames in flight."""
+    takes about a millisecond per 1080p frame and releases the interpreter lock, the nets behind it keep their frames in flight.
+    Frames of another format than bgr24 on either end are converted on the same GPU (include/uva.h uva_pix_convert)."""
 
     class _Scale1:
         scale = 1
 
-    def __init__(self, gpu, strength, h, w, alloc):
+    def __init__(self, gpu, strength, h, w, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR):
         self.gpu, self.strength = gpu, float(strength)
         self.net = self._Scale1()
-        self.outs = [alloc((h, w, 3)) for _ in range(2 * PIPE_DEPTH + 2)]
+        self.in_fmt, self.out_fmt, self.pix = in_fmt, out_fmt, pix
+        self.outs = [ncnn.pix_empty(out_fmt, h, w, alloc) for _ in range(2 * PIPE_DEPTH + 2)]
+        self._bgr_in = alloc((h, w, 3)) if in_fmt != "bgr24" else None      # (used and done with inside submit)
+        self._bgr_out = alloc((h, w, 3)) if out_fmt != "bgr24" else None
+        self.h, self.w = h, w
         self.n = 0
         self.inflight = []
 
@@ -121,9 +161,15 @@ class DenoiseStage:
         from . import _lib
         out = self.outs[self.n % len(self.outs)]
         self.n += 1
-        h, w, _ = frame.shape
-        _lib.check(_lib.load().uva_denoise_u8(self.gpu, frame.ctypes.data, h, w, frame.strides[0], out.ctypes.data, out.strides[0],
+        h, w = self.h, self.w
+        pix = self.pix
+        if self.in_fmt != "bgr24":
+            frame = ncnn.convert_pix(frame, h, w, self.in_fmt, "bgr24", pix.colour, pix.color_range, out=self._bgr_in, gpu=self.gpu)
+        dst = out if self.out_fmt == "bgr24" else self._bgr_out
+        _lib.check(_lib.load().uva_denoise_u8(self.gpu, frame.ctypes.data, h, w, frame.strides[0], dst.ctypes.data, dst.strides[0],
                                               self.strength, self.strength))
+        if self.out_fmt != "bgr24":
+            ncnn.convert_pix(dst, h, w, "bgr24", self.out_fmt, pix.colour, pix.color_range, out=out, gpu=self.gpu)
         self.inflight.append(out)
 
     def collect(self):
@@ -134,13 +180,16 @@ class Lane:
     """The chain of nets of ONE -g entry (one or two Stages on one GPU).  Frames go in with submit() and come out,
     in the order they went in, with pop()."""
 
-    def __init__(self, nets_tiles, h, w, alloc):
+    def __init__(self, nets_tiles, h, w, alloc, pix=BGR):
         self.stages = []
-        for net, tile in nets_tiles:
+        last = len(nets_tiles) - 1
+        for k, (net, tile) in enumerate(nets_tiles):
+            # the first stage takes the stream's input format, the last one produces its output format, u8 BGR in between
+            fmts = dict(in_fmt=pix.in_fmt if k == 0 else "bgr24", out_fmt=pix.out_fmt if k == last else "bgr24", pix=pix)
             if isinstance(net, tuple):         # ("denoise", gpu, K): the `-m n=K` stage
-                self.stages.append(DenoiseStage(net[1], net[2], h, w, alloc))
+                self.stages.append(DenoiseStage(net[1], net[2], h, w, alloc, **fmts))
                 continue
-            self.stages.append(Stage(net, h, w, tile, alloc))
+            self.stages.append(Stage(net, h, w, tile, alloc, **fmts))
             h, w = h * net.scale, w * net.scale
         self.count = 0                         # frames inside
 
@@ -185,22 +234,23 @@ def _regular_fd(f):
         return None
 
 
-def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threads=1):
-    """Reads u8 [h][w][3] frames from fin until EOF, pushes each through the nets in order, writes the
+def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threads=1, pix=None):
+    """Reads h x w frames of pix.in_fmt (PixFormats; default u8 [h][w][3] bgr24 at both ends) from fin until EOF, pushes each through the nets in order, writes the
     results to fout.  nets_tiles: list of (Net, tile_size) -- one GPU worker -- or a list of such lists,
     one per `-g` entry (duplicates allowed, as in the reference's worker list, README.md:45-61): ONE reader
     deals the frames out round-robin (the partition of upscale_processing.py:565-598, frames being
     independent units), every entry keeps up to PIPE_DEPTH frames in flight per net, and ONE writer puts
     the results out in frame order.  write_threads > 1 and fout a regular file: every result frame is cut into that many pieces
     written with os.pwrite by a small pool (one thread copies ~5 GB/s into the page cache: a 4K frame every 5 ms, half of what
-    one GPU delivers).  Returns the number of frames written."""
+    one GPU delivers).  Results are frames of pix.out_fmt.  Returns the number of frames written."""
     alloc = alloc or ncnn.pinned_empty
+    pix = pix or BGR
     lanes_spec = nets_tiles if nets_tiles and isinstance(nets_tiles[0], list) else [nets_tiles]
-    lanes = [Lane(spec, h, w, alloc) for spec in lanes_spec]
+    lanes = [Lane(spec, h, w, alloc, pix) for spec in lanes_spec]
     nl = len(lanes)
     # an input buffer is free again once its frame has left its lane's first stage: at most PIPE_DEPTH per lane are
     # there, plus the one being read into
-    ins = [alloc((h, w, 3)) for _ in range(nl * PIPE_DEPTH + 2)]
+    ins = [ncnn.pix_empty(pix.in_fmt, h, w, alloc) for _ in range(nl * PIPE_DEPTH + 2)]
 
     # writer thread: the blocking write of frame i overlaps the read of frame i+k and the GPUs
     wq = queue.Queue(maxsize=2)
@@ -219,7 +269,7 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
             k = os.pwrite(fd, view, pos)
             view, pos = view[k:], pos + k
 
-    sink = PipeSink(fout)
+    sink = PipeSink(fout, ring=min(len(lane.stages[-1].outs) for lane in lanes))
 
     def writer():
         pos = pos0 if fd is not None else 0
@@ -352,7 +402,7 @@ class MappedSegment:
 
 
 def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames=None, alloc=None, opener=open, mapped=None,
-                    write_threads=1):
+                    write_threads=1, pix=None):
     """The same frames -> the same bytes as stream(), for regular FILES, with NO shared serial copy: one contiguous segment of
     frames per `-g` entry (the reference's batches, upscale/upscale_processing.py:923-948, are such segments), and every entry
     runs its own stream() -- its own reader, its own pipelined chain of nets, its own writer thread -- on its own file handles.
@@ -363,8 +413,10 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
                 slower than write() on tmpfs and on overlayfs, kept as an option);  a list: one output file per entry
     One reader and one writer thread copy ~10 GB/s each, two or three GPUs' worth of 1080p -> 4K frames; N independent pairs
     scale with the entries.  A worker that fails takes the output with it: the file(s) this call created are removed (a
-    full-size file of zeros and holes is worse than none).  Returns the number of frames written."""
-    fb_in, fb_out = h * w * 3, h * scale_total * w * scale_total * 3
+    full-size file of zeros and holes is worse than none).  pix: PixFormats of the two ends (default bgr24).  Returns the number
+    of frames written."""
+    pix = pix or BGR
+    fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(h * scale_total, w * scale_total, out=True)
     nl = len(lanes_spec)
     ins = list(in_path) if isinstance(in_path, (list, tuple)) else None
     outs = list(out_path) if isinstance(out_path, (list, tuple)) else None
@@ -426,11 +478,12 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
                 fin.seek(in_first[k] * fb_in)
                 if outs is None and mapped:
                     with MappedSegment(opener(out_path, "r+b"), out_first[k] * fb_out, counts[k] * fb_out) as fout:
-                        done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k])
+                        done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], pix=pix)
                 else:
                     with opener(out_path if outs is None else outs[k], "r+b" if outs is None else "wb") as fout:
                         fout.seek(out_first[k] * fb_out)
-                        done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], write_threads=write_threads)
+                        done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], write_threads=write_threads,
+                                         pix=pix)
         except Exception as e:  # noqa: BLE001
             errs.append(e)
     threads = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(nl)]
@@ -469,15 +522,17 @@ class PipeSink:
     delivers; profiles/r05_final_rawvideo_bench.txt).  No SPLICE_F_GIFT: the pages stay ours, so a buffer must not be rewritten
     while the pipe still refers to it -- vmsplice returns once the LAST piece of a frame is in the pipe, whose capacity is far
     below one frame, so when frame k + 1 has been handed over frame k has been read completely; the result rings hold eight
-    buffers (Stage.outs).  Falls back to write() for good the first time the kernel refuses (memory it cannot take
-    references on, a pipe that went away is an error as before)."""
+    buffers (Stage.outs; `ring`, when given, is checked to be at least PIPE_DEPTH + 4 before anything is spliced: the frames in
+    flight, the writer's queue and the frame in the pipe).  Falls back to write() for good the first time the kernel refuses
+    (memory it cannot take references on, a pipe that went away is an error as before)."""
 
     class _IoVec(ctypes.Structure):
         _fields_ = [("base", ctypes.c_void_p), ("len", ctypes.c_size_t)]
 
-    def __init__(self, f):
+    def __init__(self, f, ring=None):
         import stat
         self._f = f
+        self._ring = ring
         self._fd = None
         self._cap = None            # the pipe's capacity, asked for at the first frame (grow_pipe may come after the constructor)
         self.spliced = 0            # frames that went through vmsplice (tests, the bench's log line)
@@ -501,6 +556,7 @@ class PipeSink:
         if self._fd is None or arr.nbytes < self._cap:        # (frames smaller than the pipe: several could sit in it, still referred to)
             self._f.write(memoryview(arr).cast("B"))
             return
+        assert self._ring is None or self._ring >= PIPE_DEPTH + 4, "a ring of %d result buffers is too short to splice from" % self._ring
         self._f.flush()             # (nothing of ours is buffered in front of the spliced bytes)
         addr, n, off = arr.ctypes.data, arr.nbytes, 0
         while off < n:
@@ -543,14 +599,21 @@ class PipeSink:
             time.sleep(0.001)
 
 
-def copy_through(fin, fout, h, w, max_frames=None):
-    """`-s 1` without `-m a`: the reference renames the frames, nothing is computed (:924-929)."""
-    buf = bytearray(h * w * 3)
+def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
+    """`-s 1` without `-m a`: the reference renames the frames, nothing is computed (:924-929).  Formats that differ at the two
+    ends (pix): every frame is converted once on HIP device `gpu` (include/uva.h uva_pix_convert)."""
+    pix = pix or BGR
+    buf = bytearray(pix.frame_bytes(h, w))
+    res = ncnn.pix_empty(pix.out_fmt, h, w) if pix.in_fmt != pix.out_fmt else None
     n = 0
     while max_frames is None or n < max_frames:
         if not read_exact(fin, memoryview(buf)):
             break
-        fout.write(buf)
+        if res is None:
+            fout.write(buf)
+        else:
+            ncnn.convert_pix(np.frombuffer(buf, np.uint8), h, w, pix.in_fmt, pix.out_fmt, pix.colour, pix.color_range, out=res, gpu=gpu)
+            fout.write(memoryview(res).cast("B"))
         n += 1
     fout.flush()
     return n
@@ -558,8 +621,8 @@ def copy_through(fin, fout, h, w, max_frames=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("-i", "--input", default="-", help="bgr24 rawvideo file, '-' = stdin; a,b,...: one segment file per -g entry")
-    ap.add_argument("-o", "--output", default="-", help="bgr24 rawvideo file, '-' = stdout; x,y,...: one output file per -g entry "
+    ap.add_argument("-i", "--input", default="-", help="rawvideo file (--in-pix-fmt), '-' = stdin; a,b,...: one segment file per -g entry")
+    ap.add_argument("-o", "--output", default="-", help="rawvideo file (--out-pix-fmt), '-' = stdout; x,y,...: one output file per -g entry "
                                                         "(a single input is cut into segments, segment k goes to the k-th file)")
     ap.add_argument("-W", "--width", type=int, required=True)
     ap.add_argument("-H", "--height", type=int, required=True)
@@ -576,10 +639,19 @@ def main(argv=None):
     ap.add_argument("--round-robin", action="store_true",
                     help="file to file with several -g entries: deal the frames out one by one through ONE reader and ONE writer "
                          "(what pipes get) instead of one contiguous segment of frames, reader and writer per entry")
+    ap.add_argument("--in-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS),
+                    help="ffmpeg -pix_fmt of the input frames (default bgr24); converted to BGR on the GPU")
+    ap.add_argument("--out-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS),
+                    help="ffmpeg -pix_fmt of the output frames (default bgr24); converted from the net's BGR on the GPU")
+    ap.add_argument("--colorspace", default="bt601", choices=list(ncnn.COLORSPACES),
+                    help="Y'CbCr matrix of yuv420p / nv12 / p010le frames (default bt601: what ffmpeg applies to the reference's "
+                         "untagged PNGs)")
+    ap.add_argument("--color-range", default="tv", choices=list(ncnn.COLOR_RANGES), help="tv = limited (default), pc = full")
     ap.add_argument("--model-path", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models"))
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
+    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range)
     # upscale_video.py -m: a (anime pass), n=K (film-grain denoise, K = 1..30, :782-789), r (the x_Valar_v1 model instead of
     # x_Compact_Pretrain, :913-916); the reference runs them in the order n, a, upscale (:880-920) whatever the order given
     models = [m for m in a.models.split(",") if m]
@@ -655,7 +727,7 @@ def main(argv=None):
         for net, _ in nets[0]:
             scale_total *= 1 if isinstance(net, tuple) else net.scale
         n = stream_segments(ins if len(ins) > 1 else ins[0], outs if len(outs) > 1 else outs[0], a.height, a.width, nets, scale_total,
-                            max_frames=a.frames, write_threads=wthreads)
+                            max_frames=a.frames, write_threads=wthreads, pix=pix)
         print("%d frames" % n, file=sys.stderr)
         ncnn.destroy_gpu_instance()
         return 0
@@ -667,9 +739,9 @@ def main(argv=None):
     ok = False
     try:
         if nets:
-            n = stream(fin, fout, a.height, a.width, nets, max_frames=a.frames, write_threads=wthreads)
+            n = stream(fin, fout, a.height, a.width, nets, max_frames=a.frames, write_threads=wthreads, pix=pix)
         else:
-            n = copy_through(fin, fout, a.height, a.width, a.frames)
+            n = copy_through(fin, fout, a.height, a.width, a.frames, pix=pix, gpu=gpus[0])
         ok = True
     finally:
         if fin is not sys.stdin.buffer:
