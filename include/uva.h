@@ -42,7 +42,9 @@ extern "C" {
                                15: + uva_net_process_u8_device_batch (several frames of one geometry per call; the 1x net takes up to
                                    eight per launch), uva_debug_sub10_rows_batch;
                                15 + pixel formats: + uva_pix_frame_bytes, uva_net_submit_pix, uva_pix_convert, uva_pix_convert_device
-                                   (additive: every entry point of 15 is unchanged) */
+                                   (additive: every entry point of 15 is unchanged)
+                               15 + 16-bit route: + UVA_PIX_YUV420P10LE, UVA_PIX_BGR48LE, uva_net_process_u16_device,
+                                   uva_net_process_u16, uva_net_submit_pix16, uva_pix_convert16 (additive as well) */
 
 typedef struct uva_net uva_net;
 
@@ -131,6 +133,8 @@ void uva_host_free(void* p);
  *   UVA_PIX_YUV420P  Y u8 [h][w], then U [ch][cw], then V [ch][cw]                  wh + 2 cw ch
  *   UVA_PIX_NV12     Y u8 [h][w], then [ch][cw][2] interleaved U, V                 wh + 2 cw ch
  *   UVA_PIX_P010LE   nv12's layout in little-endian 16-bit words, value << 6        2 (wh + 2 cw ch)
+ *   UVA_PIX_YUV420P10LE  yuv420p's layout in little-endian 16-bit words, the value in the low 10 bits   2 (wh + 2 cw ch)
+ *   UVA_PIX_BGR48LE  u16 [h][w][3], unorm16 (what the _u16 calls take; the 16-bit entries only)  6wh
  * colour = UVA_CSP_BT601 or UVA_CSP_BT709, | UVA_RANGE_FULL for full ("pc") range instead of limited ("tv": Y 16-235,
  * C 16-240, x4 at 10 bits).  BGR -> Y'CbCr: fixed-point textbook formulas, chroma of a 2x2 block from the block's sums;
  * Y'CbCr -> BGR: chroma replicated over its 2x2 block.  The reference's frames are untagged rgb24 PNGs, which ffmpeg merges
@@ -139,6 +143,8 @@ void uva_host_free(void* p);
 #define UVA_PIX_YUV420P 1
 #define UVA_PIX_NV12 2
 #define UVA_PIX_P010LE 3
+#define UVA_PIX_YUV420P10LE 5   /* (4 is not assigned) */
+#define UVA_PIX_BGR48LE 6
 #define UVA_CSP_BT601 0
 #define UVA_CSP_BT709 1
 #define UVA_RANGE_FULL 2
@@ -160,6 +166,25 @@ int uva_pix_convert(int device, const void* in, int in_fmt, void* out, int out_f
  * on the same device (same stream) has returned. */
 int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out, int out_fmt, int h, int w, int colour,
                            uva_net* after, uva_net* before);
+/* (uva_pix_convert and uva_net_submit_pix refuse UVA_PIX_BGR48LE: it is the 16-bit route's.) */
+
+/* ---- the 16-bit route ---------------------------------------------------------------------
+ * The 2x and 4x Compact nets on u16 BGR samples (unorm16, v / 65535): head operand fp16(v / 257) times 1/255, tail output
+ * clamp(rint(y * 65535), 0, 65535).  Y'CbCr frames reach the net without an 8-bit hop (10 bits in, 10 bits out); bgr24
+ * frames go in as v * 257 and come out as rint(v / 257).  Every 16-bit entry refuses the 1x net, generic graphs (x_Valar_v1)
+ * and frames whose byte offsets pass 32 bits, with uva_last_error set. */
+/* uva_net_process_u8_device's analogue: d_in u16 [h][w][3], d_out u16 [h*s][w*s][3], strides in bytes (even). */
+int uva_net_process_u16_device(uva_net* net, const void* d_in, int h, int w, size_t in_stride, void* d_out, size_t out_stride,
+                               int tile_size, int border);
+/* Host to host, synchronous (tests, Python). */
+int uva_net_process_u16(uva_net* net, const uint16_t* in, int h, int w, size_t in_stride, uint16_t* out, size_t out_stride,
+                        int tile_size, int border);
+/* uva_net_submit_pix's arguments and rules (collected by uva_net_collect_u8), converting to and from u16 BGR instead of u8:
+ * BGR48LE on both ends is uva_net_process_u16's frame. */
+long long uva_net_submit_pix16(uva_net* net, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
+                               int tile_size, int border);
+/* uva_pix_convert through u16 BGR (any two formats, UVA_PIX_BGR48LE included). */
+int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour);
 
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 

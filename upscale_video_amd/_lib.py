@@ -20,6 +20,8 @@ SYMBOLS = [
     "uva_net_debug_packed_weights", "uva_last_error", "uva_abi_version",
     # 15 + pixel formats (additive; an older ABI-15 build lacks them: load() then declares what it has, see UVA_ALLOW_OLD_ABI)
     "uva_pix_frame_bytes", "uva_net_submit_pix", "uva_pix_convert", "uva_pix_convert_device",
+    # 15 + the 16-bit route (additive as well)
+    "uva_net_process_u16_device", "uva_net_process_u16", "uva_net_submit_pix16", "uva_pix_convert16",
 ]
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -76,6 +78,10 @@ def load():
     decl("uva_pix_frame_bytes", [c_i, c_i, c_i], c_sz)
     decl("uva_net_submit_pix", [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i], ctypes.c_longlong)
     decl("uva_pix_convert", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i])
+    decl("uva_net_submit_pix16", [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i], ctypes.c_longlong)
+    decl("uva_pix_convert16", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i])
+    decl("uva_net_process_u16", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i])
+    decl("uva_net_process_u16_device", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i])
     decl("uva_pix_convert_device", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p])
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])

@@ -361,16 +361,28 @@ int launch_conv(uva_net* n, int mode, const ConvArgs& a)
     return fail("no kernel for this trunk width");
 }
 
-// u8 tails of the 64-feature 2x and 4x nets: ping-pong kernels on 4-row tiles (the other tails: conv3x3_kernel)
-int launch_tail_u8(uva_net* n, const Workspace* ws, ConvArgs ca)
+// does the net have the ping-pong tails (the 64-feature 2x and 4x nets), which the 16-bit route needs?
+bool has_tail64(const uva_net* n) { return n->g.nf == 64 && (n->g.scale == 2 || n->g.scale == 4) && n->layers.back().wpk16; }
+
+// u8 tails of the 64-feature 2x and 4x nets: ping-pong kernels on 4-row tiles (the other tails: conv3x3_kernel).  u16: the same
+// kernels on u16 BGR frames (the 16-bit route; the callers have refused every other net)
+int launch_tail_u8(uva_net* n, const Workspace* ws, ConvArgs ca, bool u16 = false)
 {
-    if (n->g.nf == 64 && (n->g.scale == 2 || n->g.scale == 4) && n->layers.back().wpk16) {
+    if (has_tail64(n)) {
         const bool x4 = n->g.scale == 4;
-        const size_t lds = x4 ? tail4_lds_bytes<64>() : tail_lds_bytes<64>();
-        void (*kfn)(ConvArgs) = x4 ? tail4_kernel<64> : tail_kernel<64, 2>;
-        if (!n->attr_set[7]) {
+        size_t lds;
+        void (*kfn)(ConvArgs);
+        if (u16) {
+            lds = x4 ? tail4_lds_bytes<64, uint16_t>() : tail_lds_bytes<64, uint16_t>();
+            kfn = x4 ? tail4_kernel<64, uint16_t> : tail_kernel<64, 2, uint16_t>;
+        } else {
+            lds = x4 ? tail4_lds_bytes<64>() : tail_lds_bytes<64>();
+            kfn = x4 ? tail4_kernel<64, uint8_t> : tail_kernel<64, 2, uint8_t>;
+        }
+        const int slot = u16 ? 10 : 7;
+        if (!n->attr_set[slot]) {
             HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            n->attr_set[7] = true;
+            n->attr_set[slot] = true;
         }
         const int grid = std::max(8, (n->ncu / 8) * 8);
         const int per_launch = 8 * (2 * (grid / 8)) * ((TAIL_SCHED_MAX - TRUNK_LOOKAHEAD) / 2 - 1);
@@ -385,6 +397,7 @@ int launch_tail_u8(uva_net* n, const Workspace* ws, ConvArgs ca)
         }
         return 0;
     }
+    if (u16) return fail("the 16-bit route has no tail for this net");
     return launch_conv(n, 1, ca);
 }
 
@@ -920,8 +933,15 @@ int launch_pair24(uva_net* n, const ConvArgs& a)
     return 0;
 }
 
-int launch_head(uva_net* n, bool f32, const HeadArgs& a)
+int launch_head(uva_net* n, bool f32, const HeadArgs& a, bool u16 = false)
 {
+    if (u16) {                  // the 16-bit route: headp_kernel<64, 2> only (its callers have refused every other net)
+        if (n->g.nf != 64 || !a.sink) return fail("the 16-bit route has no head for this net");
+        const dim3 grid(std::min(a.ntiles, n->ncu * HEADP_WG_PER_CU)), block(256);
+        hipLaunchKernelGGL((headp_kernel<64, 2>), grid, block, headp_lds_bytes<64>(), n->stream, a);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     // headp_kernel (persistent, the next tile's pixels requested while this one is computed) unless UVA_HEAD_PERSIST=0
     const char* const hp = uva::debug_env("UVA_HEAD_PERSIST");        // (read per call: the GPU test switches it between two frames)
     const bool persist = !hp || std::atoi(hp) != 0;
@@ -1402,13 +1422,14 @@ int run_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_str
     return rc;
 }
 
+// u16: the 16-bit route (u16 HWC BGR in and out; 64-feature 2x / 4x nets only)
 int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_stride, void* dst,
-              size_t dst_stride, int stop_after)
+              size_t dst_stride, int stop_after, bool u16 = false)
 {
     const Graph& g = n->g;
     const int nconv = (int)g.convs.size();
     // the 24-feature 1x net on a whole-frame plane, u8 in / u8 out: one launch for all ten convolutions
-    if (sub10_route(n, ws, f32, stop_after)) {
+    if (!u16 && sub10_route(n, ws, f32, stop_after)) {
         const int rc = run_sub10(n, ws, &src, src_stride, &dst, dst_stride, 1);
         if (rc != 2) return rc;
     }
@@ -1439,9 +1460,9 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
     ha.wpk = n->layers[0].wpk;
     ha.bias = n->layers[0].bias;
     ha.slope = n->layers[0].slope;
-    ha.in_scale = f32 ? 1.0f : (float)(1 / 255.0);
+    ha.in_scale = f32 ? 1.0f : (float)(1 / 255.0);      // (u16: the operand is v / 257, see headp_kernel)
     ha.sink = n->d_sink;
-    if (launch_head(n, f32, ha)) return 1;
+    if (launch_head(n, f32, ha, u16)) return 1;
     if (prof) HIP_TRY(hipEventRecord(ev.e[1], n->stream));
 
     ConvArgs ca;
@@ -1545,7 +1566,7 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
         ca.dst_u8 = (uint8_t*)dst;
         ca.dst_stride = dst_stride;
     }
-    if (f32 ? launch_conv(n, 2, ca) : launch_tail_u8(n, ws, ca)) return 1;
+    if (f32 ? launch_conv(n, 2, ca) : launch_tail_u8(n, ws, ca, u16)) return 1;
     if (prof) {
         HIP_TRY(hipEventRecord(ev.e[3], n->stream));
         n->ev_pending.push_back(ev);
@@ -2205,11 +2226,12 @@ int pix_grow(PixCtx& c, uint8_t** p, size_t* cap, size_t bytes)
     return grow_dev(p, cap, bytes);
 }
 
-int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, int w, int colour)
+int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, int w, int colour, bool u16 = false)
 {
     if (!in || !out) return fail("null frame pointer");
     if (h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image size");
     if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) return fail("unknown pixel format");
+    if (!u16 && (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE)) return fail("bgr48le is a 16-bit format: use the 16-bit entries (uva_pix_convert16)");
     if (colour & ~PIX_COLOUR_MASK) return fail("bad colour word");
     return 0;
 }
@@ -2227,6 +2249,23 @@ int pix_convert_launch(PixCtx& c, const uint8_t* d_in, int in_fmt, uint8_t* d_ou
         if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(PIX_BGR24, h, w))) return 1;
         HIP_TRY(launch_pix_to_bgr(c.stream, in_fmt, colour, d_in, c.d_mid, h, w));
         HIP_TRY(launch_pix_from_bgr(c.stream, out_fmt, colour, c.d_mid, d_out, h, w));
+    }
+    return 0;
+}
+
+// the 16-bit form: d_in (in_fmt) -> d_out (out_fmt) through u16 BGR (d_mid) when neither end is BGR48LE
+int pix_convert16_launch(PixCtx& c, const uint8_t* d_in, int in_fmt, uint8_t* d_out, int out_fmt, int h, int w, int colour)
+{
+    if (in_fmt == out_fmt) {
+        HIP_TRY(hipMemcpyAsync(d_out, d_in, pix_frame_bytes(in_fmt, h, w), hipMemcpyDeviceToDevice, c.stream));
+    } else if (in_fmt == PIX_BGR48LE) {
+        HIP_TRY(launch_pix16_from_bgr(c.stream, out_fmt, colour, (const uint16_t*)d_in, d_out, h, w));
+    } else if (out_fmt == PIX_BGR48LE) {
+        HIP_TRY(launch_pix16_to_bgr(c.stream, in_fmt, colour, d_in, (uint16_t*)d_out, h, w));
+    } else {
+        if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(PIX_BGR48LE, h, w))) return 1;
+        HIP_TRY(launch_pix16_to_bgr(c.stream, in_fmt, colour, d_in, (uint16_t*)c.d_mid, h, w));
+        HIP_TRY(launch_pix16_from_bgr(c.stream, out_fmt, colour, (const uint16_t*)c.d_mid, d_out, h, w));
     }
     return 0;
 }
@@ -2755,6 +2794,34 @@ int uva_net_process_u8_device(uva_net* n, const void* d_in, int h, int w, size_t
     return run_graph(n, ws, false, d_in, in_stride, d_out, out_stride, -1);
 }
 
+// the 16-bit route's refusals, shared by every 16-bit entry: 2x / 4x Compact nets only
+static int check_u16_net(uva_net* n)
+{
+    if (n->generic) return fail("the 16-bit route takes the 2x and 4x Compact nets only (this net runs as a generic graph)");
+    if (!has_tail64(n)) return fail("the 16-bit route takes the 2x and 4x Compact nets only (64 features, scale 2 or 4)");
+    return 0;
+}
+
+int uva_net_process_u16_device(uva_net* n, const void* d_in, int h, int w, size_t in_stride, void* d_out,
+                               size_t out_stride, int tile_size, int border)
+{
+    if (check_dims(n, h, w)) return 1;
+    if (!d_in || !d_out) return fail("null frame pointer");
+    if (ensure_device(n)) return 1;
+    if (check_u16_net(n)) return 1;
+    const int s = uva_net_scale(n);
+    if (in_stride < (size_t)w * 6 || out_stride < (size_t)w * s * 6) return fail("row stride too small");
+    if ((((uintptr_t)d_in | (uintptr_t)d_out | in_stride | out_stride) & 1) != 0) return fail("16-bit frames need 2-byte aligned rows");
+    // the tail kernels address the residual and output bytes with 32-bit offsets from the frame's base
+    if ((unsigned long long)in_stride * (unsigned long long)h >= (1ull << 32) - 64 ||
+        (unsigned long long)out_stride * (unsigned long long)h * (unsigned long long)s >= (1ull << 32) - 64)
+        return fail("frame of 4 GB or more");
+    Workspace* ws = nullptr;
+    if (get_workspace(n, h, w, tile_size, border, &ws)) return 1;
+    n->last = LastCall();        // the debug replays know u8 and f32 frames only
+    return run_graph(n, ws, false, d_in, in_stride, d_out, out_stride, -1, true);
+}
+
 // `count` frames of ONE geometry, all resident on the net's device.  The 1x net takes up to S10_MAXB of them per launch
 // (sub10_kernel: the segments' warm-up rows and the pipeline's fill and drain are paid once per launch, not once per frame);
 // every other net -- and whatever does not fit the kernel's row table -- runs frame by frame, exactly as `count` calls of
@@ -2828,9 +2895,11 @@ namespace {
 // in HBM, its PNG deflate blocks go to the page-locked workspace png_ws) and uva_net_submit_pix (in_fmt / out_fmt other than
 // BGR24: the dense packed frame goes to d_pin and is converted into d_in on the net's stream, d_out is converted into d_pout
 // behind the net and d_pout comes back)
+// u16: the 16-bit route -- the net's frames are u16 BGR (BGR48LE), in_stride / out_stride are in bytes, and a packed frame
+// (bgr24 included) is converted to and from u16 BGR
 long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out, size_t out_stride,
                     int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
-                    int colour = 0)
+                    int colour = 0, bool u16 = false)
 {
     if (check_dims(n, h, w)) return -1;
     if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
@@ -2838,11 +2907,13 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     if (ensure_device(n)) return -1;
     auto tryhip = [](hipError_t e, const char* what) { return e == hipSuccess ? 0 : fail(std::string(what) + ": " + hipGetErrorString(e)); };
     const int s = uva_net_scale(n);
-    const size_t in_row = (size_t)w * 3, out_row = (size_t)w * s * 3;
+    const size_t bps = u16 ? 2 : 1;        // bytes per sample of the net's frames
+    const size_t in_row = (size_t)w * 3 * bps, out_row = (size_t)w * s * 3 * bps;
     if (png_ws) out_stride = out_row;
     if (in_stride < in_row || out_stride < out_row) { fail("row stride too small"); return -1; }
     const size_t in_bytes = in_row * h, out_bytes = out_row * (size_t)h * s;
-    const bool pin = in_fmt != PIX_BGR24, pout = out_fmt != PIX_BGR24;
+    const int native = u16 ? PIX_BGR48LE : PIX_BGR24;
+    const bool pin = in_fmt != native, pout = out_fmt != native;
     const size_t pin_bytes = pix_frame_bytes(in_fmt, h, w), pout_bytes = pix_frame_bytes(out_fmt, h * s, w * s);
     if (pout_bytes > (size_t)INT_MAX) { fail("result frame of 2 GB or more"); return -1; }
     uva_net::PipeSlot* free_slot = nullptr;
@@ -2884,9 +2955,16 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
                                 hipMemcpyHostToDevice, n->s_h2d), "H2D") ||
         tryhip(hipEventRecord(ps.ev_h2d, n->s_h2d), "hipEventRecord") ||
         tryhip(hipStreamWaitEvent(n->stream, ps.ev_h2d, 0), "hipStreamWaitEvent")) return -1;
-    if (pin && tryhip(launch_pix_to_bgr(n->stream, in_fmt, colour, ps.d_pin, ps.d_in, h, w), "pix_to_bgr")) return -1;
-    if (uva_net_process_u8_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
-    if (pout && tryhip(launch_pix_from_bgr(n->stream, out_fmt, colour, ps.d_out, ps.d_pout, h * s, w * s), "pix_from_bgr")) return -1;
+    if (u16) {
+        if (pin && tryhip(launch_pix16_to_bgr(n->stream, in_fmt, colour, ps.d_pin, (uint16_t*)ps.d_in, h, w), "pix16_to_bgr")) return -1;
+        if (uva_net_process_u16_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
+        if (pout && tryhip(launch_pix16_from_bgr(n->stream, out_fmt, colour, (const uint16_t*)ps.d_out, ps.d_pout, h * s, w * s), "pix16_from_bgr"))
+            return -1;
+    } else {
+        if (pin && tryhip(launch_pix_to_bgr(n->stream, in_fmt, colour, ps.d_pin, ps.d_in, h, w), "pix_to_bgr")) return -1;
+        if (uva_net_process_u8_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
+        if (pout && tryhip(launch_pix_from_bgr(n->stream, out_fmt, colour, ps.d_out, ps.d_pout, h * s, w * s), "pix_from_bgr")) return -1;
+    }
     // png: the deflate kernel follows the net on its stream and leaves the blocks in HBM, packed end to end by a second
     // (device-to-device) kernel: 0.15 ms per 4K frame together
     if (png_ws && (png_launch(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png) ||
@@ -3007,12 +3085,54 @@ long long uva_net_submit_pix(uva_net* n, const void* in, int in_fmt, int h, int 
                              int tile_size, int border)
 {
     if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
+    if (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE) { fail("bgr48le is a 16-bit format: use uva_net_submit_pix16"); return -1; }
     if (colour & ~PIX_COLOUR_MASK) { fail("bad colour word"); return -1; }
     if (check_dims(n, h, w)) return -1;
     const int s = uva_net_scale(n);
     if (s <= 0) { fail("net has no graph"); return -1; }
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3, (uint8_t*)out, (size_t)w * s * 3, tile_size, border, nullptr, 0,
                      in_fmt, out_fmt, colour);
+}
+
+long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
+                               int tile_size, int border)
+{
+    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
+    if (colour & ~PIX_COLOUR_MASK) { fail("bad colour word"); return -1; }
+    if (check_dims(n, h, w)) return -1;
+    if (ensure_device(n) || check_u16_net(n)) return -1;
+    const int s = uva_net_scale(n);
+    return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 6, (uint8_t*)out, (size_t)w * s * 6, tile_size, border, nullptr, 0,
+                     in_fmt, out_fmt, colour, true);
+}
+
+int uva_net_process_u16(uva_net* n, const uint16_t* in, int h, int w, size_t in_stride, uint16_t* out, size_t out_stride,
+                        int tile_size, int border)
+{
+    if (check_dims(n, h, w)) return 1;
+    if (!in || !out) return fail("null frame pointer");
+    if (ensure_device(n) || check_u16_net(n)) return 1;
+    const long long t = submit_u8(n, (const uint8_t*)in, h, w, in_stride, (uint8_t*)out, out_stride, tile_size, border, nullptr, 0,
+                                  PIX_BGR48LE, PIX_BGR48LE, 0, true);
+    if (t < 0) return 1;
+    if (uva_net_collect_u8(n, t)) return 1;
+    resolve_events(n);
+    return 0;
+}
+
+int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
+{
+    if (pix_check(in, in_fmt, out, out_fmt, h, w, colour, true)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
+    if (pix_convert16_launch(*c, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 size_t uva_png_workspace_bytes(int h, int w)

@@ -23,6 +23,7 @@
 //                           is the cheapest per flop), host-built tile schedule
 //   tail_kernel<64,2>       u8 tail of the 2x net on the same skeleton (residual bytes by LDS-DMA)
 //   tail4_kernel<64>        u8 tail of the 4x net: weights in LDS, 3-slot ring, stores from registers
+//                           (both tails also in a u16 instantiation for the 16-bit route)
 //   conv3x3_kernel<NF,M,R>  everything else (24-feature nets, f32-route tails): one persistent 4-wave
 //                           workgroup per CU (two for NF = 24), one wave per SIMD, every wave keeps the
 //                           layer's whole weight matrix in its 512-entry register file, 8x32 tiles,
@@ -1722,11 +1723,16 @@ __global__ __launch_bounds__(512, 2) void trunk2_kernel(Trunk2Args a)
 // like the ring pieces), instead of per-lane byte loads whose compiler-inserted wait would drain
 // the DMA queue.
 // ----------------------------------------------------------------------------------------------
+//
+// T is the frame's sample type: uint8_t, or uint16_t (unorm16 BGR, the 16-bit route): residual (v / 257) / 255 (= v / 65535;
+// v = 257 k gives the u8 route's k / 255 exactly), output clamp(rint(y * 65535), 0, 65535), 6-byte pixels -- twice the
+// residual dwords and twice the staged row bytes.
 constexpr int TAIL_SCHED_MAX = 448;
-constexpr int TAIL_RESID_LDS = 8 * 128;       // per wave: 2 rows x 16 dwords
-template <int NF>
-constexpr int tail_lds_bytes() { return TRUNK_SLOTS * TrunkGeo<NF>::SLOTB + PARAMS_AND_PLANES_LDS + TAIL_SCHED_MAX * 16 + TAIL_RESID_LDS; }
+constexpr int TAIL_RESID_LDS = 8 * 128;       // per wave: 2 rows x 16 dwords (u16 frames: x 32 dwords, twice this)
+template <int NF, typename T = uint8_t>
+constexpr int tail_lds_bytes() { return TRUNK_SLOTS * TrunkGeo<NF>::SLOTB + PARAMS_AND_PLANES_LDS + TAIL_SCHED_MAX * 16 + TAIL_RESID_LDS * (int)sizeof(T); }
 static_assert(tail_lds_bytes<64>() <= 160 * 1024, "tail kernel LDS budget");
+static_assert(tail_lds_bytes<64, uint16_t>() <= 160 * 1024, "tail kernel LDS budget (u16)");
 
 // 4 bytes per active lane from sbase + voff to lds_dst + lane*4
 __device__ __forceinline__ void glds4_s(const void* sbase, unsigned voff, unsigned lds_dst)
@@ -1742,10 +1748,11 @@ __device__ __forceinline__ void glds4_s(const void* sbase, unsigned voff, unsign
         : "v"(voff), "s"(sbase), "s"(lds_dst));
 }
 
-template <int NF, int R>
+template <int NF, int R, typename T>
 __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
 {
     static_assert(NF == 64 && R == 2, "written for the 2x net's tail (64 -> 12)");
+    constexpr int SB = (int)sizeof(T);        // bytes per sample: 1 (u8) or 2 (u16)
     using G = Geo<NF, TH4>;
     using TG = TrunkGeo<NF>;
     constexpr int KS = 18;                    // k-steps of 32: (tap, input-channel half)
@@ -1756,8 +1763,8 @@ __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
     constexpr int CPW_K = 8;                  // DMA pieces issued in the k-loop phase (the rest in the epilogue phase):
                                               // all 8 measured slightly better than 5 + 3
     constexpr int NSTEP = 24;
-    constexpr int ROWB = 16 * R * 3;          // staged bytes per output row of this wave
-    constexpr int STAGEB = 512;               // per wave: 2R rows x ROWB = 384
+    constexpr int ROWB = 16 * R * 3 * SB;     // staged bytes per output row of this wave
+    constexpr int STAGEB = 512 * SB;          // per wave: 2R rows x ROWB = 384 (u8) / 768 (u16)
     static_assert(2 * R * ROWB <= STAGEB && 4 * STAGEB <= SLOTB, "output staging");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1855,8 +1862,8 @@ __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
     int cur = grp;
     Sched la = read_sched(grp + TRUNK_LOOKAHEAD);
 
-    const unsigned resid_lds = lds0 + (unsigned)(resid_all - smem) + wave8 * 128;
-    const char* const resid_rd = resid_all + wave8 * 128;
+    const unsigned resid_lds = lds0 + (unsigned)(resid_all - smem) + wave8 * (128 * SB);
+    const char* const resid_rd = resid_all + wave8 * (128 * SB);
     // the lane's four output channels' bias, resident (an LDS read at the top of every epilogue is a round trip of its own)
     const f32x4 b4 = *(const f32x4*)(bias_lds + 4 * (lane >> 4));
     const bool stamp = UVA_STAMP_ON(a);
@@ -1890,19 +1897,19 @@ __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
         int sh[2];
         {
             const int xc = min(xs, pl_w - 1);
-            const unsigned nb = 3u * (unsigned)min(16, pl_w - xc);         // valid bytes of the row segment (>= 3)
+            const unsigned nb = 3u * SB * (unsigned)min(16, pl_w - xc);    // valid bytes of the row segment (>= 3)
             unsigned voff = 0;
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const int yc = min(y_t + n, pl_h - 1);
-                const unsigned ra = (unsigned)(src_y0 + yc) * src_stride32 + (unsigned)(src_x0 + xc) * 3u;   // byte offset in the frame
+                const unsigned ra = (unsigned)(src_y0 + yc) * src_stride32 + (unsigned)(src_x0 + xc) * (3u * SB);   // byte offset in the frame
                 const unsigned al = src_lo2 + ra;                          // same low bits as the byte's address
                 sh[n] = (int)(al & 3u);
                 const int dmax = (int)((((al + nb - 1u) & ~3u) - (al & ~3u)) >> 2);
-                const unsigned vo = (ra - (unsigned)sh[n]) + 4u * (unsigned)min(lane & 15, dmax);
-                if ((lane >> 4) == n) voff = vo;
+                const unsigned vo = (ra - (unsigned)sh[n]) + 4u * (unsigned)min(lane & (16 * SB - 1), dmax);
+                if ((lane >> (SB == 1 ? 4 : 5)) == n) voff = vo;
             }
-            if (active && lane < 32) glds4_s(a.src_u8, voff, resid_lds);
+            if (active && lane < 32 * SB) glds4_s(a.src_u8, voff, resid_lds);
         }
         f32x4 acc[2];
         const int fill = cur + TRUNK_LOOKAHEAD >= TRUNK_SLOTS ? cur + TRUNK_LOOKAHEAD - TRUNK_SLOTS : cur + TRUNK_LOOKAHEAD;
@@ -1959,10 +1966,19 @@ __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
             if (g < 3) {
                 unsigned rb[2];
 #pragma unroll
-                for (int n = 0; n < 2; ++n) rb[n] = *(const uint8_t*)(resid_rd + n * 64 + sh[n] + 3 * p + g);
+                for (int n = 0; n < 2; ++n) rb[n] = *(const T*)(resid_rd + n * 64 * SB + sh[n] + (3 * p + g) * SB);
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
-                    const float res = (float)rb[n] * norm;
+                    const float res = SB == 1 ? (float)rb[n] * norm : ((float)rb[n] / 257.0f) * norm;
+                    if constexpr (SB == 2) {
+                        // rint rounds half to even, as v_cvt_pk_u8_f32 does on the u8 route; med3 clamps to the codes
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(((acc[n][j] + b4[j]) + res) * 65535.0f), 0.f, 65535.f);
+                            *(uint16_t*)(stage + (n * R + (j >> 1)) * ROWB + ((p * R + (j & 1)) * 3 + g) * 2) = (uint16_t)(unsigned)q;
+                        }
+                        continue;
+                    }
                     // v_cvt_pk_u8_f32 rounds half to even and saturates: cv2's convertTo(CV_8U) in one instruction (as in sub10_kernel)
                     unsigned q4 = 0;
 #pragma unroll
@@ -1980,9 +1996,9 @@ __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
             const int core_y0 = ctx.core_y0, core_y1 = min(ctx.core_y1, pl_h);
             const int core_x0 = ctx.core_x0, core_x1 = min(ctx.core_x1, pl_w);
             const int x_lo = max(core_x0, xs) - xs, x_hi = min(core_x1, xs + 16) - xs;
-            const int b_lo = x_lo * R * 3, b_hi = x_hi * R * 3;
+            const int b_lo = x_lo * R * 3 * SB, b_hi = x_hi * R * 3 * SB;
             // (32-bit offset inside the output frame: uva_net_process_u8_device refuses frames of 4 GB and more)
-            uint8_t* const dbase = a.dst_u8 + ((unsigned)(src_y0 + y_t) * (unsigned)R * dst_stride32 + (unsigned)(src_x0 + xs) * (unsigned)(R * 3));
+            uint8_t* const dbase = a.dst_u8 + ((unsigned)(src_y0 + y_t) * (unsigned)R * dst_stride32 + (unsigned)(src_x0 + xs) * (unsigned)(R * 3 * SB));
             const bool full = b_lo == 0 && b_hi == ROWB && y_t >= core_y0 && y_t + 2 <= core_y1;
             const size_t align_bits = (size_t)dbase | a.dst_stride;
             constexpr int Q = ROWB / 16, WORDS = ROWB / 4;
@@ -2038,17 +2054,20 @@ __global__ __launch_bounds__(512, 2) void tail_kernel(ConvArgs a)
 constexpr int TAIL4_SLOTS = 3;
 constexpr int TAIL4_MB = 3;                                  // 16-channel blocks = colour channels
 constexpr int TAIL4_W_LDS = 18 * TAIL4_MB * 1024;            // weights: [k-step][block][lane][8] fp16
-template <int NF>
+template <int NF, typename T = uint8_t>
 constexpr int tail4_lds_bytes()
 {
-    return TAIL4_SLOTS * TrunkGeo<NF>::SLOTB + TAIL4_W_LDS + PARAMS_AND_PLANES_LDS + TAIL_SCHED_MAX * 16 + TAIL_RESID_LDS;
+    return TAIL4_SLOTS * TrunkGeo<NF>::SLOTB + TAIL4_W_LDS + PARAMS_AND_PLANES_LDS + TAIL_SCHED_MAX * 16 + TAIL_RESID_LDS * (int)sizeof(T);
 }
 static_assert(tail4_lds_bytes<64>() <= 160 * 1024, "tail4 kernel LDS budget");
+static_assert(tail4_lds_bytes<64, uint16_t>() <= 160 * 1024, "tail4 kernel LDS budget (u16)");
 
-template <int NF>
+// T: uint8_t, or uint16_t for the 16-bit route (see tail_kernel); a u16 lane stores 24 contiguous bytes
+template <int NF, typename T>
 __global__ __launch_bounds__(512, 2) void tail4_kernel(ConvArgs a)
 {
     static_assert(NF == 64, "written for the 4x net's tail (64 -> 48)");
+    constexpr int SB = (int)sizeof(T);
     using G = Geo<NF, TH4>;
     using TG = TrunkGeo<NF>;
     constexpr int R = 4, MB = TAIL4_MB;
@@ -2134,8 +2153,8 @@ __global__ __launch_bounds__(512, 2) void tail4_kernel(ConvArgs a)
     if (grp == 1) group_barrier();   // group 1 runs half a period behind group 0
     int cur = grp;                   // ring slot of this group's current tile: (2*it + grp) % 3
 
-    const unsigned resid_lds = lds0 + (unsigned)(resid_all - smem) + wave8 * 128;
-    const char* const resid_rd = resid_all + wave8 * 128;
+    const unsigned resid_lds = lds0 + (unsigned)(resid_all - smem) + wave8 * (128 * SB);
+    const char* const resid_rd = resid_all + wave8 * (128 * SB);
     const char* const wrd = w_lds + lane * 16;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // the lane's 3 x 4 output channels' bias, resident (no LDS round trip at the top of every epilogue)
@@ -2167,19 +2186,19 @@ __global__ __launch_bounds__(512, 2) void tail4_kernel(ConvArgs a)
         int sh[2];
         {
             const int xc = min(xs, pl_w - 1);
-            const unsigned nb = 3u * (unsigned)min(16, pl_w - xc);
+            const unsigned nb = 3u * SB * (unsigned)min(16, pl_w - xc);
             unsigned voff = 0;
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const int yc = min(y_t + n, pl_h - 1);
-                const unsigned ra = (unsigned)(src_y0 + yc) * src_stride32 + (unsigned)(src_x0 + xc) * 3u;
+                const unsigned ra = (unsigned)(src_y0 + yc) * src_stride32 + (unsigned)(src_x0 + xc) * (3u * SB);
                 const unsigned al = src_lo2 + ra;
                 sh[n] = (int)(al & 3u);
                 const int dmax = (int)((((al + nb - 1u) & ~3u) - (al & ~3u)) >> 2);
-                const unsigned vo = (ra - (unsigned)sh[n]) + 4u * (unsigned)min(lane & 15, dmax);
-                if ((lane >> 4) == n) voff = vo;
+                const unsigned vo = (ra - (unsigned)sh[n]) + 4u * (unsigned)min(lane & (16 * SB - 1), dmax);
+                if ((lane >> (SB == 1 ? 4 : 5)) == n) voff = vo;
             }
-            if (active && lane < 32) glds4_s(a.src_u8, voff, resid_lds);
+            if (active && lane < 32 * SB) glds4_s(a.src_u8, voff, resid_lds);
         }
         f32x4 acc[2][MB];
         {
@@ -2239,6 +2258,7 @@ __global__ __launch_bounds__(512, 2) void tail4_kernel(ConvArgs a)
             const int lane_o = opaque(lane);
             const int g = lane_o >> 4, p = lane_o & 15;          // sub-row of the 4x4 output block, pixel
             const float norm = (float)(1 / 255.0);
+            const float vmax = SB == 1 ? 255.0f : 65535.0f;
             const int core_y0 = ctx.core_y0, core_y1 = min(ctx.core_y1, pl_h);
             const int core_x0 = ctx.core_x0, core_x1 = min(ctx.core_x1, pl_w);
             const bool col_ok = xs + p >= core_x0 && xs + p < core_x1;
@@ -2251,16 +2271,38 @@ __global__ __launch_bounds__(512, 2) void tail4_kernel(ConvArgs a)
                 float q[MB][4];
                 unsigned rb[MB];
 #pragma unroll
-                for (int m = 0; m < MB; ++m) rb[m] = *(const uint8_t*)(resid_rd + n * 64 + sh[n] + 3 * p + m);
+                for (int m = 0; m < MB; ++m) rb[m] = *(const T*)(resid_rd + n * 64 * SB + sh[n] + (3 * p + m) * SB);
 #pragma unroll
                 for (int m = 0; m < MB; ++m) {
-                    const float res = (float)rb[m] * norm;
+                    const float res = SB == 1 ? (float)rb[m] * norm : ((float)rb[m] / 257.0f) * norm;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) q[m][j] = ((acc[n][m][j] + b4[m][j]) + res) * 255.0f;
+                    for (int j = 0; j < 4; ++j) q[m][j] = ((acc[n][m][j] + b4[m][j]) + res) * vmax;
                 }
                 if (y >= core_y0 && y < core_y1 && col_ok) {
                     // output row 4y + g, pixels 4(x) .. 4(x)+3, BGR each: 12 contiguous bytes
-                    uint8_t* d = a.dst_u8 + ((size_t)(src_y0 + y) * R + g) * a.dst_stride + (size_t)(src_x0 + xs + p) * R * 3;
+                    uint8_t* d = a.dst_u8 + ((size_t)(src_y0 + y) * R + g) * a.dst_stride + (size_t)(src_x0 + xs + p) * R * 3 * SB;
+                    if constexpr (SB == 2) {
+                        // 12 samples, pixel-major: clamp(rint(q), 0, 65535) (rint: half to even, the u8 route's rounding)
+                        auto cv = [](float f) __attribute__((always_inline)) {
+                            return (unsigned)__builtin_amdgcn_fmed3f(__builtin_rintf(f), 0.f, 65535.f);
+                        };
+                        unsigned wd[6];
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) {
+                            const int e0 = 2 * k, e1 = 2 * k + 1;      // sample e = 3 * sub-column + channel
+                            wd[k] = cv(q[e0 % 3][e0 / 3]) | (cv(q[e1 % 3][e1 / 3]) << 16);
+                        }
+                        if (aligned) {
+#pragma unroll
+                            for (int k = 0; k < 6; ++k) ((unsigned*)d)[k] = wd[k];
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < 6; ++k) {
+                                ((uint16_t*)d)[2 * k] = (uint16_t)wd[k]; ((uint16_t*)d)[2 * k + 1] = (uint16_t)(wd[k] >> 16);
+                            }
+                        }
+                        continue;
+                    }
                     auto pk4 = [](float b0, float b1, float b2, float b3) __attribute__((always_inline)) {
                         unsigned r = __builtin_amdgcn_cvt_pk_u8_f32(b0, 0, 0u);
                         r = __builtin_amdgcn_cvt_pk_u8_f32(b1, 1, r);
@@ -2415,6 +2457,7 @@ __global__ __launch_bounds__(256, HEAD_WPE) void head_kernel(HeadArgs a)
 
 // ----------------------------------------------------------------------------------------------
 // headp_kernel<NF, SRC>: head_kernel's arithmetic (same K layout, same rounding points, same bytes) as a PERSISTENT,
+// (SRC 2, this kernel only: u16 HWC BGR, the 16-bit route -- operand fp16(v / 257), in_scale 1/255)
 // software-pipelined kernel.  head_kernel writes 128 B per pixel and computes next to nothing, yet ran at half the
 // rate a plain store loop reaches (tools/hbm_stream_bench.hip: 273 MB in 39 us): a workgroup lived for its chain of
 // dependent loads -- plane lookup, pixels, (weights) -- and a CU holds three of them.  Here a workgroup keeps its
@@ -2496,6 +2539,13 @@ __global__ __launch_bounds__(256, HEADP_WG_PER_CU) void headp_kernel(HeadArgs a)
             if constexpr (SRC == 0) {
                 const uint8_t* sp = a.src_u8 + (size_t)(T.src_y0 + yc) * a.src_stride + (size_t)(T.src_x0 + xc) * 3;
                 pv[k][0] = (float)sp[0]; pv[k][1] = (float)sp[1]; pv[k][2] = (float)sp[2];
+            } else if constexpr (SRC == 2) {
+                // u16 samples scaled to 0..255 in fp32 (v * (1/257)) before the fp16 rounding: raw codes >= 65520 would be inf in
+                // fp16; this keeps fp16's 2^-11 relative precision and makes v = 257 k exactly k, the u8 route's operand (the
+                // 1/255 stays on the fp32 accumulator, in_scale, as there)
+                const uint16_t* sp = (const uint16_t*)(a.src_u8 + (size_t)(T.src_y0 + yc) * a.src_stride + (size_t)(T.src_x0 + xc) * 6);
+                constexpr float inv = (float)(1 / 257.0);
+                pv[k][0] = (float)sp[0] * inv; pv[k][1] = (float)sp[1] * inv; pv[k][2] = (float)sp[2] * inv;
             } else {
                 const size_t hw = (size_t)T.pl_h * T.pl_w, o = (size_t)yc * T.pl_w + xc;
                 pv[k][0] = a.src_f32[o]; pv[k][1] = a.src_f32[hw + o]; pv[k][2] = a.src_f32[2 * hw + o];

@@ -5,6 +5,8 @@
 //   yuv420p  Y [h][w] u8, then U [ch][cw], then V [ch][cw]
 //   nv12     Y [h][w] u8, then [ch][cw][2] interleaved U, V
 //   p010le   nv12's layout in 16-bit little-endian words, the 10-bit value in the high bits (v << 6)
+//   yuv420p10le  yuv420p's layout in 16-bit little-endian words, the 10-bit value in the low bits
+//   bgr48le  [h][w][3] u16 (unorm16): the 16-bit route's BGR (section 7.4)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -12,16 +14,19 @@
 
 namespace uva {
 
-enum { PIX_BGR24 = 0, PIX_YUV420P = 1, PIX_NV12 = 2, PIX_P010LE = 3, PIX_NFMT = 4 };
+enum { PIX_BGR24 = 0, PIX_YUV420P = 1, PIX_NV12 = 2, PIX_P010LE = 3, PIX_YUV420P10LE = 5, PIX_BGR48LE = 6, PIX_NFMT = 7 };   // (4: never assigned)
 // colour word: matrix in bit 0 (0 BT.601, 1 BT.709), bit 1 set = full ("pc") range, clear = limited ("tv") range
 enum { PIX_CSP_BT601 = 0, PIX_CSP_BT709 = 1, PIX_RANGE_FULL = 2, PIX_COLOUR_MASK = 3 };
 
 // bytes of one dense h x w frame of `fmt`; 0 for an unknown format or a size <= 0
 size_t pix_frame_bytes(int fmt, int h, int w);
 
-// bgr (dense u8 [h][w][3]) <- src of format fmt (!= PIX_BGR24), on `stream`
+// bgr (dense u8 [h][w][3]) <- src of format fmt (a Y'CbCr format), on `stream`
 hipError_t launch_pix_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint8_t* bgr, int h, int w);
-// dst of format fmt (!= PIX_BGR24) <- bgr (dense u8 [h][w][3]), on `stream`
+// dst of format fmt (a Y'CbCr format) <- bgr (dense u8 [h][w][3]), on `stream`
 hipError_t launch_pix_from_bgr(hipStream_t stream, int fmt, int colour, const uint8_t* bgr, void* dst, int h, int w);
+// the 16-bit route: bgr is dense u16 [h][w][3]; fmt is a Y'CbCr format or PIX_BGR24 (v * 257 in, rint(v / 257) out)
+hipError_t launch_pix16_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint16_t* bgr, int h, int w);
+hipError_t launch_pix16_from_bgr(hipStream_t stream, int fmt, int colour, const uint16_t* bgr, void* dst, int h, int w);
 
 }  // namespace uva

@@ -2,6 +2,9 @@
 // translation unit of its own like uva_sww.hip.  Two kernel families, each instantiated per format:
 //   pix_from_bgr  u8 BGR -> yuv420p / nv12 / p010le   (behind the net: its u8 result is what gets converted)
 //   pix_to_bgr    yuv420p / nv12 / p010le -> u8 BGR   (in front of the net)
+// (yuv420p10le: p010le's arithmetic in planar words, the value in the low 10 bits), and the 16-bit route's twins (section 7.4):
+// Both families are templated on the BGR sample type S: u8, or u16 (unorm16) for the 16-bit route (section 7.4).  Beside them
+//   pix_widen / pix_narrow  u8 BGR <-> u16 BGR (v * 257, rint(v / 257))
 // One thread covers 8 pixels of two rows -- a 2x2 block per chroma sample, so every chroma sample is read or written once.  Both
 // are memory-bound: with w % 8 == 0 (and 16-byte aligned bases) a thread's bytes move as 8- and 16-byte accesses, lanes side by
 // side along the row; elsewhere (odd sizes, the frame's right / bottom edge) byte by byte with bounds checks.
@@ -21,7 +24,12 @@ constexpr int BX = 64, BY = 4;      // threads of a workgroup along x (groups of
 struct FwdCoef { int yr, yg, yb, ur, ug, ub, vr, vg, vb, yoff, coff, maxv; };
 struct InvCoef { int ky, rv, gu, gv, bu, yoff, coff; };
 
-int fix16(double c) { return (int)std::floor(c * 65536.0 + 0.5); }
+int fixs(double c, int sh) { return (int)std::floor(std::ldexp(c, sh) + 0.5); }
+
+// The 16-bit route's shifts: u16 samples times round(c * 2^16) would overflow int32, so the forward
+// coefficients are c * (code range / 65535) * 2^19 (a 2x2 chroma sum of 10-bit full range stays below 2^31) and the inverse
+// ones c * (65535 / code range) * 2^13 (the largest |sum|, ~1.41e5 * 2^13, likewise)
+constexpr int FWD16_SH = 19, INV16_SH = 13;
 
 void matrix(int colour, double& kr, double& kb)
 {
@@ -38,36 +46,40 @@ void ranges(int colour, int depth, int& ys, int& cs, int& yoff)
     yoff = full ? 0 : 16 << (depth - 8);
 }
 
-FwdCoef fwd_coef(int colour, int depth)
+FwdCoef fwd_coef(int colour, int depth, bool u16 = false)
 {
     double kr, kb;
     matrix(colour, kr, kb);
     const double kg = 1.0 - kr - kb;
     int ys, cs, yoff;
     ranges(colour, depth, ys, cs, yoff);
-    const double sy = ys / 255.0, sc = cs / 255.0;
+    const double vmax = u16 ? 65535.0 : 255.0;
+    const int sh = u16 ? FWD16_SH : 16;
+    const double sy = ys / vmax, sc = cs / vmax;
     FwdCoef c;
-    c.yr = fix16(kr * sy); c.yg = fix16(kg * sy); c.yb = fix16(kb * sy);
-    c.ur = fix16(-kr / (2 * (1 - kb)) * sc); c.ug = fix16(-kg / (2 * (1 - kb)) * sc); c.ub = fix16(0.5 * sc);
-    c.vr = fix16(0.5 * sc); c.vg = fix16(-kg / (2 * (1 - kr)) * sc); c.vb = fix16(-kb / (2 * (1 - kr)) * sc);
+    c.yr = fixs(kr * sy, sh); c.yg = fixs(kg * sy, sh); c.yb = fixs(kb * sy, sh);
+    c.ur = fixs(-kr / (2 * (1 - kb)) * sc, sh); c.ug = fixs(-kg / (2 * (1 - kb)) * sc, sh); c.ub = fixs(0.5 * sc, sh);
+    c.vr = fixs(0.5 * sc, sh); c.vg = fixs(-kg / (2 * (1 - kr)) * sc, sh); c.vb = fixs(-kb / (2 * (1 - kr)) * sc, sh);
     c.yoff = yoff; c.coff = 1 << (depth - 1); c.maxv = (1 << depth) - 1;
     return c;
 }
 
-InvCoef inv_coef(int colour, int depth)
+InvCoef inv_coef(int colour, int depth, bool u16 = false)
 {
     double kr, kb;
     matrix(colour, kr, kb);
     const double kg = 1.0 - kr - kb;
     int ys, cs, yoff;
     ranges(colour, depth, ys, cs, yoff);
-    const double ky = 255.0 / ys, kc = 255.0 / cs;
+    const double vmax = u16 ? 65535.0 : 255.0;
+    const int sh = u16 ? INV16_SH : 16;
+    const double ky = vmax / ys, kc = vmax / cs;
     InvCoef c;
-    c.ky = fix16(ky);
-    c.rv = fix16(2 * (1 - kr) * kc);
-    c.bu = fix16(2 * (1 - kb) * kc);
-    c.gu = fix16(-2 * kb * (1 - kb) / kg * kc);
-    c.gv = fix16(-2 * kr * (1 - kr) / kg * kc);
+    c.ky = fixs(ky, sh);
+    c.rv = fixs(2 * (1 - kr) * kc, sh);
+    c.bu = fixs(2 * (1 - kb) * kc, sh);
+    c.gu = fixs(-2 * kb * (1 - kb) / kg * kc, sh);
+    c.gv = fixs(-2 * kr * (1 - kr) / kg * kc, sh);
     c.yoff = yoff; c.coff = 1 << (depth - 1);
     return c;
 }
@@ -81,12 +93,15 @@ __device__ __forceinline__ uint32_t pack2(int a, int b) { return (uint32_t)a | (
 __device__ __forceinline__ int byte_of(const uint32_t* d, int k) { return (d[k >> 2] >> (8 * (k & 3))) & 255; }
 __device__ __forceinline__ int half_of(const uint32_t* d, int k) { return (d[k >> 1] >> (16 * (k & 1))) & 0xffff; }
 
-// u8 BGR [h][w][3] -> planes.  yp: the Y plane; up / vp: U and V (yuv420p) or the interleaved plane and null (nv12, p010le).
-template <int FMT, bool VEC>
-__global__ __launch_bounds__(BX * BY) void pix_from_bgr(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
+// BGR [h][w][3] of S (u8, or u16 for the 16-bit route) -> planes.  yp: the Y plane; up / vp: U and V (yuv420p, yuv420p10le) or
+// the interleaved plane and null (nv12, p010le).
+template <int FMT, bool VEC, typename S>
+__global__ __launch_bounds__(BX * BY) void pix_from_bgr(const S* __restrict__ bgr, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
                                                          uint8_t* __restrict__ vp, int h, int w, FwdCoef c)
 {
-    constexpr bool W16 = FMT == PIX_P010LE;
+    constexpr bool W16 = FMT == PIX_P010LE || FMT == PIX_YUV420P10LE;
+    constexpr int LS = FMT == PIX_P010LE ? 6 : 0;                 // where a 10-bit value sits in its word
+    constexpr int SH = sizeof(S) == 1 ? 16 : FWD16_SH;
     const int x0 = (blockIdx.x * BX + threadIdx.x) * PX, gy = blockIdx.y * BY + threadIdx.y, y0 = 2 * gy;
     if (x0 >= w || y0 >= h) return;
     const int cw = (w + 1) >> 1;
@@ -94,16 +109,27 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const uint8_t* __restric
     int r[2][PX], g[2][PX], b[2][PX];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const uint8_t* row = bgr + ((size_t)(y0 + k) * w + x0) * 3;
+        const S* row = bgr + ((size_t)(y0 + k) * w + x0) * 3;
         if (whole) {
-            uint32_t d[6];
+            if constexpr (sizeof(S) == 1) {
+                uint32_t d[6];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const uint2 v = reinterpret_cast<const uint2*>(row)[q];
-                d[2 * q] = v.x; d[2 * q + 1] = v.y;
+                for (int q = 0; q < 3; ++q) {
+                    const uint2 v = reinterpret_cast<const uint2*>(row)[q];
+                    d[2 * q] = v.x; d[2 * q + 1] = v.y;
+                }
+#pragma unroll
+                for (int i = 0; i < PX; ++i) { b[k][i] = byte_of(d, 3 * i); g[k][i] = byte_of(d, 3 * i + 1); r[k][i] = byte_of(d, 3 * i + 2); }
+            } else {
+                uint32_t d[12];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const uint4 v = reinterpret_cast<const uint4*>(row)[q];
+                    d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+                }
+#pragma unroll
+                for (int i = 0; i < PX; ++i) { b[k][i] = half_of(d, 3 * i); g[k][i] = half_of(d, 3 * i + 1); r[k][i] = half_of(d, 3 * i + 2); }
             }
-#pragma unroll
-            for (int i = 0; i < PX; ++i) { b[k][i] = byte_of(d, 3 * i); g[k][i] = byte_of(d, 3 * i + 1); r[k][i] = byte_of(d, 3 * i + 2); }
         } else {
 #pragma unroll
             for (int i = 0; i < PX; ++i) {
@@ -119,17 +145,17 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const uint8_t* __restric
         int yv[PX];
 #pragma unroll
         for (int i = 0; i < PX; ++i)
-            yv[i] = clampi((c.yr * r[k][i] + c.yg * g[k][i] + c.yb * b[k][i] + (c.yoff << 16) + 32768) >> 16, c.maxv);
+            yv[i] = clampi((c.yr * r[k][i] + c.yg * g[k][i] + c.yb * b[k][i] + (c.yoff << SH) + (1 << (SH - 1))) >> SH, c.maxv);
         const size_t o = (size_t)(y0 + k) * w + x0;
         if (W16) {
             uint16_t* dst = reinterpret_cast<uint16_t*>(yp) + o;
             if (whole) {
-                reinterpret_cast<uint4*>(dst)[0] = make_uint4(pack2(yv[0] << 6, yv[1] << 6), pack2(yv[2] << 6, yv[3] << 6),
-                                                              pack2(yv[4] << 6, yv[5] << 6), pack2(yv[6] << 6, yv[7] << 6));
+                reinterpret_cast<uint4*>(dst)[0] = make_uint4(pack2(yv[0] << LS, yv[1] << LS), pack2(yv[2] << LS, yv[3] << LS),
+                                                              pack2(yv[4] << LS, yv[5] << LS), pack2(yv[6] << LS, yv[7] << LS));
             } else {
 #pragma unroll
                 for (int i = 0; i < PX; ++i)
-                    if (x0 + i < w) dst[i] = (uint16_t)(yv[i] << 6);
+                    if (x0 + i < w) dst[i] = (uint16_t)(yv[i] << LS);
             }
         } else {
             uint8_t* dst = yp + o;
@@ -154,7 +180,7 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const uint8_t* __restric
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 if (k < rows && i < cols) { sr += r[k][2 * j + i]; sg += g[k][2 * j + i]; sb += b[k][2 * j + i]; }
-        const int s = 16 + (rows - 1) + (cols - 1);
+        const int s = SH + (rows - 1) + (cols - 1);
         cu[j] = clampi((c.ur * sr + c.ug * sg + c.ub * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
         cv[j] = clampi((c.vr * sr + c.vg * sg + c.vb * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
     }
@@ -169,6 +195,17 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const uint8_t* __restric
 #pragma unroll
             for (int j = 0; j < PX / 2; ++j)
                 if (cx0 + j < cw) { du[j] = (uint8_t)cu[j]; dv[j] = (uint8_t)cv[j]; }
+        }
+    } else if (FMT == PIX_YUV420P10LE) {
+        uint16_t* du = reinterpret_cast<uint16_t*>(up) + (size_t)gy * cw + cx0;
+        uint16_t* dv = reinterpret_cast<uint16_t*>(vp) + (size_t)gy * cw + cx0;
+        if (whole) {
+            reinterpret_cast<uint2*>(du)[0] = make_uint2(pack2(cu[0], cu[1]), pack2(cu[2], cu[3]));
+            reinterpret_cast<uint2*>(dv)[0] = make_uint2(pack2(cv[0], cv[1]), pack2(cv[2], cv[3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j)
+                if (cx0 + j < cw) { du[j] = (uint16_t)cu[j]; dv[j] = (uint16_t)cv[j]; }
         }
     } else if (FMT == PIX_NV12) {
         uint8_t* d = up + (size_t)gy * 2 * cw + 2 * cx0;
@@ -192,12 +229,15 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const uint8_t* __restric
     }
 }
 
-// planes -> u8 BGR [h][w][3]; chroma replicated over its 2x2 block; p010le converts from the 10-bit values (word >> 6)
-template <int FMT, bool VEC>
+// planes -> BGR [h][w][3] of S; chroma replicated over its 2x2 block; p010le converts from the 10-bit values (word >> 6),
+// yuv420p10le from the low 10 bits of its words
+template <int FMT, bool VEC, typename S>
 __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
-                                                       const uint8_t* __restrict__ vp, uint8_t* __restrict__ bgr, int h, int w, InvCoef c)
+                                                       const uint8_t* __restrict__ vp, S* __restrict__ bgr, int h, int w, InvCoef c)
 {
-    constexpr bool W16 = FMT == PIX_P010LE;
+    constexpr bool W16 = FMT == PIX_P010LE || FMT == PIX_YUV420P10LE;
+    constexpr int SH = sizeof(S) == 1 ? 16 : INV16_SH;
+    constexpr int VMAX = sizeof(S) == 1 ? 255 : 65535;
     const int x0 = (blockIdx.x * BX + threadIdx.x) * PX, gy = blockIdx.y * BY + threadIdx.y, y0 = 2 * gy;
     if (x0 >= w || y0 >= h) return;
     const int cw = (w + 1) >> 1, cx0 = x0 >> 1;
@@ -215,6 +255,21 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
             for (int j = 0; j < PX / 2; ++j) {
                 const bool in = cx0 + j < cw;
                 cu[j] = in ? su[j] : 0; cv[j] = in ? sv[j] : 0;
+            }
+        }
+    } else if (FMT == PIX_YUV420P10LE) {
+        const uint16_t* su = reinterpret_cast<const uint16_t*>(up) + (size_t)gy * cw + cx0;
+        const uint16_t* sv = reinterpret_cast<const uint16_t*>(vp) + (size_t)gy * cw + cx0;
+        if (whole) {
+            const uint2 vu = reinterpret_cast<const uint2*>(su)[0], vv = reinterpret_cast<const uint2*>(sv)[0];
+            const uint32_t du[2] = {vu.x, vu.y}, dv[2] = {vv.x, vv.y};
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j) { cu[j] = half_of(du, j) & 1023; cv[j] = half_of(dv, j) & 1023; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j) {
+                const bool in = cx0 + j < cw;
+                cu[j] = in ? su[j] & 1023 : 0; cv[j] = in ? sv[j] & 1023 : 0;
             }
         }
     } else if (FMT == PIX_NV12) {
@@ -251,9 +306,9 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
 #pragma unroll
     for (int j = 0; j < PX / 2; ++j) {
         const int u = cu[j] - c.coff, v = cv[j] - c.coff;
-        tr[j] = c.rv * v + 32768;
-        tg[j] = c.gu * u + c.gv * v + 32768;
-        tb[j] = c.bu * u + 32768;
+        tr[j] = c.rv * v + (1 << (SH - 1));
+        tg[j] = c.gu * u + c.gv * v + (1 << (SH - 1));
+        tb[j] = c.bu * u + (1 << (SH - 1));
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -266,10 +321,13 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
                 const uint4 v = reinterpret_cast<const uint4*>(s)[0];
                 const uint32_t d[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-                for (int i = 0; i < PX; ++i) yv[i] = half_of(d, i) >> 6;
+                for (int i = 0; i < PX; ++i) yv[i] = FMT == PIX_P010LE ? half_of(d, i) >> 6 : half_of(d, i) & 1023;
             } else {
 #pragma unroll
-                for (int i = 0; i < PX; ++i) yv[i] = x0 + i < w ? s[i] >> 6 : 0;
+                for (int i = 0; i < PX; ++i) {
+                    if (FMT == PIX_P010LE) yv[i] = x0 + i < w ? s[i] >> 6 : 0;
+                    else yv[i] = x0 + i < w ? s[i] & 1023 : 0;
+                }
             }
         } else {
             const uint8_t* s = yp + o;
@@ -287,21 +345,62 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
 #pragma unroll
         for (int i = 0; i < PX; ++i) {
             const int yy = c.ky * (yv[i] - c.yoff);
-            px[3 * i] = clampi((yy + tb[i >> 1]) >> 16, 255);
-            px[3 * i + 1] = clampi((yy + tg[i >> 1]) >> 16, 255);
-            px[3 * i + 2] = clampi((yy + tr[i >> 1]) >> 16, 255);
+            px[3 * i] = clampi((yy + tb[i >> 1]) >> SH, VMAX);
+            px[3 * i + 1] = clampi((yy + tg[i >> 1]) >> SH, VMAX);
+            px[3 * i + 2] = clampi((yy + tr[i >> 1]) >> SH, VMAX);
         }
-        uint8_t* dst = bgr + o * 3;
+        S* dst = bgr + o * 3;
         if (whole) {
+            if constexpr (sizeof(S) == 1) {
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
-                reinterpret_cast<uint2*>(dst)[q] = make_uint2(pack4(px[8 * q], px[8 * q + 1], px[8 * q + 2], px[8 * q + 3]),
-                                                              pack4(px[8 * q + 4], px[8 * q + 5], px[8 * q + 6], px[8 * q + 7]));
+                for (int q = 0; q < 3; ++q)
+                    reinterpret_cast<uint2*>(dst)[q] = make_uint2(pack4(px[8 * q], px[8 * q + 1], px[8 * q + 2], px[8 * q + 3]),
+                                                                  pack4(px[8 * q + 4], px[8 * q + 5], px[8 * q + 6], px[8 * q + 7]));
+            } else {
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    reinterpret_cast<uint4*>(dst)[q] = make_uint4(pack2(px[8 * q], px[8 * q + 1]), pack2(px[8 * q + 2], px[8 * q + 3]),
+                                                                  pack2(px[8 * q + 4], px[8 * q + 5]), pack2(px[8 * q + 6], px[8 * q + 7]));
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < 3 * PX; ++i)
-                if (x0 + i / 3 < w) dst[i] = (uint8_t)px[i];
+                if (x0 + i / 3 < w) dst[i] = (S)px[i];
         }
+    }
+}
+
+// u8 BGR <-> u16 BGR, 8 samples per thread: v * 257 is exact (v / 255 = 257 v / 65535); rint(v / 257) never meets a tie (257 is
+// odd), so it is floor((v + 128) / 257)
+constexpr int WN = 8;
+template <bool VEC>
+__global__ __launch_bounds__(256) void pix_widen(const uint8_t* __restrict__ src, uint16_t* __restrict__ dst, size_t n)
+{
+    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * WN;
+    if (i0 >= n) return;
+    if (VEC && i0 + WN <= n) {
+        const uint2 v = *reinterpret_cast<const uint2*>(src + i0);
+        const uint32_t d[2] = {v.x, v.y};
+        *reinterpret_cast<uint4*>(dst + i0) = make_uint4(pack2(byte_of(d, 0) * 257, byte_of(d, 1) * 257), pack2(byte_of(d, 2) * 257, byte_of(d, 3) * 257),
+                                                         pack2(byte_of(d, 4) * 257, byte_of(d, 5) * 257), pack2(byte_of(d, 6) * 257, byte_of(d, 7) * 257));
+    } else {
+        for (size_t i = i0; i < n && i < i0 + WN; ++i) dst[i] = (uint16_t)(src[i] * 257);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void pix_narrow(const uint16_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n)
+{
+    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * WN;
+    if (i0 >= n) return;
+    auto nar = [](int v) __attribute__((always_inline)) { return (v + 128) / 257; };
+    if (VEC && i0 + WN <= n) {
+        const uint4 v = *reinterpret_cast<const uint4*>(src + i0);
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+        *reinterpret_cast<uint2*>(dst + i0) = make_uint2(pack4(nar(half_of(d, 0)), nar(half_of(d, 1)), nar(half_of(d, 2)), nar(half_of(d, 3))),
+                                                         pack4(nar(half_of(d, 4)), nar(half_of(d, 5)), nar(half_of(d, 6)), nar(half_of(d, 7))));
+    } else {
+        for (size_t i = i0; i < n && i < i0 + WN; ++i) dst[i] = (uint8_t)nar(src[i]);
     }
 }
 
@@ -311,6 +410,7 @@ void planes(int fmt, const uint8_t* base, int h, int w, const uint8_t** yp, cons
     const size_t cw = (size_t)(w + 1) / 2, ch = (size_t)(h + 1) / 2, wh = (size_t)w * h;
     *yp = base;
     if (fmt == PIX_YUV420P) { *up = base + wh; *vp = base + wh + cw * ch; }
+    else if (fmt == PIX_YUV420P10LE) { *up = base + 2 * wh; *vp = base + 2 * (wh + cw * ch); }
     else if (fmt == PIX_NV12) { *up = base + wh; *vp = nullptr; }
     else { *up = base + 2 * wh; *vp = nullptr; }
 }
@@ -329,55 +429,98 @@ size_t pix_frame_bytes(int fmt, int h, int w)
     switch (fmt) {
     case PIX_BGR24: return 3 * wh;
     case PIX_YUV420P: case PIX_NV12: return wh + c;
-    case PIX_P010LE: return 2 * (wh + c);
+    case PIX_P010LE: case PIX_YUV420P10LE: return 2 * (wh + c);
+    case PIX_BGR48LE: return 6 * wh;
     default: return 0;
     }
 }
 
-hipError_t launch_pix_from_bgr(hipStream_t stream, int fmt, int colour, const uint8_t* bgr, void* dst, int h, int w)
+namespace {
+int depth_of(int fmt) { return fmt == PIX_P010LE || fmt == PIX_YUV420P10LE ? 10 : 8; }
+
+template <typename S>
+hipError_t from_bgr(hipStream_t stream, int fmt, int colour, const S* bgr, void* dst, int h, int w)
 {
     if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
     const uint8_t *yp, *up, *vp;
     planes(fmt, (const uint8_t*)dst, h, w, &yp, &up, &vp);
-    const FwdCoef c = fwd_coef(colour, fmt == PIX_P010LE ? 10 : 8);
+    const FwdCoef c = fwd_coef(colour, depth_of(fmt), sizeof(S) == 2);
     const bool vec = vec_ok(bgr, dst, w);
     const dim3 grid = grid_of(h, w), block(BX, BY);
     uint8_t *y = const_cast<uint8_t*>(yp), *u = const_cast<uint8_t*>(up), *v = const_cast<uint8_t*>(vp);
 #define UVA_PIX_LAUNCH(F)                                                                                                   \
     do {                                                                                                                    \
-        if (vec) hipLaunchKernelGGL((pix_from_bgr<F, true>), grid, block, 0, stream, bgr, y, u, v, h, w, c);               \
-        else hipLaunchKernelGGL((pix_from_bgr<F, false>), grid, block, 0, stream, bgr, y, u, v, h, w, c);                  \
+        if (vec) hipLaunchKernelGGL((pix_from_bgr<F, true, S>), grid, block, 0, stream, bgr, y, u, v, h, w, c);            \
+        else hipLaunchKernelGGL((pix_from_bgr<F, false, S>), grid, block, 0, stream, bgr, y, u, v, h, w, c);               \
     } while (0)
     switch (fmt) {
     case PIX_YUV420P: UVA_PIX_LAUNCH(PIX_YUV420P); break;
     case PIX_NV12: UVA_PIX_LAUNCH(PIX_NV12); break;
     case PIX_P010LE: UVA_PIX_LAUNCH(PIX_P010LE); break;
+    case PIX_YUV420P10LE: UVA_PIX_LAUNCH(PIX_YUV420P10LE); break;
     default: return hipErrorInvalidValue;
     }
 #undef UVA_PIX_LAUNCH
     return hipGetLastError();
 }
 
-hipError_t launch_pix_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint8_t* bgr, int h, int w)
+template <typename S>
+hipError_t to_bgr(hipStream_t stream, int fmt, int colour, const void* src, S* bgr, int h, int w)
 {
     if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
     const uint8_t *y, *u, *v;
     planes(fmt, (const uint8_t*)src, h, w, &y, &u, &v);
-    const InvCoef c = inv_coef(colour, fmt == PIX_P010LE ? 10 : 8);
+    const InvCoef c = inv_coef(colour, depth_of(fmt), sizeof(S) == 2);
     const bool vec = vec_ok(bgr, src, w);
     const dim3 grid = grid_of(h, w), block(BX, BY);
 #define UVA_PIX_LAUNCH(F)                                                                                                   \
     do {                                                                                                                    \
-        if (vec) hipLaunchKernelGGL((pix_to_bgr<F, true>), grid, block, 0, stream, y, u, v, bgr, h, w, c);                 \
-        else hipLaunchKernelGGL((pix_to_bgr<F, false>), grid, block, 0, stream, y, u, v, bgr, h, w, c);                    \
+        if (vec) hipLaunchKernelGGL((pix_to_bgr<F, true, S>), grid, block, 0, stream, y, u, v, bgr, h, w, c);              \
+        else hipLaunchKernelGGL((pix_to_bgr<F, false, S>), grid, block, 0, stream, y, u, v, bgr, h, w, c);                 \
     } while (0)
     switch (fmt) {
     case PIX_YUV420P: UVA_PIX_LAUNCH(PIX_YUV420P); break;
     case PIX_NV12: UVA_PIX_LAUNCH(PIX_NV12); break;
     case PIX_P010LE: UVA_PIX_LAUNCH(PIX_P010LE); break;
+    case PIX_YUV420P10LE: UVA_PIX_LAUNCH(PIX_YUV420P10LE); break;
     default: return hipErrorInvalidValue;
     }
 #undef UVA_PIX_LAUNCH
+    return hipGetLastError();
+}
+
+dim3 flat_grid(size_t n) { return dim3((unsigned)((n + 256 * WN - 1) / (256 * WN))); }
+}  // namespace
+
+hipError_t launch_pix_from_bgr(hipStream_t stream, int fmt, int colour, const uint8_t* bgr, void* dst, int h, int w)
+{
+    return from_bgr<uint8_t>(stream, fmt, colour, bgr, dst, h, w);
+}
+
+hipError_t launch_pix_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint8_t* bgr, int h, int w)
+{
+    return to_bgr<uint8_t>(stream, fmt, colour, src, bgr, h, w);
+}
+
+hipError_t launch_pix16_from_bgr(hipStream_t stream, int fmt, int colour, const uint16_t* bgr, void* dst, int h, int w)
+{
+    if (fmt != PIX_BGR24) return from_bgr<uint16_t>(stream, fmt, colour, bgr, dst, h, w);
+    if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK)) return hipErrorInvalidValue;
+    const size_t n = (size_t)3 * w * h;
+    if (flat_grid(n).x == 0 || n / (256 * WN) >= 0x7fffffffu) return hipErrorInvalidValue;
+    if ((((uintptr_t)bgr % 16) | ((uintptr_t)dst % 8)) == 0) hipLaunchKernelGGL((pix_narrow<true>), flat_grid(n), dim3(256), 0, stream, bgr, (uint8_t*)dst, n);
+    else hipLaunchKernelGGL((pix_narrow<false>), flat_grid(n), dim3(256), 0, stream, bgr, (uint8_t*)dst, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_pix16_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint16_t* bgr, int h, int w)
+{
+    if (fmt != PIX_BGR24) return to_bgr<uint16_t>(stream, fmt, colour, src, bgr, h, w);
+    if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK)) return hipErrorInvalidValue;
+    const size_t n = (size_t)3 * w * h;
+    if (flat_grid(n).x == 0 || n / (256 * WN) >= 0x7fffffffu) return hipErrorInvalidValue;
+    if ((((uintptr_t)src % 8) | ((uintptr_t)bgr % 16)) == 0) hipLaunchKernelGGL((pix_widen<true>), flat_grid(n), dim3(256), 0, stream, (const uint8_t*)src, bgr, n);
+    else hipLaunchKernelGGL((pix_widen<false>), flat_grid(n), dim3(256), 0, stream, (const uint8_t*)src, bgr, n);
     return hipGetLastError();
 }
 

@@ -116,19 +116,24 @@ def png_encode_u8(img_bgr, gpu=0, workspace=None):
 
 
 # ---- raw-video pixel formats (include/uva.h UVA_PIX_*) -----------------------------------------
-PIX_FORMATS = {"bgr24": 0, "yuv420p": 1, "nv12": 2, "p010le": 3}     # ffmpeg's -pix_fmt names
+PIX_FORMATS = {"bgr24": 0, "yuv420p": 1, "nv12": 2, "p010le": 3}     # ffmpeg's -pix_fmt names (the first four)
+# every format the calls take: + yuv420p10le (both routes) and bgr48le (u16 BGR: the 16-bit route's own, bit_depth=16).  Kept
+# apart so that PIX_FORMATS still lists exactly the formats of the first pixel-format release
+PIX_FORMATS_ALL = dict(PIX_FORMATS, yuv420p10le=5, bgr48le=6)      # (code 4 is not assigned)
+PIX16_ONLY = ("bgr48le",)
 COLORSPACES = {"bt601": 0, "bt709": 1}                              # ffmpeg's -colorspace names
 COLOR_RANGES = {"tv": 0, "pc": 2}                                   # ffmpeg's -color_range names (limited, full)
 
 
 def pix_frame_bytes(fmt, h, w):
     """bytes of one dense h x w rawvideo frame of `fmt` (chroma planes ceil(w/2) x ceil(h/2); include/uva.h uva_pix_frame_bytes)"""
-    if fmt not in PIX_FORMATS:
-        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS)))
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
     if h <= 0 or w <= 0:
         raise ValueError("frame size must be positive")
     c = 2 * ((w + 1) // 2) * ((h + 1) // 2)
-    return {"bgr24": 3 * w * h, "yuv420p": w * h + c, "nv12": w * h + c, "p010le": 2 * (w * h + c)}[fmt]
+    return {"bgr24": 3 * w * h, "yuv420p": w * h + c, "nv12": w * h + c, "p010le": 2 * (w * h + c), "yuv420p10le": 2 * (w * h + c),
+            "bgr48le": 6 * w * h}[fmt]
 
 
 def colour_word(colour="bt601", color_range="tv"):
@@ -141,9 +146,11 @@ def colour_word(colour="bt601", color_range="tv"):
 
 
 def pix_empty(fmt, h, w, alloc=None):
-    """a buffer for one h x w frame of `fmt`: u8 [h][w][3] for bgr24, a flat u8 array of pix_frame_bytes otherwise.
-    `alloc(shape)` -> u8 array (default np.empty; pinned_empty for page-locked memory)"""
+    """a buffer for one h x w frame of `fmt`: u8 [h][w][3] for bgr24, u16 [h][w][3] for bgr48le, a flat u8 array of
+    pix_frame_bytes otherwise.  `alloc(shape)` -> u8 array (default np.empty; pinned_empty for page-locked memory)"""
     alloc = alloc or (lambda shape: np.empty(shape, np.uint8))
+    if fmt == "bgr48le":
+        return alloc((h, w, 6)).view(np.uint16)
     return alloc((h, w, 3)) if fmt == "bgr24" else alloc((pix_frame_bytes(fmt, h, w),))
 
 
@@ -154,17 +161,29 @@ def _pix_frame(buf, fmt, h, w, what):
     return a
 
 
-def convert_pix(buf, h, w, in_fmt, out_fmt, colour="bt601", color_range="tv", out=None, gpu=0):
+def _bit_depth(bit_depth, fmts):
+    if bit_depth not in (8, 16):
+        raise ValueError("bit_depth must be 8 or 16")
+    for f in fmts:
+        if f not in PIX_FORMATS_ALL:
+            raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(PIX_FORMATS_ALL)))
+        if bit_depth == 8 and f in PIX16_ONLY:
+            raise ValueError("%s is a 16-bit format: it needs bit_depth=16" % f)
+
+
+def convert_pix(buf, h, w, in_fmt, out_fmt, colour="bt601", color_range="tv", out=None, gpu=0, bit_depth=8):
     """One dense h x w frame of in_fmt -> out_fmt on HIP device `gpu`, host to host, synchronous (include/uva.h
-    uva_pix_convert).  Returns `out` (u8 [h][w][3] for bgr24, flat u8 otherwise; allocated when None)."""
+    uva_pix_convert; bit_depth=16: uva_pix_convert16, through u16 BGR).  Returns `out` (pix_empty's
+    array for out_fmt; allocated when None)."""
+    _bit_depth(bit_depth, (in_fmt, out_fmt))
     cw = colour_word(colour, color_range)
     src = _pix_frame(buf, in_fmt, h, w, "input")
     if out is None:
         out = pix_empty(out_fmt, h, w)
     if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(out_fmt, h, w):
         raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, h, w))
-    _lib.check(_lib.load().uva_pix_convert(int(gpu), src.ctypes.data, PIX_FORMATS[in_fmt], out.ctypes.data, PIX_FORMATS[out_fmt],
-                                           h, w, cw))
+    fn = _lib.load().uva_pix_convert16 if bit_depth == 16 else _lib.load().uva_pix_convert
+    _lib.check(fn(int(gpu), src.ctypes.data, PIX_FORMATS_ALL[in_fmt], out.ctypes.data, PIX_FORMATS_ALL[out_fmt], h, w, cw))
     return out
 
 
@@ -336,6 +355,21 @@ class Net:
                                               w * s * 3, int(tile_size), int(border)))
         return out
 
+    def process_u16(self, img_bgr, tile_size=0, border=0):
+        """process_u8 on 16-bit samples (include/uva.h uva_net_process_u16): u16 HWC BGR (unorm16) ->
+        u16 HWC BGR.  The 2x and 4x Compact nets only."""
+        img = np.ascontiguousarray(img_bgr, dtype=np.uint16)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("frame must be u16 [h][w][3]")
+        s = self.scale
+        if s <= 0:
+            raise _lib.UvaError("net has no graph: load_param/load_model failed or were not called")
+        h, w, _ = img.shape
+        out = np.empty((h * s, w * s, 3), np.uint16)
+        _lib.check(self._L.uva_net_process_u16(self._h, img.ctypes.data, h, w, w * 6, out.ctypes.data,
+                                               w * s * 6, int(tile_size), int(border)))
+        return out
+
     def submit_u8(self, img_bgr, out=None, tile_size=0, border=0):
         """Pipelined process_u8 (include/uva.h uva_net_submit_u8): returns a Ticket at once; up to 3
         frames may be in flight and their H2D copy, kernels and D2H copy overlap.  `out`: optional
@@ -357,14 +391,14 @@ class Net:
             raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
         return Ticket(t, img, out)
 
-    def submit_pix(self, buf, h, w, in_fmt, out=None, out_fmt="bgr24", colour="bt601", color_range="tv", tile_size=0, border=0):
+    def submit_pix(self, buf, h, w, in_fmt, out=None, out_fmt="bgr24", colour="bt601", color_range="tv", tile_size=0, border=0,
+                   bit_depth=8):
         """submit_u8 with a rawvideo pixel format on either end (include/uva.h uva_net_submit_pix): `buf` holds one dense
         h x w frame of in_fmt, the result is one dense (h*s) x (w*s) frame of out_fmt; both conversions run on the GPU around
         the net.  `out`: optional preallocated result buffer of pix_frame_bytes(out_fmt, h*s, w*s) bytes (pix_empty; pinned
-        memory avoids the staging copy).  Returns a Ticket that collect_u8 takes."""
-        for f in (in_fmt, out_fmt):
-            if f not in PIX_FORMATS:
-                raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(PIX_FORMATS)))
+        memory avoids the staging copy).  Returns a Ticket that collect_u8 takes.  bit_depth=16: the 16-bit route
+        (uva_net_submit_pix16): the frame reaches the net as u16 BGR and leaves it as u16 BGR, no 8-bit hop."""
+        _bit_depth(bit_depth, (in_fmt, out_fmt))
         cw = colour_word(colour, color_range)
         s = self.scale
         if s <= 0:
@@ -374,8 +408,8 @@ class Net:
             out = pix_empty(out_fmt, h * s, w * s)
         if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(out_fmt, h * s, w * s):
             raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, h * s, w * s))
-        t = self._L.uva_net_submit_pix(self._h, src.ctypes.data, PIX_FORMATS[in_fmt], h, w, out.ctypes.data, PIX_FORMATS[out_fmt], cw,
-                                       int(tile_size), int(border))
+        fn = self._L.uva_net_submit_pix16 if bit_depth == 16 else self._L.uva_net_submit_pix
+        t = fn(self._h, src.ctypes.data, PIX_FORMATS_ALL[in_fmt], h, w, out.ctypes.data, PIX_FORMATS_ALL[out_fmt], cw, int(tile_size), int(border))
         if t < 0:
             raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
         return Ticket(t, src, out)
@@ -383,8 +417,8 @@ class Net:
     def convert_pix_device(self, d_in, h, w, in_fmt, d_out, out_fmt, colour="bt601", color_range="tv", after=None):
         """A conversion of a frame in HBM queued IN FRONT of this net (include/uva.h uva_pix_convert_device), like
         denoise_u8_device: `after` (a net, or None) comes first, this net's next work waits for the frame."""
-        _lib.check(self._L.uva_pix_convert_device(self.device_index, ctypes.c_void_p(d_in), PIX_FORMATS[in_fmt], ctypes.c_void_p(d_out),
-                                                  PIX_FORMATS[out_fmt], h, w, colour_word(colour, color_range),
+        _lib.check(self._L.uva_pix_convert_device(self.device_index, ctypes.c_void_p(d_in), PIX_FORMATS_ALL[in_fmt], ctypes.c_void_p(d_out),
+                                                  PIX_FORMATS_ALL[out_fmt], h, w, colour_word(colour, color_range),
                                                   after._h if after is not None else None, self._h))
 
     def collect_u8(self, ticket):

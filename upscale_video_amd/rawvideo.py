@@ -16,6 +16,9 @@ p010le; --colorspace bt601|bt709, --color-range tv|pc, default bt601 / tv: DESIG
       | python -m upscale_video_amd.rawvideo -W 1920 -H 1080 -s 2 --in-pix-fmt yuv420p --out-pix-fmt p010le \\
       | ffmpeg -f rawvideo -pix_fmt p010le -s 3840x2160 -r 24 -i - -c:v libx265 out.mkv
 
+--bit-depth 16 runs the 2x / 4x net on 16-bit samples so that 10-bit frames (p010le, yuv420p10le) keep their depth
+(no -m option with it).
+
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
 conversions run on the net's stream around its kernels); nets in between pass u8 BGR.  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
@@ -61,14 +64,24 @@ PIPE_DEPTH = 3   # include/uva.h: at most 3 frames in flight per net
 
 
 class PixFormats:
-    """the raw-video formats of a stream's two ends and the colour arithmetic between them (ncnn.PIX_FORMATS etc.)"""
+    """the raw-video formats of a stream's two ends and the colour arithmetic between them (ncnn.PIX_FORMATS_ALL etc.)"""
 
-    def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv"):
+    def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv", bit_depth=8):
         for f in (in_fmt, out_fmt):
-            if f not in ncnn.PIX_FORMATS:
-                raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(ncnn.PIX_FORMATS)))
+            if f not in ncnn.PIX_FORMATS_ALL:
+                raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(ncnn.PIX_FORMATS_ALL)))
+        if bit_depth not in (8, 16):
+            raise ValueError("bit depth must be 8 or 16")
+        for f in (in_fmt, out_fmt):
+            if bit_depth == 8 and f in ncnn.PIX16_ONLY:
+                raise ValueError("%s is a 16-bit format: it needs --bit-depth 16" % f)
         ncnn.colour_word(colour, color_range)              # (checks both names)
         self.in_fmt, self.out_fmt, self.colour, self.color_range = in_fmt, out_fmt, colour, color_range
+        self.bit_depth = bit_depth     # 16: the net runs on u16 BGR (DESIGN.md section 7.4), no 8-bit hop at either end
+
+    def depth_kw(self):
+        """the keyword the 16-bit calls take (none at 8 bits: those calls are the first pixel-format release's)"""
+        return {"bit_depth": 16} if self.bit_depth == 16 else {}
 
     def frame_bytes(self, h, w, out=False):
         return ncnn.pix_frame_bytes(self.out_fmt if out else self.in_fmt, h, w)
@@ -123,12 +136,12 @@ class Stage:
         out = self.outs[self.n % len(self.outs)]
         self.n += 1
         border = TILE_BORDER if self.tile else 0
-        if self.in_fmt == self.out_fmt == "bgr24":
+        if self.in_fmt == self.out_fmt == "bgr24" and self.pix.bit_depth == 8:
             self.inflight.append(self.net.submit_u8(frame, out=out, tile_size=self.tile, border=border))
         else:
             self.inflight.append(self.net.submit_pix(frame, self.h, self.w, self.in_fmt, out=out, out_fmt=self.out_fmt,
                                                      colour=self.pix.colour, color_range=self.pix.color_range,
-                                                     tile_size=self.tile, border=border))
+                                                     tile_size=self.tile, border=border, **self.pix.depth_kw()))
 
     def collect(self):
         return self.net.collect_u8(self.inflight.pop(0))
@@ -601,7 +614,8 @@ class PipeSink:
 
 def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
     """`-s 1` without `-m a`: the reference renames the frames, nothing is computed (:924-929).  Formats that differ at the two
-    ends (pix): every frame is converted once on HIP device `gpu` (include/uva.h uva_pix_convert)."""
+    ends (pix): every frame is converted once on HIP device `gpu` (include/uva.h uva_pix_convert; with pix.bit_depth 16
+    uva_pix_convert16, through u16 BGR)."""
     pix = pix or BGR
     buf = bytearray(pix.frame_bytes(h, w))
     res = ncnn.pix_empty(pix.out_fmt, h, w) if pix.in_fmt != pix.out_fmt else None
@@ -612,7 +626,8 @@ def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
         if res is None:
             fout.write(buf)
         else:
-            ncnn.convert_pix(np.frombuffer(buf, np.uint8), h, w, pix.in_fmt, pix.out_fmt, pix.colour, pix.color_range, out=res, gpu=gpu)
+            ncnn.convert_pix(np.frombuffer(buf, np.uint8), h, w, pix.in_fmt, pix.out_fmt, pix.colour, pix.color_range, out=res, gpu=gpu,
+                             **pix.depth_kw())
             fout.write(memoryview(res).cast("B"))
         n += 1
     fout.flush()
@@ -639,19 +654,25 @@ def main(argv=None):
     ap.add_argument("--round-robin", action="store_true",
                     help="file to file with several -g entries: deal the frames out one by one through ONE reader and ONE writer "
                          "(what pipes get) instead of one contiguous segment of frames, reader and writer per entry")
-    ap.add_argument("--in-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS),
+    ap.add_argument("--in-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS_ALL),
                     help="ffmpeg -pix_fmt of the input frames (default bgr24); converted to BGR on the GPU")
-    ap.add_argument("--out-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS),
+    ap.add_argument("--out-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS_ALL),
                     help="ffmpeg -pix_fmt of the output frames (default bgr24); converted from the net's BGR on the GPU")
     ap.add_argument("--colorspace", default="bt601", choices=list(ncnn.COLORSPACES),
                     help="Y'CbCr matrix of yuv420p / nv12 / p010le frames (default bt601: what ffmpeg applies to the reference's "
                          "untagged PNGs)")
     ap.add_argument("--color-range", default="tv", choices=list(ncnn.COLOR_RANGES), help="tv = limited (default), pc = full")
+    ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
+                    help="16: the 2x / 4x net runs on 16-bit samples, so 10-bit frames (p010le, yuv420p10le) keep their depth "
+                         "(default 8); takes no -m option")
     ap.add_argument("--model-path", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models"))
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
-    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range)
+    for f in (a.in_pix_fmt, a.out_pix_fmt):
+        if f in ncnn.PIX16_ONLY and a.bit_depth != 16:
+            ap.error("%s is a 16-bit format: it needs --bit-depth 16" % f)
+    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range, a.bit_depth)
     # upscale_video.py -m: a (anime pass), n=K (film-grain denoise, K = 1..30, :782-789), r (the x_Valar_v1 model instead of
     # x_Compact_Pretrain, :913-916); the reference runs them in the order n, a, upscale (:880-920) whatever the order given
     models = [m for m in a.models.split(",") if m]
@@ -666,6 +687,8 @@ def main(argv=None):
                 ap.error("-m n=K: K must be between 1 and 30")
         elif m not in ("a", "r"):
             ap.error("unknown model option %r (a, n=K, r)" % m)
+    if models and a.bit_depth == 16:
+        ap.error("--bit-depth 16 takes the 2x and 4x Compact nets only: -m a, -m n=K and -m r run at 8 bits (-m %s)" % a.models)
     final_stem = MODEL_FILES[a.scale]
     if "r" in models:
         if a.scale != 4:
