@@ -176,7 +176,7 @@ int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out
 /* uva_net_process_u8_device's analogue: d_in u16 [h][w][3], d_out u16 [h*s][w*s][3], strides in bytes (even). */
 int uva_net_process_u16_device(uva_net* net, const void* d_in, int h, int w, size_t in_stride, void* d_out, size_t out_stride,
                                int tile_size, int border);
-/* Host to host, synchronous (tests, Python). */
+/* Host to host, synchronous (tests, Python); strides and frame addresses even, as above. */
 int uva_net_process_u16(uva_net* net, const uint16_t* in, int h, int w, size_t in_stride, uint16_t* out, size_t out_stride,
                         int tile_size, int border);
 /* uva_net_submit_pix's arguments and rules (collected by uva_net_collect_u8), converting to and from u16 BGR instead of u8:

@@ -5,7 +5,8 @@
 
     check_u8("tiled 2x 70x75 t32", got, want, vs="fp32 oracle", max_lsb=2, min_psnr=50)
 
-records max |diff| (LSB), PSNR (dB) and the share of differing samples, THEN asserts the bars.  conftest.py writes the
+records max |diff| (LSB), PSNR (dB) and the share of differing samples, THEN asserts the bars (check_u16: u16 frames, scored
+in codes; check_f32: float blobs).  conftest.py writes the
 records to gpurun_out/parity_report.json at the end of the session and prints one line per record in pytest's terminal
 summary (so that the driver's `-q` log shows them); tools/parity_slack.py turns a report into tests/golden/parity_slack.json,
 the committed measurements the product-mode bars are derived from (bar = measured maximum + margin, per model and route).
@@ -118,6 +119,60 @@ def check_u8(name, got, want, vs, max_lsb, min_psnr=None, max_share=None, model=
     return worst, p, share
 
 
+U16_PRODUCT = "product-mode oracle, u16 codes"    # the vs of the 16-bit route's product-mode records (tools/parity_slack.py)
+U16_MAX = 65535
+
+
+def structure_codes(d):
+    """structure_u8 for |diff| in codes (u16 frames): its standard error assumes a sample's variance equals its mean, true of
+    u8's 0/1 differences; differences of many codes have a variance of about their mean squared, so |diff| is rescaled by
+    mean / variance first (a rescaling the ratios ignore)"""
+    if d.ndim != 3 or d.shape[0] < STRUCTURE_MIN or d.shape[1] < STRUCTURE_MIN:
+        return None
+    v = float(d.var())
+    return structure_u8(d * (float(d.mean()) / v) if v > 0 else d)
+
+
+def score_u16(got, want):
+    """u16 frames -> their distance in codes (1 / 65535): max |diff|, RMS, mean signed bias (got - want), share of samples
+    that differ, and the share of samples off the clamp ends (0, 65535) that are multiples of 257 -- every one on a route
+    that carries 8 bits somewhere (widen(narrow(y)) = 257 rint(y / 257)), about 1 / 257 on a route that keeps 16"""
+    d = got.astype(np.int32) - want.astype(np.int32)
+    inner = got[(got != 0) & (got != U16_MAX)]
+    return {"max_codes": int(np.abs(d).max()) if d.size else 0,
+            "rms_codes": float(np.sqrt((d.astype(np.float64) ** 2).mean())) if d.size else 0.0,
+            "bias_codes": float(d.mean()) if d.size else 0.0,
+            "differ_share": float((d != 0).mean()) if d.size else 0.0,
+            "x257_share": float((inner % 257 == 0).mean()) if inner.size else 0.0}
+
+
+def check_u16(name, got, want, vs, max_codes=None, max_rms=None, max_bias=None, max_x257=None, model=None, route=None,
+              structure=True, counterfactual=False):
+    """u16 frames, scored in codes (score_u16, and on frames of at least 48 x 48 structure_codes): record, then hold to the
+    bars given (max |diff|, RMS and |mean signed bias| in codes, the share of unclamped samples that are multiples of 257).
+    counterfactual=True: `got` is what a route that carries 8 bits would give (widen(narrow(y))).  It is recorded with the
+    bars, without the structure statistic (quantising smooth content is structured by nature), and must FAIL each depth bar
+    given -- RMS and multiples of 257 -- which shows that those bars tell such a route from a 16-bit one."""
+    assert got.shape == want.shape and got.dtype == np.uint16 and want.dtype == np.uint16, (name, got.shape, want.shape, got.dtype, want.dtype)
+    sc = score_u16(got, want)
+    st = structure_codes(np.abs(got.astype(np.int32) - want.astype(np.int32))) if structure and not counterfactual else None
+    record(name, kind="u16", vs=vs, model=model, route=route, samples=int(got.size), structure=st,
+           bar_max_codes=max_codes, bar_rms_codes=max_rms, bar_bias_codes=max_bias, bar_x257_share=max_x257,
+           bar_structure_z=(STRUCTURE_Z if st else None), counterfactual=counterfactual, **sc)
+    bars = (("max |diff| codes", "max_codes", max_codes), ("RMS codes", "rms_codes", max_rms), ("|bias| codes", "bias_codes", max_bias),
+            ("x257 share", "x257_share", max_x257))
+    fails = [(what, sc[key], bar) for what, key, bar in bars if bar is not None and abs(sc[key]) > bar]
+    if counterfactual:
+        depth = [(what, sc[key], bar) for what, key, bar in bars if key in ("rms_codes", "x257_share") and bar is not None]
+        assert depth and all(abs(v) > bar for _, v, bar in depth), (name, vs, "the 8-bit counterfactual passes a depth bar", depth, sc)
+        return sc
+    if st:
+        assert st["col_z"] <= STRUCTURE_Z, (name, vs, "structured error: column", st["col_at"], "stands", st["col_z"], "s.e. above its neighbours", st)
+        assert st["row_z"] <= STRUCTURE_Z, (name, vs, "structured error: row", st["row_at"], "stands", st["row_z"], "s.e. above its neighbours", st)
+    assert not fails, (name, vs, fails, sc)
+    return sc
+
+
 def check_f32(name, got, want, vs, max_abs, model=None, route=None, what="f32_abs", scale=None):
     """float blobs: record max |diff| (and, with `scale`, relative to the blob's range), then hold to max_abs"""
     err = float(np.abs(got - want).max()) if got.size else 0.0
@@ -149,6 +204,16 @@ def summary_lines():
                 r["name"][:58], r["vs"][:34], r["max_lsb"], r["bar_max_lsb"], r["psnr_db"], r["bar_min_psnr_db"],
                 100 * r["differ_share"], ("%.1f %%" % (100 * r["bar_max_share"])) if r["bar_max_share"] is not None else "-",
                 ("  structure z col %.1f row %.1f (bar %.0f)" % (st["col_z"], st["row_z"], r["bar_structure_z"])) if st else ""))
+        elif r.get("kind") == "u16":
+            st = r.get("structure")
+            bar = lambda k, f, m=1: ("bar " + f % (m * r[k])) if r.get(k) is not None else "bar -"   # noqa: E731
+            yield ("parity %-58s vs %-34s max %d codes (%s)  RMS %.2f codes (%s)  bias %+.2f (%s)  differ %.1f %%  "
+                   "x257 %.2f %% (%s)%s%s" % (
+                       r["name"][:58], r["vs"][:34], r["max_codes"], bar("bar_max_codes", "%.0f"), r["rms_codes"],
+                       bar("bar_rms_codes", "%.2f"), r["bias_codes"], bar("bar_bias_codes", "%.2f"), 100 * r["differ_share"],
+                       100 * r["x257_share"], bar("bar_x257_share", "%.2f %%", 100),
+                       ("  structure z col %.1f row %.1f (bar %.0f)" % (st["col_z"], st["row_z"], r["bar_structure_z"])) if st else "",
+                       "  8-bit COUNTERFACTUAL (fails its depth bars)" if r.get("counterfactual") else ""))
         else:
             yield ("parity %-58s vs %-34s max |err| %.3e (bar %.3e)%s" % (
                 r["name"][:58], r["vs"][:34], r["max_abs_err"], r["bar_max_abs"],

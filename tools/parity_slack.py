@@ -6,8 +6,15 @@ route, as MEASURED MAXIMUM + MARGIN instead of a round number (VERDICT r4 item 4
     u8_differ_share  share of u8 samples that differ (by one level)          margin: one point (0.01)
     layer_rel        per-layer activations, max |err| / the layer's range    margin: 5e-4
     f32_abs          pre-quantisation f32 output, max |err|                  margin: 5e-4
+    u16/rms_codes    the 16-bit route's u16 output, RMS in codes             margin: MARGIN["rms_codes"]
+    u16/max_codes    the 16-bit route's u16 output, max |diff| in codes      margin: MARGIN["max_codes"]
+
+The u16 bars come from the records whose vs is U16_VS (tests/parity_report.py U16_PRODUCT; counterfactual records left out),
+and are capped: RMS at half an 8-bit hop's, max |diff| at the float route's f32_abs bar of the same model in codes (the bar
+the route borrowed before it had its own).
 
     python tools/parity_slack.py [report.json ...]      several reports (boxes, sweeps): the maximum over all of them
+    python tools/parity_slack.py --out PATH [...]       write PATH instead of tests/golden/parity_slack.json
 
 The fp32 bars (<= 2 LSB, >= 50 dB; whole 1080p frames >= 60 dB) are independent of the kernel and stay as they are."""
 import json
@@ -15,20 +22,30 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MARGIN = {"u8_differ_share": 0.01, "layer_rel": 5e-4, "f32_abs": 5e-4}
-# the round numbers of round 4 the derived bars replaced (tests/test_gpu_parity.py's fallbacks): never exceeded
-FIXED = {"u8_differ_share": {"1x": 5e-2, "wino": 8e-2}, "layer_rel": {"1x": 2e-3, "wino": 3e-3}, "f32_abs": {"1x": 3e-3, "wino": 4e-3}}
+U16_VS = "product-mode oracle, u16 codes"
+MARGIN = {"u8_differ_share": 0.01, "layer_rel": 5e-4, "f32_abs": 5e-4, "rms_codes": 1.0, "max_codes": 33.0}
+# the round numbers of round 4 the derived bars replaced (tests/test_gpu_parity.py's fallbacks): never exceeded.  u16: half
+# the RMS of an 8-bit hop on content spread over the codes (257 / sqrt(12) / 2); max |diff|: the float route's round number
+# in codes, unless that model's f32_abs bar is there to cap it
+FIXED = {"u8_differ_share": {"1x": 5e-2, "wino": 8e-2}, "layer_rel": {"1x": 2e-3, "wino": 3e-3}, "f32_abs": {"1x": 3e-3, "wino": 4e-3},
+         "rms_codes": {"1x": 37.0, "wino": 37.0}, "max_codes": {"1x": 3e-3 * 65535, "wino": 4e-3 * 65535}}
 FP32_PSNR_MARGIN, FP32_SHARE_MARGIN = 2.0, 0.015
 
 
-def main(paths):
+def main(paths, dst=None):
     paths = paths or [os.path.join(ROOT, "gpurun_out", "parity_report.json")]
     worst, count, fp32 = {}, {}, {}
     for p in paths:
         for r in json.load(open(p))["records"]:
             if not r.get("model") or not r.get("route"):
                 continue
-            if "product rounding mode" in r["vs"]:
+            if r["kind"] == "u16":
+                if r["vs"] == U16_VS and not r.get("counterfactual"):
+                    for what in ("rms_codes", "max_codes"):
+                        key = f"{r['model']}/{r['route']}/{what}"
+                        worst[key] = max(worst.get(key, 0.0), r[what])
+                        count[key] = count.get(key, 0) + 1
+            elif "product rounding mode" in r["vs"]:
                 if r["kind"] == "u8":
                     key, val = f"{r['model']}/{r['route']}/u8_differ_share", r["differ_share"]
                 elif r.get("what") == "layer_rel":
@@ -45,9 +62,11 @@ def main(paths):
                 e["min_psnr_db"] = round(min(e["min_psnr_db"], r["psnr_db"]), 2)
                 e["max_differ_share"] = round(max(e["max_differ_share"], r["differ_share"]), 5)
     bars = {}
-    for key in sorted(worst):
+    for key in sorted(worst, key=lambda k: k.endswith("_codes")):             # the u16 caps read the float bars
         what = key.rsplit("/", 1)[1]
         cap = FIXED[what]["1x" if key.startswith("1x/") else "wino"]         # a recalibration can only tighten
+        if what == "max_codes" and key.split("/")[0] + "/float/f32_abs" in bars:
+            cap = round(65535 * bars[key.split("/")[0] + "/float/f32_abs"]["bar"], 1)
         bars[key] = {"measured_max": round(worst[key], 6), "margin": MARGIN[what], "bar": round(min(worst[key] + MARGIN[what], cap), 6),
                      "cap": cap, "comparisons": count[key]}
     # the kernel-independent bars (GPU against the fp32 oracle), per model and route: measured worst case -/+ a margin, and never
@@ -58,12 +77,13 @@ def main(paths):
         fp32_bars[k] = {"max_lsb": min(3 if chain else 2, e["max_lsb"] + 1),
                         "min_psnr_db": round(max(48.0 if chain else 50.0, e["min_psnr_db"] - FP32_PSNR_MARGIN), 2),
                         "max_differ_share": round(e["max_differ_share"] + FP32_SHARE_MARGIN, 5)}
+    bars = dict(sorted(bars.items()))
     out = {"about": "product-mode parity bars = measured maximum + margin (tools/parity_slack.py); fp32_bars = the kernel-independent "
                     "bars against the fp32 oracle, measured worst case (fp32_measured) -/+ a margin, capped at the round numbers "
                     "they replace (<= 2 LSB, >= 50 dB)",
            "sources": [os.path.relpath(os.path.abspath(p), ROOT) for p in paths], "bars": bars, "fp32_measured": fp32,
            "fp32_bars": fp32_bars, "fp32_margins": {"psnr_db": FP32_PSNR_MARGIN, "differ_share": FP32_SHARE_MARGIN}}
-    dst = os.path.join(ROOT, "tests", "golden", "parity_slack.json")
+    dst = dst or os.path.join(ROOT, "tests", "golden", "parity_slack.json")
     with open(dst, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
     print("wrote", dst)
@@ -71,7 +91,14 @@ def main(paths):
         print("  fp32 %-29s <= %d LSB, >= %.2f dB, differ <= %.3f" % (k, v["max_lsb"], v["min_psnr_db"], v["max_differ_share"]))
     for k, v in bars.items():
         print("  %-34s measured %.5f + %.4f -> bar %.5f (%d comparisons)" % (k, v["measured_max"], v["margin"], v["bar"], v["comparisons"]))
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    args = sys.argv[1:]
+    out_path = None
+    if "--out" in args:
+        i = args.index("--out")
+        out_path = args[i + 1]
+        del args[i:i + 2]
+    main(args, out_path)

@@ -3111,6 +3111,9 @@ int uva_net_process_u16(uva_net* n, const uint16_t* in, int h, int w, size_t in_
 {
     if (check_dims(n, h, w)) return 1;
     if (!in || !out) return fail("null frame pointer");
+    // as uva_net_process_u16_device: the staging copies would take any stride, but a row of u16 samples at an odd address is
+    // no uint16_t array
+    if ((((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 1) != 0) return fail("16-bit frames need 2-byte aligned rows");
     if (ensure_device(n) || check_u16_net(n)) return 1;
     const long long t = submit_u8(n, (const uint8_t*)in, h, w, in_stride, (uint8_t*)out, out_stride, tile_size, border, nullptr, 0,
                                   PIX_BGR48LE, PIX_BGR48LE, 0, true);
