@@ -44,7 +44,9 @@ extern "C" {
                                15 + pixel formats: + uva_pix_frame_bytes, uva_net_submit_pix, uva_pix_convert, uva_pix_convert_device
                                    (additive: every entry point of 15 is unchanged)
                                15 + 16-bit route: + UVA_PIX_YUV420P10LE, UVA_PIX_BGR48LE, uva_net_process_u16_device,
-                                   uva_net_process_u16, uva_net_submit_pix16, uva_pix_convert16 (additive as well) */
+                                   uva_net_process_u16, uva_net_submit_pix16, uva_pix_convert16 (additive as well)
+                               15 + chroma siting: + UVA_CHROMA_BILINEAR, UVA_CHROMA_CENTER, UVA_CHROMA_TOPLEFT in the colour word of
+                                   every pixel-format entry (additive: colour words 0-3 mean what they meant) */
 
 typedef struct uva_net uva_net;
 
@@ -138,7 +140,12 @@ void uva_host_free(void* p);
  * colour = UVA_CSP_BT601 or UVA_CSP_BT709, | UVA_RANGE_FULL for full ("pc") range instead of limited ("tv": Y 16-235,
  * C 16-240, x4 at 10 bits).  BGR -> Y'CbCr: fixed-point textbook formulas, chroma of a 2x2 block from the block's sums;
  * Y'CbCr -> BGR: chroma replicated over its 2x2 block.  The reference's frames are untagged rgb24 PNGs, which ffmpeg merges
- * as BT.601 limited range (upscale/upscale_processing.py:604-640): colour 0. */
+ * as BT.601 limited range (upscale/upscale_processing.py:604-640): colour 0.
+ * | UVA_CHROMA_BILINEAR: both directions interpolate chroma for where its samples sit instead --
+ * Y'CbCr -> BGR bilinear, BGR -> Y'CbCr the matching [1 2 1] / [1 1] filters, taps beyond the plane's edge replicated.  The
+ * siting is ffmpeg's chroma_sample_location: left (neither siting bit: H.264 / HEVC video), | UVA_CHROMA_CENTER (JPEG,
+ * MPEG-1) or | UVA_CHROMA_TOPLEFT (UHD BT.2020 material).  A siting bit without UVA_CHROMA_BILINEAR, both siting bits, or any
+ * other bit is refused by every entry that takes a colour word, with uva_last_error set. */
 #define UVA_PIX_BGR24 0
 #define UVA_PIX_YUV420P 1
 #define UVA_PIX_NV12 2
@@ -148,6 +155,9 @@ void uva_host_free(void* p);
 #define UVA_CSP_BT601 0
 #define UVA_CSP_BT709 1
 #define UVA_RANGE_FULL 2
+#define UVA_CHROMA_BILINEAR 4
+#define UVA_CHROMA_CENTER 8
+#define UVA_CHROMA_TOPLEFT 16
 /* Bytes of one dense h x w frame of `fmt`; 0 for an unknown format or a size <= 0. */
 size_t uva_pix_frame_bytes(int fmt, int h, int w);
 /* uva_net_submit_u8 with a pixel format on either end, collected by uva_net_collect_u8: `in` holds one dense frame of

@@ -5,7 +5,9 @@
                     conversion kernels' times.  Prints each route's wall-clock rate.
     pipe [frames]   profiler off: python -m upscale_video_amd.rawvideo pipe -> pipe, p010le both ways, --bit-depth 8 and 16
                     (frames held in /dev/shm; rate = (frames - 1) / (wall - wall of a 1-frame run)).
+    --chroma-filter bilinear [--chroma-loc left|center|topleft]: either run with the interpolating chroma kernels (section 7.5).
 """
+import argparse
 import os
 import subprocess
 import sys
@@ -17,6 +19,9 @@ from upscale_video_amd import ncnn                      # noqa: E402
 from upscale_video_amd.synth import synthetic_frame      # noqa: E402
 
 h, w = 1080, 1920
+
+
+CHROMA = {}            # submit_pix's chroma keywords (main fills them in)
 
 
 def probe(n):
@@ -39,7 +44,7 @@ def probe(n):
             if len(inflight) == 3:
                 net.collect_u8(inflight.pop(0))
             inflight.append(net.submit_pix(frames[i % 4], h, w, "p010le", out=outs[i % 3], out_fmt="p010le", tile_size=960, border=10,
-                                           bit_depth=bd))
+                                           bit_depth=bd, **CHROMA))
         while inflight:
             net.collect_u8(inflight.pop(0))
         if k >= 40:                                   # (the first block of each route warms up)
@@ -54,6 +59,8 @@ def probe(n):
 def pipe(n):
     base = [sys.executable, "-m", "upscale_video_amd.rawvideo", "-W", str(w), "-H", str(h), "-s", "2",
             "--in-pix-fmt", "p010le", "--out-pix-fmt", "p010le"]
+    for k, v in CHROMA.items():
+        base += ["--" + k.replace("_", "-"), v]
     src = "/dev/shm/uva_bd16_in.p010"
     packed = [ncnn.convert_pix(synthetic_frame(h, w, seed=i), h, w, "bgr24", "p010le").tobytes() for i in range(4)]
     with open(src, "wb") as o:
@@ -76,6 +83,13 @@ def pipe(n):
 
 
 if __name__ == "__main__":
-    what = sys.argv[1] if len(sys.argv) > 1 else "probe"
-    n = int(sys.argv[2]) if len(sys.argv) > 2 else (200 if what == "probe" else 600)
-    probe(n) if what == "probe" else pipe(n)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", nargs="?", default="probe", choices=["probe", "pipe"])
+    ap.add_argument("frames", nargs="?", type=int, default=None)
+    ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS))
+    ap.add_argument("--chroma-loc", default="left", choices=list(ncnn.CHROMA_LOCS))
+    a = ap.parse_args()
+    if a.chroma_filter != "replicate":
+        CHROMA.update(chroma_filter=a.chroma_filter, chroma_loc=a.chroma_loc)
+    n = a.frames if a.frames is not None else (200 if a.what == "probe" else 600)
+    probe(n) if a.what == "probe" else pipe(n)

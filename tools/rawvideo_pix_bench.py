@@ -1,7 +1,9 @@
 """Rate of the rawvideo streamer (python -m upscale_video_amd.rawvideo -s 2) at 1080p -> 2x per pair of pixel formats
 (--in-pix-fmt / --out-pix-fmt), file -> /dev/null and pipe -> pipe, frames held in /dev/shm: whole process wall time minus
 the wall time of a 1-frame run (interpreter start, model load, first-use allocations), as tools/rawvideo_bench.py.
-Argument: frames (default 600)."""
+Argument: frames (default 600).  --formats in:out[,in:out...] picks the rows; --chroma-filter / --chroma-loc go to the streamer
+(DESIGN.md section 7.5)."""
+import argparse
 import os
 import subprocess
 import sys
@@ -12,9 +14,18 @@ sys.path.insert(0, ROOT)
 from upscale_video_amd import ncnn                      # noqa: E402
 from upscale_video_amd.synth import synthetic_frame      # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 600
+ap = argparse.ArgumentParser()
+ap.add_argument("frames", nargs="?", type=int, default=600)
+ap.add_argument("--formats", default="bgr24:bgr24,yuv420p:yuv420p,yuv420p:p010le")
+ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS))
+ap.add_argument("--chroma-loc", default="left", choices=list(ncnn.CHROMA_LOCS))
+a = ap.parse_args()
+N = a.frames
 h, w = 1080, 1920
 base = [sys.executable, "-m", "upscale_video_amd.rawvideo", "-W", str(w), "-H", str(h), "-s", "2"]
+if a.chroma_filter != "replicate":
+    base += ["--chroma-filter", a.chroma_filter, "--chroma-loc", a.chroma_loc]
+    print("chroma %s/%s" % (a.chroma_filter, a.chroma_loc), flush=True)
 
 
 def wall(cmd, shell=False):
@@ -24,7 +35,7 @@ def wall(cmd, shell=False):
 
 
 fr = [synthetic_frame(h, w, seed=i) for i in range(4)]
-for fin, fout in (("bgr24", "bgr24"), ("yuv420p", "yuv420p"), ("yuv420p", "p010le")):
+for fin, fout in (tuple(x.split(":")) for x in a.formats.split(",")):
     src = "/dev/shm/uva_in.%s" % fin
     packed = [ncnn.convert_pix(f, h, w, "bgr24", fin).tobytes() if fin != "bgr24" else f.tobytes() for f in fr]
     with open(src, "wb") as o:

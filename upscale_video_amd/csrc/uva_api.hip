@@ -2232,7 +2232,7 @@ int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, i
     if (h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image size");
     if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) return fail("unknown pixel format");
     if (!u16 && (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE)) return fail("bgr48le is a 16-bit format: use the 16-bit entries (uva_pix_convert16)");
-    if (colour & ~PIX_COLOUR_MASK) return fail("bad colour word");
+    if (!pix_colour_ok(colour)) return fail("bad colour word");
     return 0;
 }
 
@@ -3086,7 +3086,7 @@ long long uva_net_submit_pix(uva_net* n, const void* in, int in_fmt, int h, int 
 {
     if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
     if (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE) { fail("bgr48le is a 16-bit format: use uva_net_submit_pix16"); return -1; }
-    if (colour & ~PIX_COLOUR_MASK) { fail("bad colour word"); return -1; }
+    if (!pix_colour_ok(colour)) { fail("bad colour word"); return -1; }
     if (check_dims(n, h, w)) return -1;
     const int s = uva_net_scale(n);
     if (s <= 0) { fail("net has no graph"); return -1; }
@@ -3098,7 +3098,7 @@ long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, in
                                int tile_size, int border)
 {
     if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
-    if (colour & ~PIX_COLOUR_MASK) { fail("bad colour word"); return -1; }
+    if (!pix_colour_ok(colour)) { fail("bad colour word"); return -1; }
     if (check_dims(n, h, w)) return -1;
     if (ensure_device(n) || check_u16_net(n)) return -1;
     const int s = uva_net_scale(n);

@@ -15,8 +15,24 @@
 namespace uva {
 
 enum { PIX_BGR24 = 0, PIX_YUV420P = 1, PIX_NV12 = 2, PIX_P010LE = 3, PIX_YUV420P10LE = 5, PIX_BGR48LE = 6, PIX_NFMT = 7 };   // (4: never assigned)
-// colour word: matrix in bit 0 (0 BT.601, 1 BT.709), bit 1 set = full ("pc") range, clear = limited ("tv") range
-enum { PIX_CSP_BT601 = 0, PIX_CSP_BT709 = 1, PIX_RANGE_FULL = 2, PIX_COLOUR_MASK = 3 };
+// colour word: matrix in bit 0 (0 BT.601, 1 BT.709), bit 1 set = full ("pc") range, clear = limited ("tv") range; bit 2 set =
+// chroma interpolated for its siting instead of replicated / box-averaged, the siting in bits 3 and 4
+// (neither: left, as H.264 / HEVC video; bit 3: center; bit 4: topleft)
+enum { PIX_CSP_BT601 = 0, PIX_CSP_BT709 = 1, PIX_RANGE_FULL = 2, PIX_CHROMA_BILINEAR = 4, PIX_CHROMA_CENTER = 8, PIX_CHROMA_TOPLEFT = 16,
+       PIX_COLOUR_MASK = 31 };
+// a siting bit needs the interpolation bit, and there is one siting
+inline bool pix_colour_ok(int colour)
+{
+    if (colour & ~PIX_COLOUR_MASK) return false;
+    const int loc = colour & (PIX_CHROMA_CENTER | PIX_CHROMA_TOPLEFT);
+    return !loc || ((colour & PIX_CHROMA_BILINEAR) && loc != (PIX_CHROMA_CENTER | PIX_CHROMA_TOPLEFT));
+}
+// 0: replicate / box (sections 7.3, 7.4); 1: left; 2: center; 3: topleft
+inline int pix_chroma_mode(int colour)
+{
+    if (!(colour & PIX_CHROMA_BILINEAR)) return 0;
+    return colour & PIX_CHROMA_CENTER ? 2 : (colour & PIX_CHROMA_TOPLEFT ? 3 : 1);
+}
 
 // bytes of one dense h x w frame of `fmt`; 0 for an unknown format or a size <= 0
 size_t pix_frame_bytes(int fmt, int h, int w);

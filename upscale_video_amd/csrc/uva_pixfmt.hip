@@ -2,7 +2,9 @@
 // translation unit of its own like uva_sww.hip.  Two kernel families, each instantiated per format:
 //   pix_from_bgr  u8 BGR -> yuv420p / nv12 / p010le   (behind the net: its u8 result is what gets converted)
 //   pix_to_bgr    yuv420p / nv12 / p010le -> u8 BGR   (in front of the net)
-// (yuv420p10le: p010le's arithmetic in planar words, the value in the low 10 bits), and the 16-bit route's twins (section 7.4):
+// (yuv420p10le: p010le's arithmetic in planar words, the value in the low 10 bits), and the 16-bit route's twins (section 7.4).
+// Template parameter MODE picks the chroma resampling: 0 replicates / box-averages (sections 7.3, 7.4), 1..3 interpolate for
+// chroma sited left, center or topleft (section 7.5).
 // Both families are templated on the BGR sample type S: u8, or u16 (unorm16) for the 16-bit route (section 7.4).  Beside them
 //   pix_widen / pix_narrow  u8 BGR <-> u16 BGR (v * 257, rint(v / 257))
 // One thread covers 8 pixels of two rows -- a 2x2 block per chroma sample, so every chroma sample is read or written once.  Both
@@ -93,9 +95,113 @@ __device__ __forceinline__ uint32_t pack2(int a, int b) { return (uint32_t)a | (
 __device__ __forceinline__ int byte_of(const uint32_t* d, int k) { return (d[k >> 2] >> (8 * (k & 3))) & 255; }
 __device__ __forceinline__ int half_of(const uint32_t* d, int k) { return (d[k >> 1] >> (16 * (k & 1))) & 0xffff; }
 
+// ---- the interpolating chroma modes ----------------------------------------------------------
+// MODE 0: chroma replicated coming in, the 2x2 box going out (sections 7.3, 7.4).  MODE 1..3: bilinear for chroma sited
+// `left` (horizontally on luma 2k, vertically midway), `center` (midway on both axes) or `topleft` (on luma 2k, 2k on both).
+// A tap outside the plane takes the nearest sample inside.  The weights are integers over 2^DL; the division is in the
+// final shift.  u8 sums stay in int32; u16 sums (section 7.4's scales times up to 16) are added in int64.
+template <int MODE> struct Siting {
+    static constexpr bool HCO = MODE == 1 || MODE == 3;      // horizontally co-sited
+    static constexpr bool VCO = MODE == 3;                   // vertically co-sited
+    static constexpr int DL = 4 - (HCO ? 1 : 0) - (VCO ? 1 : 0);       // coming in: 2 x 2, 2 x 4 or 4 x 4
+    static constexpr int DLF = 2 + (HCO ? 1 : 0) + (VCO ? 1 : 0);      // going out: [1 1] or [1 2 1] per axis
+};
+template <typename S, int MODE> struct AccOf { typedef long long type; };
+template <int MODE> struct AccOf<uint8_t, MODE> { typedef int type; };
+template <typename S> struct AccOf<S, 0> { typedef int type; };
+
+// one chroma sample pair at (cy, cx), both inside the plane
+template <int FMT>
+__device__ __forceinline__ void chroma_at(const uint8_t* __restrict__ up, const uint8_t* __restrict__ vp, int cy, int cx, int cw, int& u, int& v)
+{
+    const size_t o = (size_t)cy * cw + cx;
+    if (FMT == PIX_YUV420P) { u = up[o]; v = vp[o]; }
+    else if (FMT == PIX_YUV420P10LE) { u = reinterpret_cast<const uint16_t*>(up)[o] & 1023; v = reinterpret_cast<const uint16_t*>(vp)[o] & 1023; }
+    else if (FMT == PIX_NV12) { u = up[2 * o]; v = up[2 * o + 1]; }
+    else { u = reinterpret_cast<const uint16_t*>(up)[2 * o] >> 6; v = reinterpret_cast<const uint16_t*>(up)[2 * o + 1] >> 6; }
+}
+
+// chroma row cy, samples cx0 - 1 .. cx0 + 4 (clamped into the row) -> u[0..5], v[0..5]; `whole`: the middle four lie inside
+// and aligned, and move as one access per plane
+template <int FMT>
+__device__ __forceinline__ void chroma_row6(const uint8_t* __restrict__ up, const uint8_t* __restrict__ vp, int cy, int cx0, int cw, bool whole,
+                                            int* u, int* v)
+{
+    if (whole) {
+        const size_t o = (size_t)cy * cw + cx0;
+        if (FMT == PIX_YUV420P) {
+            const uint32_t du = *reinterpret_cast<const uint32_t*>(up + o), dv = *reinterpret_cast<const uint32_t*>(vp + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { u[j + 1] = byte_of(&du, j); v[j + 1] = byte_of(&dv, j); }
+        } else if (FMT == PIX_YUV420P10LE) {
+            const uint2 vu = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(up) + o);
+            const uint2 vv = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(vp) + o);
+            const uint32_t du[2] = {vu.x, vu.y}, dv[2] = {vv.x, vv.y};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { u[j + 1] = half_of(du, j) & 1023; v[j + 1] = half_of(dv, j) & 1023; }
+        } else if (FMT == PIX_NV12) {
+            const uint2 q = *reinterpret_cast<const uint2*>(up + 2 * o);
+            const uint32_t d[2] = {q.x, q.y};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { u[j + 1] = byte_of(d, 2 * j); v[j + 1] = byte_of(d, 2 * j + 1); }
+        } else {
+            const uint4 q = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(up) + 2 * o);
+            const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { u[j + 1] = half_of(d, 2 * j) >> 6; v[j + 1] = half_of(d, 2 * j + 1) >> 6; }
+        }
+        chroma_at<FMT>(up, vp, cy, max(cx0 - 1, 0), cw, u[0], v[0]);
+        chroma_at<FMT>(up, vp, cy, min(cx0 + 4, cw - 1), cw, u[5], v[5]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) chroma_at<FMT>(up, vp, cy, min(max(cx0 - 1 + j, 0), cw - 1), cw, u[j], v[j]);
+    }
+}
+
+// BGR row `line`, pixels x0 - 1 .. x0 + 7 (clamped into the row) -> b[0..8], g[0..8], r[0..8]; `whole`: the last eight lie
+// inside and aligned
+template <typename S>
+__device__ __forceinline__ void bgr_row9(const S* __restrict__ line, int x0, int w, bool whole, int* b, int* g, int* r)
+{
+    const S* l = line + 3 * (size_t)max(x0 - 1, 0);
+    b[0] = l[0]; g[0] = l[1]; r[0] = l[2];
+    if (whole) {
+        const S* row = line + 3 * (size_t)x0;
+        if constexpr (sizeof(S) == 1) {
+            uint32_t d[6];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const uint2 v = reinterpret_cast<const uint2*>(row)[q];
+                d[2 * q] = v.x; d[2 * q + 1] = v.y;
+            }
+#pragma unroll
+            for (int i = 0; i < PX; ++i) { b[i + 1] = byte_of(d, 3 * i); g[i + 1] = byte_of(d, 3 * i + 1); r[i + 1] = byte_of(d, 3 * i + 2); }
+        } else {
+            uint32_t d[12];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const uint4 v = reinterpret_cast<const uint4*>(row)[q];
+                d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+            }
+#pragma unroll
+            for (int i = 0; i < PX; ++i) { b[i + 1] = half_of(d, 3 * i); g[i + 1] = half_of(d, 3 * i + 1); r[i + 1] = half_of(d, 3 * i + 2); }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < PX; ++i) {
+            const S* p = line + 3 * (size_t)min(x0 + i, w - 1);
+            b[i + 1] = p[0]; g[i + 1] = p[1]; r[i + 1] = p[2];
+        }
+    }
+}
+
+// the horizontal filter going out, around chroma sample j of a thread: [1 2 1] on luma 2j (co-sited) or [1 1] on 2j, 2j + 1;
+// p[0] is the pixel left of the thread's eight
+template <bool HCO> __device__ __forceinline__ int hsum(const int* p, int j) { return HCO ? p[2 * j] + 2 * p[2 * j + 1] + p[2 * j + 2] : p[2 * j + 1] + p[2 * j + 2]; }
+
 // BGR [h][w][3] of S (u8, or u16 for the 16-bit route) -> planes.  yp: the Y plane; up / vp: U and V (yuv420p, yuv420p10le) or
 // the interleaved plane and null (nv12, p010le).
-template <int FMT, bool VEC, typename S>
+template <int FMT, bool VEC, typename S, int MODE = 0>
 __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const S* __restrict__ bgr, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
                                                          uint8_t* __restrict__ vp, int h, int w, FwdCoef c)
 {
@@ -107,36 +213,47 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const S* __restrict__ bg
     const int cw = (w + 1) >> 1;
     const bool whole = VEC && x0 + PX <= w && y0 + 2 <= h;
     int r[2][PX], g[2][PX], b[2][PX];
+    int er[3][PX + 1], eg[3][PX + 1], eb[3][PX + 1];    // MODE != 0: rows y0 - 1, y0, y0 + 1, the pixel left of the eight in front
+    if constexpr (MODE == 0) {
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const S* row = bgr + ((size_t)(y0 + k) * w + x0) * 3;
-        if (whole) {
-            if constexpr (sizeof(S) == 1) {
-                uint32_t d[6];
+        for (int k = 0; k < 2; ++k) {
+            const S* row = bgr + ((size_t)(y0 + k) * w + x0) * 3;
+            if (whole) {
+                if constexpr (sizeof(S) == 1) {
+                    uint32_t d[6];
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const uint2 v = reinterpret_cast<const uint2*>(row)[q];
-                    d[2 * q] = v.x; d[2 * q + 1] = v.y;
+                    for (int q = 0; q < 3; ++q) {
+                        const uint2 v = reinterpret_cast<const uint2*>(row)[q];
+                        d[2 * q] = v.x; d[2 * q + 1] = v.y;
+                    }
+#pragma unroll
+                    for (int i = 0; i < PX; ++i) { b[k][i] = byte_of(d, 3 * i); g[k][i] = byte_of(d, 3 * i + 1); r[k][i] = byte_of(d, 3 * i + 2); }
+                } else {
+                    uint32_t d[12];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        const uint4 v = reinterpret_cast<const uint4*>(row)[q];
+                        d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+                    }
+#pragma unroll
+                    for (int i = 0; i < PX; ++i) { b[k][i] = half_of(d, 3 * i); g[k][i] = half_of(d, 3 * i + 1); r[k][i] = half_of(d, 3 * i + 2); }
                 }
-#pragma unroll
-                for (int i = 0; i < PX; ++i) { b[k][i] = byte_of(d, 3 * i); g[k][i] = byte_of(d, 3 * i + 1); r[k][i] = byte_of(d, 3 * i + 2); }
             } else {
-                uint32_t d[12];
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const uint4 v = reinterpret_cast<const uint4*>(row)[q];
-                    d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+                for (int i = 0; i < PX; ++i) {
+                    const bool in = y0 + k < h && x0 + i < w;
+                    b[k][i] = in ? row[3 * i] : 0; g[k][i] = in ? row[3 * i + 1] : 0; r[k][i] = in ? row[3 * i + 2] : 0;
                 }
-#pragma unroll
-                for (int i = 0; i < PX; ++i) { b[k][i] = half_of(d, 3 * i); g[k][i] = half_of(d, 3 * i + 1); r[k][i] = half_of(d, 3 * i + 2); }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < PX; ++i) {
-                const bool in = y0 + k < h && x0 + i < w;
-                b[k][i] = in ? row[3 * i] : 0; g[k][i] = in ? row[3 * i + 1] : 0; r[k][i] = in ? row[3 * i + 2] : 0;
             }
         }
+    } else {
+#pragma unroll
+        for (int k = Siting<MODE>::VCO ? 0 : 1; k < 3; ++k)
+            bgr_row9<S>(bgr + (size_t)min(max(y0 - 1 + k, 0), h - 1) * w * 3, x0, w, whole, eb[k], eg[k], er[k]);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int i = 0; i < PX; ++i) { b[k][i] = eb[k + 1][i + 1]; g[k][i] = eg[k + 1][i + 1]; r[k][i] = er[k + 1][i + 1]; }
     }
     // luma
 #pragma unroll
@@ -169,20 +286,38 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const S* __restrict__ bg
         }
     }
     // chroma: one sample per 2x2 block (2 or 1 pixels at an odd edge), from the block's sums; the division is in the shift
-    const int rows = h - y0 < 2 ? 1 : 2;
     int cu[PX / 2], cv[PX / 2];
+    if constexpr (MODE == 0) {
+        const int rows = h - y0 < 2 ? 1 : 2;
 #pragma unroll
-    for (int j = 0; j < PX / 2; ++j) {
-        const int cols = w - (x0 + 2 * j) < 2 ? 1 : 2;
-        int sr = 0, sg = 0, sb = 0;
+        for (int j = 0; j < PX / 2; ++j) {
+            const int cols = w - (x0 + 2 * j) < 2 ? 1 : 2;
+            int sr = 0, sg = 0, sb = 0;
 #pragma unroll
-        for (int k = 0; k < 2; ++k)
+            for (int k = 0; k < 2; ++k)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-                if (k < rows && i < cols) { sr += r[k][2 * j + i]; sg += g[k][2 * j + i]; sb += b[k][2 * j + i]; }
-        const int s = SH + (rows - 1) + (cols - 1);
-        cu[j] = clampi((c.ur * sr + c.ug * sg + c.ub * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
-        cv[j] = clampi((c.vr * sr + c.vg * sg + c.vb * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
+                for (int i = 0; i < 2; ++i)
+                    if (k < rows && i < cols) { sr += r[k][2 * j + i]; sg += g[k][2 * j + i]; sb += b[k][2 * j + i]; }
+            const int s = SH + (rows - 1) + (cols - 1);
+            cu[j] = clampi((c.ur * sr + c.ug * sg + c.ub * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
+            cv[j] = clampi((c.vr * sr + c.vg * sg + c.vb * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
+        }
+    } else {
+        // section 7.5: the weighted sums of R, G, B over the siting's window (3x2, 2x2 or 3x3), the weights' 2^DLF in the shift
+        typedef typename AccOf<S, MODE>::type Acc;
+        constexpr bool HCO = Siting<MODE>::HCO, VCO = Siting<MODE>::VCO;
+        constexpr int s = SH + Siting<MODE>::DLF;
+#pragma unroll
+        for (int j = 0; j < PX / 2; ++j) {
+            int sr = hsum<HCO>(er[1], j) + hsum<HCO>(er[2], j), sg = hsum<HCO>(eg[1], j) + hsum<HCO>(eg[2], j),
+                sb = hsum<HCO>(eb[1], j) + hsum<HCO>(eb[2], j);
+            if (VCO) {
+                sr += hsum<HCO>(er[0], j) + hsum<HCO>(er[1], j); sg += hsum<HCO>(eg[0], j) + hsum<HCO>(eg[1], j);
+                sb += hsum<HCO>(eb[0], j) + hsum<HCO>(eb[1], j);
+            }
+            cu[j] = clampi((int)(((Acc)c.ur * sr + (Acc)c.ug * sg + (Acc)c.ub * sb + ((Acc)c.coff << s) + ((Acc)1 << (s - 1))) >> s), c.maxv);
+            cv[j] = clampi((int)(((Acc)c.vr * sr + (Acc)c.vg * sg + (Acc)c.vb * sb + ((Acc)c.coff << s) + ((Acc)1 << (s - 1))) >> s), c.maxv);
+        }
     }
     const int cx0 = x0 >> 1;
     if (FMT == PIX_YUV420P) {
@@ -229,9 +364,9 @@ __global__ __launch_bounds__(BX * BY) void pix_from_bgr(const S* __restrict__ bg
     }
 }
 
-// planes -> BGR [h][w][3] of S; chroma replicated over its 2x2 block; p010le converts from the 10-bit values (word >> 6),
+// planes -> BGR [h][w][3] of S; chroma replicated over its 2x2 block (MODE 0) or interpolated (MODE 1..3); p010le converts from the 10-bit values (word >> 6),
 // yuv420p10le from the low 10 bits of its words
-template <int FMT, bool VEC, typename S>
+template <int FMT, bool VEC, typename S, int MODE = 0>
 __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
                                                        const uint8_t* __restrict__ vp, S* __restrict__ bgr, int h, int w, InvCoef c)
 {
@@ -243,72 +378,80 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
     const int cw = (w + 1) >> 1, cx0 = x0 >> 1;
     const bool whole = VEC && x0 + PX <= w && y0 + 2 <= h;
     int cu[PX / 2], cv[PX / 2];
-    if (FMT == PIX_YUV420P) {
-        const uint8_t* su = up + (size_t)gy * cw + cx0;
-        const uint8_t* sv = vp + (size_t)gy * cw + cx0;
-        if (whole) {
-            const uint32_t du = reinterpret_cast<const uint32_t*>(su)[0], dv = reinterpret_cast<const uint32_t*>(sv)[0];
+    int tr[PX / 2], tg[PX / 2], tb[PX / 2];
+    int nu[3][PX / 2 + 2], nv[3][PX / 2 + 2];      // MODE != 0: chroma rows gy - 1, gy, gy + 1, samples cx0 - 1 .. cx0 + 4
+    if constexpr (MODE == 0) {
+        if (FMT == PIX_YUV420P) {
+            const uint8_t* su = up + (size_t)gy * cw + cx0;
+            const uint8_t* sv = vp + (size_t)gy * cw + cx0;
+            if (whole) {
+                const uint32_t du = reinterpret_cast<const uint32_t*>(su)[0], dv = reinterpret_cast<const uint32_t*>(sv)[0];
 #pragma unroll
-            for (int j = 0; j < PX / 2; ++j) { cu[j] = byte_of(&du, j); cv[j] = byte_of(&dv, j); }
+                for (int j = 0; j < PX / 2; ++j) { cu[j] = byte_of(&du, j); cv[j] = byte_of(&dv, j); }
+            } else {
+#pragma unroll
+                for (int j = 0; j < PX / 2; ++j) {
+                    const bool in = cx0 + j < cw;
+                    cu[j] = in ? su[j] : 0; cv[j] = in ? sv[j] : 0;
+                }
+            }
+        } else if (FMT == PIX_YUV420P10LE) {
+            const uint16_t* su = reinterpret_cast<const uint16_t*>(up) + (size_t)gy * cw + cx0;
+            const uint16_t* sv = reinterpret_cast<const uint16_t*>(vp) + (size_t)gy * cw + cx0;
+            if (whole) {
+                const uint2 vu = reinterpret_cast<const uint2*>(su)[0], vv = reinterpret_cast<const uint2*>(sv)[0];
+                const uint32_t du[2] = {vu.x, vu.y}, dv[2] = {vv.x, vv.y};
+#pragma unroll
+                for (int j = 0; j < PX / 2; ++j) { cu[j] = half_of(du, j) & 1023; cv[j] = half_of(dv, j) & 1023; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < PX / 2; ++j) {
+                    const bool in = cx0 + j < cw;
+                    cu[j] = in ? su[j] & 1023 : 0; cv[j] = in ? sv[j] & 1023 : 0;
+                }
+            }
+        } else if (FMT == PIX_NV12) {
+            const uint8_t* s = up + (size_t)gy * 2 * cw + 2 * cx0;
+            if (whole) {
+                const uint2 v = reinterpret_cast<const uint2*>(s)[0];
+                const uint32_t d[2] = {v.x, v.y};
+#pragma unroll
+                for (int j = 0; j < PX / 2; ++j) { cu[j] = byte_of(d, 2 * j); cv[j] = byte_of(d, 2 * j + 1); }
+            } else {
+#pragma unroll
+                for (int j = 0; j < PX / 2; ++j) {
+                    const bool in = cx0 + j < cw;
+                    cu[j] = in ? s[2 * j] : 0; cv[j] = in ? s[2 * j + 1] : 0;
+                }
+            }
         } else {
+            const uint16_t* s = reinterpret_cast<const uint16_t*>(up) + (size_t)gy * 2 * cw + 2 * cx0;
+            if (whole) {
+                const uint4 v = reinterpret_cast<const uint4*>(s)[0];
+                const uint32_t d[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int j = 0; j < PX / 2; ++j) {
-                const bool in = cx0 + j < cw;
-                cu[j] = in ? su[j] : 0; cv[j] = in ? sv[j] : 0;
+                for (int j = 0; j < PX / 2; ++j) { cu[j] = half_of(d, 2 * j) >> 6; cv[j] = half_of(d, 2 * j + 1) >> 6; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < PX / 2; ++j) {
+                    const bool in = cx0 + j < cw;
+                    cu[j] = in ? s[2 * j] >> 6 : 0; cv[j] = in ? s[2 * j + 1] >> 6 : 0;
+                }
             }
         }
-    } else if (FMT == PIX_YUV420P10LE) {
-        const uint16_t* su = reinterpret_cast<const uint16_t*>(up) + (size_t)gy * cw + cx0;
-        const uint16_t* sv = reinterpret_cast<const uint16_t*>(vp) + (size_t)gy * cw + cx0;
-        if (whole) {
-            const uint2 vu = reinterpret_cast<const uint2*>(su)[0], vv = reinterpret_cast<const uint2*>(sv)[0];
-            const uint32_t du[2] = {vu.x, vu.y}, dv[2] = {vv.x, vv.y};
+        // the chroma terms of a sample are shared by its block's pixels
 #pragma unroll
-            for (int j = 0; j < PX / 2; ++j) { cu[j] = half_of(du, j) & 1023; cv[j] = half_of(dv, j) & 1023; }
-        } else {
-#pragma unroll
-            for (int j = 0; j < PX / 2; ++j) {
-                const bool in = cx0 + j < cw;
-                cu[j] = in ? su[j] & 1023 : 0; cv[j] = in ? sv[j] & 1023 : 0;
-            }
-        }
-    } else if (FMT == PIX_NV12) {
-        const uint8_t* s = up + (size_t)gy * 2 * cw + 2 * cx0;
-        if (whole) {
-            const uint2 v = reinterpret_cast<const uint2*>(s)[0];
-            const uint32_t d[2] = {v.x, v.y};
-#pragma unroll
-            for (int j = 0; j < PX / 2; ++j) { cu[j] = byte_of(d, 2 * j); cv[j] = byte_of(d, 2 * j + 1); }
-        } else {
-#pragma unroll
-            for (int j = 0; j < PX / 2; ++j) {
-                const bool in = cx0 + j < cw;
-                cu[j] = in ? s[2 * j] : 0; cv[j] = in ? s[2 * j + 1] : 0;
-            }
+        for (int j = 0; j < PX / 2; ++j) {
+            const int u = cu[j] - c.coff, v = cv[j] - c.coff;
+            tr[j] = c.rv * v + (1 << (SH - 1));
+            tg[j] = c.gu * u + c.gv * v + (1 << (SH - 1));
+            tb[j] = c.bu * u + (1 << (SH - 1));
         }
     } else {
-        const uint16_t* s = reinterpret_cast<const uint16_t*>(up) + (size_t)gy * 2 * cw + 2 * cx0;
-        if (whole) {
-            const uint4 v = reinterpret_cast<const uint4*>(s)[0];
-            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+        const int ch = (h + 1) >> 1;
 #pragma unroll
-            for (int j = 0; j < PX / 2; ++j) { cu[j] = half_of(d, 2 * j) >> 6; cv[j] = half_of(d, 2 * j + 1) >> 6; }
-        } else {
-#pragma unroll
-            for (int j = 0; j < PX / 2; ++j) {
-                const bool in = cx0 + j < cw;
-                cu[j] = in ? s[2 * j] >> 6 : 0; cv[j] = in ? s[2 * j + 1] >> 6 : 0;
-            }
-        }
-    }
-    // the chroma terms of a sample are shared by its block's pixels
-    int tr[PX / 2], tg[PX / 2], tb[PX / 2];
-#pragma unroll
-    for (int j = 0; j < PX / 2; ++j) {
-        const int u = cu[j] - c.coff, v = cv[j] - c.coff;
-        tr[j] = c.rv * v + (1 << (SH - 1));
-        tg[j] = c.gu * u + c.gv * v + (1 << (SH - 1));
-        tb[j] = c.bu * u + (1 << (SH - 1));
+        for (int k = Siting<MODE>::VCO ? 1 : 0; k < 3; ++k)
+            chroma_row6<FMT>(up, vp, min(max(gy - 1 + k, 0), ch - 1), cx0, cw, whole, nu[k], nv[k]);
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -342,12 +485,47 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
             }
         }
         int px[3 * PX];
+        if constexpr (MODE == 0) {
 #pragma unroll
-        for (int i = 0; i < PX; ++i) {
-            const int yy = c.ky * (yv[i] - c.yoff);
-            px[3 * i] = clampi((yy + tb[i >> 1]) >> SH, VMAX);
-            px[3 * i + 1] = clampi((yy + tg[i >> 1]) >> SH, VMAX);
-            px[3 * i + 2] = clampi((yy + tr[i >> 1]) >> SH, VMAX);
+            for (int i = 0; i < PX; ++i) {
+                const int yy = c.ky * (yv[i] - c.yoff);
+                px[3 * i] = clampi((yy + tb[i >> 1]) >> SH, VMAX);
+                px[3 * i + 1] = clampi((yy + tg[i >> 1]) >> SH, VMAX);
+                px[3 * i + 2] = clampi((yy + tr[i >> 1]) >> SH, VMAX);
+            }
+        } else {
+            // section 7.5: the two axes' integer weights multiplied out, over 2^DL; the sum goes into the matrix unrounded
+            typedef typename AccOf<S, MODE>::type Acc;
+            constexpr bool HCO = Siting<MODE>::HCO, VCO = Siting<MODE>::VCO;
+            constexpr int DL = Siting<MODE>::DL, s = SH + DL;
+            int vu[PX / 2 + 2], vv[PX / 2 + 2];     // this luma row's vertical sums
+#pragma unroll
+            for (int j = 0; j < PX / 2 + 2; ++j) {
+                if (VCO) {
+                    vu[j] = k == 0 ? 2 * nu[1][j] : nu[1][j] + nu[2][j];
+                    vv[j] = k == 0 ? 2 * nv[1][j] : nv[1][j] + nv[2][j];
+                } else {
+                    vu[j] = k == 0 ? nu[0][j] + 3 * nu[1][j] : 3 * nu[1][j] + nu[2][j];
+                    vv[j] = k == 0 ? nv[0][j] + 3 * nv[1][j] : 3 * nv[1][j] + nv[2][j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < PX; ++i) {
+                const int j = (i >> 1) + 1;
+                int u, v;
+                if (HCO) {
+                    u = i & 1 ? vu[j] + vu[j + 1] : 2 * vu[j];
+                    v = i & 1 ? vv[j] + vv[j + 1] : 2 * vv[j];
+                } else {
+                    u = i & 1 ? 3 * vu[j] + vu[j + 1] : vu[j - 1] + 3 * vu[j];
+                    v = i & 1 ? 3 * vv[j] + vv[j + 1] : vv[j - 1] + 3 * vv[j];
+                }
+                u -= c.coff << DL; v -= c.coff << DL;
+                const Acc yy = (Acc)(c.ky * (yv[i] - c.yoff)) * (1 << DL) + ((Acc)1 << (s - 1));
+                px[3 * i] = clampi((int)((yy + (Acc)c.bu * u) >> s), VMAX);
+                px[3 * i + 1] = clampi((int)((yy + (Acc)c.gu * u + (Acc)c.gv * v) >> s), VMAX);
+                px[3 * i + 2] = clampi((int)((yy + (Acc)c.rv * v) >> s), VMAX);
+            }
         }
         S* dst = bgr + o * 3;
         if (whole) {
@@ -441,17 +619,26 @@ int depth_of(int fmt) { return fmt == PIX_P010LE || fmt == PIX_YUV420P10LE ? 10 
 template <typename S>
 hipError_t from_bgr(hipStream_t stream, int fmt, int colour, const S* bgr, void* dst, int h, int w)
 {
-    if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
+    if (h <= 0 || w <= 0 || !pix_colour_ok(colour) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
     const uint8_t *yp, *up, *vp;
     planes(fmt, (const uint8_t*)dst, h, w, &yp, &up, &vp);
     const FwdCoef c = fwd_coef(colour, depth_of(fmt), sizeof(S) == 2);
     const bool vec = vec_ok(bgr, dst, w);
     const dim3 grid = grid_of(h, w), block(BX, BY);
     uint8_t *y = const_cast<uint8_t*>(yp), *u = const_cast<uint8_t*>(up), *v = const_cast<uint8_t*>(vp);
+#define UVA_PIX_LAUNCH_M(F, M)                                                                                              \
+    do {                                                                                                                    \
+        if (vec) hipLaunchKernelGGL((pix_from_bgr<F, true, S, M>), grid, block, 0, stream, bgr, y, u, v, h, w, c);         \
+        else hipLaunchKernelGGL((pix_from_bgr<F, false, S, M>), grid, block, 0, stream, bgr, y, u, v, h, w, c);            \
+    } while (0)
 #define UVA_PIX_LAUNCH(F)                                                                                                   \
     do {                                                                                                                    \
-        if (vec) hipLaunchKernelGGL((pix_from_bgr<F, true, S>), grid, block, 0, stream, bgr, y, u, v, h, w, c);            \
-        else hipLaunchKernelGGL((pix_from_bgr<F, false, S>), grid, block, 0, stream, bgr, y, u, v, h, w, c);               \
+        switch (pix_chroma_mode(colour)) {                                                                                  \
+        case 0: UVA_PIX_LAUNCH_M(F, 0); break;                                                                              \
+        case 1: UVA_PIX_LAUNCH_M(F, 1); break;                                                                              \
+        case 2: UVA_PIX_LAUNCH_M(F, 2); break;                                                                              \
+        default: UVA_PIX_LAUNCH_M(F, 3); break;                                                                             \
+        }                                                                                                                   \
     } while (0)
     switch (fmt) {
     case PIX_YUV420P: UVA_PIX_LAUNCH(PIX_YUV420P); break;
@@ -461,22 +648,32 @@ hipError_t from_bgr(hipStream_t stream, int fmt, int colour, const S* bgr, void*
     default: return hipErrorInvalidValue;
     }
 #undef UVA_PIX_LAUNCH
+#undef UVA_PIX_LAUNCH_M
     return hipGetLastError();
 }
 
 template <typename S>
 hipError_t to_bgr(hipStream_t stream, int fmt, int colour, const void* src, S* bgr, int h, int w)
 {
-    if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
+    if (h <= 0 || w <= 0 || !pix_colour_ok(colour) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
     const uint8_t *y, *u, *v;
     planes(fmt, (const uint8_t*)src, h, w, &y, &u, &v);
     const InvCoef c = inv_coef(colour, depth_of(fmt), sizeof(S) == 2);
     const bool vec = vec_ok(bgr, src, w);
     const dim3 grid = grid_of(h, w), block(BX, BY);
+#define UVA_PIX_LAUNCH_M(F, M)                                                                                              \
+    do {                                                                                                                    \
+        if (vec) hipLaunchKernelGGL((pix_to_bgr<F, true, S, M>), grid, block, 0, stream, y, u, v, bgr, h, w, c);         \
+        else hipLaunchKernelGGL((pix_to_bgr<F, false, S, M>), grid, block, 0, stream, y, u, v, bgr, h, w, c);            \
+    } while (0)
 #define UVA_PIX_LAUNCH(F)                                                                                                   \
     do {                                                                                                                    \
-        if (vec) hipLaunchKernelGGL((pix_to_bgr<F, true, S>), grid, block, 0, stream, y, u, v, bgr, h, w, c);              \
-        else hipLaunchKernelGGL((pix_to_bgr<F, false, S>), grid, block, 0, stream, y, u, v, bgr, h, w, c);                 \
+        switch (pix_chroma_mode(colour)) {                                                                                  \
+        case 0: UVA_PIX_LAUNCH_M(F, 0); break;                                                                              \
+        case 1: UVA_PIX_LAUNCH_M(F, 1); break;                                                                              \
+        case 2: UVA_PIX_LAUNCH_M(F, 2); break;                                                                              \
+        default: UVA_PIX_LAUNCH_M(F, 3); break;                                                                             \
+        }                                                                                                                   \
     } while (0)
     switch (fmt) {
     case PIX_YUV420P: UVA_PIX_LAUNCH(PIX_YUV420P); break;
@@ -486,6 +683,7 @@ hipError_t to_bgr(hipStream_t stream, int fmt, int colour, const void* src, S* b
     default: return hipErrorInvalidValue;
     }
 #undef UVA_PIX_LAUNCH
+#undef UVA_PIX_LAUNCH_M
     return hipGetLastError();
 }
 
@@ -505,7 +703,7 @@ hipError_t launch_pix_to_bgr(hipStream_t stream, int fmt, int colour, const void
 hipError_t launch_pix16_from_bgr(hipStream_t stream, int fmt, int colour, const uint16_t* bgr, void* dst, int h, int w)
 {
     if (fmt != PIX_BGR24) return from_bgr<uint16_t>(stream, fmt, colour, bgr, dst, h, w);
-    if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK)) return hipErrorInvalidValue;
+    if (h <= 0 || w <= 0 || !pix_colour_ok(colour)) return hipErrorInvalidValue;
     const size_t n = (size_t)3 * w * h;
     if (flat_grid(n).x == 0 || n / (256 * WN) >= 0x7fffffffu) return hipErrorInvalidValue;
     if ((((uintptr_t)bgr % 16) | ((uintptr_t)dst % 8)) == 0) hipLaunchKernelGGL((pix_narrow<true>), flat_grid(n), dim3(256), 0, stream, bgr, (uint8_t*)dst, n);
@@ -516,7 +714,7 @@ hipError_t launch_pix16_from_bgr(hipStream_t stream, int fmt, int colour, const 
 hipError_t launch_pix16_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint16_t* bgr, int h, int w)
 {
     if (fmt != PIX_BGR24) return to_bgr<uint16_t>(stream, fmt, colour, src, bgr, h, w);
-    if (h <= 0 || w <= 0 || (colour & ~PIX_COLOUR_MASK)) return hipErrorInvalidValue;
+    if (h <= 0 || w <= 0 || !pix_colour_ok(colour)) return hipErrorInvalidValue;
     const size_t n = (size_t)3 * w * h;
     if (flat_grid(n).x == 0 || n / (256 * WN) >= 0x7fffffffu) return hipErrorInvalidValue;
     if ((((uintptr_t)src % 8) | ((uintptr_t)bgr % 16)) == 0) hipLaunchKernelGGL((pix_widen<true>), flat_grid(n), dim3(256), 0, stream, (const uint8_t*)src, bgr, n);

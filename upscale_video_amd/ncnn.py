@@ -123,6 +123,11 @@ PIX_FORMATS_ALL = dict(PIX_FORMATS, yuv420p10le=5, bgr48le=6)      # (code 4 is 
 PIX16_ONLY = ("bgr48le",)
 COLORSPACES = {"bt601": 0, "bt709": 1}                              # ffmpeg's -colorspace names
 COLOR_RANGES = {"tv": 0, "pc": 2}                                   # ffmpeg's -color_range names (limited, full)
+# 4:2:0 chroma resampling: replicate = chroma repeated over its 2x2 block coming in and the 2x2 box
+# going out (sections 7.3, 7.4); bilinear = interpolated for where the chroma samples sit (ffmpeg's chroma_sample_location
+# names; H.264 / HEVC video is left, JPEG / MPEG-1 center, UHD BT.2020 material topleft)
+CHROMA_FILTERS = {"replicate": 0, "bilinear": 4}
+CHROMA_LOCS = {"left": 0, "center": 8, "topleft": 16}
 
 
 def pix_frame_bytes(fmt, h, w):
@@ -136,13 +141,19 @@ def pix_frame_bytes(fmt, h, w):
             "bgr48le": 6 * w * h}[fmt]
 
 
-def colour_word(colour="bt601", color_range="tv"):
-    """the C ABI's colour argument: UVA_CSP_* | UVA_RANGE_FULL"""
+def colour_word(colour="bt601", color_range="tv", chroma_filter="replicate", chroma_loc="left"):
+    """the C ABI's colour argument: UVA_CSP_* | UVA_RANGE_FULL | UVA_CHROMA_BILINEAR | UVA_CHROMA_CENTER / _TOPLEFT"""
     if colour not in COLORSPACES:
         raise ValueError("unknown colorspace %r (%s)" % (colour, ", ".join(COLORSPACES)))
     if color_range not in COLOR_RANGES:
         raise ValueError("unknown color range %r (%s)" % (color_range, ", ".join(COLOR_RANGES)))
-    return COLORSPACES[colour] | COLOR_RANGES[color_range]
+    if chroma_filter not in CHROMA_FILTERS:
+        raise ValueError("unknown chroma filter %r (%s)" % (chroma_filter, ", ".join(CHROMA_FILTERS)))
+    if chroma_loc not in CHROMA_LOCS:
+        raise ValueError("unknown chroma location %r (%s)" % (chroma_loc, ", ".join(CHROMA_LOCS)))
+    if chroma_filter == "replicate" and chroma_loc != "left":
+        raise ValueError("chroma_loc %r needs chroma_filter='bilinear': replicate knows no siting" % chroma_loc)
+    return COLORSPACES[colour] | COLOR_RANGES[color_range] | CHROMA_FILTERS[chroma_filter] | CHROMA_LOCS[chroma_loc]
 
 
 def pix_empty(fmt, h, w, alloc=None):
@@ -171,12 +182,14 @@ def _bit_depth(bit_depth, fmts):
             raise ValueError("%s is a 16-bit format: it needs bit_depth=16" % f)
 
 
-def convert_pix(buf, h, w, in_fmt, out_fmt, colour="bt601", color_range="tv", out=None, gpu=0, bit_depth=8):
+def convert_pix(buf, h, w, in_fmt, out_fmt, colour="bt601", color_range="tv", out=None, gpu=0, bit_depth=8,
+                chroma_filter="replicate", chroma_loc="left"):
     """One dense h x w frame of in_fmt -> out_fmt on HIP device `gpu`, host to host, synchronous (include/uva.h
     uva_pix_convert; bit_depth=16: uva_pix_convert16, through u16 BGR).  Returns `out` (pix_empty's
-    array for out_fmt; allocated when None)."""
+    array for out_fmt; allocated when None).  chroma_filter="bilinear": the Y'CbCr conversions interpolate chroma sited at chroma_loc
+    (DESIGN.md section 7.5)."""
     _bit_depth(bit_depth, (in_fmt, out_fmt))
-    cw = colour_word(colour, color_range)
+    cw = colour_word(colour, color_range, chroma_filter, chroma_loc)
     src = _pix_frame(buf, in_fmt, h, w, "input")
     if out is None:
         out = pix_empty(out_fmt, h, w)
@@ -392,14 +405,15 @@ class Net:
         return Ticket(t, img, out)
 
     def submit_pix(self, buf, h, w, in_fmt, out=None, out_fmt="bgr24", colour="bt601", color_range="tv", tile_size=0, border=0,
-                   bit_depth=8):
+                   bit_depth=8, chroma_filter="replicate", chroma_loc="left"):
         """submit_u8 with a rawvideo pixel format on either end (include/uva.h uva_net_submit_pix): `buf` holds one dense
         h x w frame of in_fmt, the result is one dense (h*s) x (w*s) frame of out_fmt; both conversions run on the GPU around
         the net.  `out`: optional preallocated result buffer of pix_frame_bytes(out_fmt, h*s, w*s) bytes (pix_empty; pinned
         memory avoids the staging copy).  Returns a Ticket that collect_u8 takes.  bit_depth=16: the 16-bit route
-        (uva_net_submit_pix16): the frame reaches the net as u16 BGR and leaves it as u16 BGR, no 8-bit hop."""
+        (uva_net_submit_pix16): the frame reaches the net as u16 BGR and leaves it as u16 BGR, no 8-bit hop.
+        chroma_filter="bilinear": both conversions interpolate chroma sited at chroma_loc."""
         _bit_depth(bit_depth, (in_fmt, out_fmt))
-        cw = colour_word(colour, color_range)
+        cw = colour_word(colour, color_range, chroma_filter, chroma_loc)
         s = self.scale
         if s <= 0:
             raise _lib.UvaError("net has no graph: load_param/load_model failed or were not called")
@@ -414,11 +428,13 @@ class Net:
             raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
         return Ticket(t, src, out)
 
-    def convert_pix_device(self, d_in, h, w, in_fmt, d_out, out_fmt, colour="bt601", color_range="tv", after=None):
+    def convert_pix_device(self, d_in, h, w, in_fmt, d_out, out_fmt, colour="bt601", color_range="tv", after=None,
+                           chroma_filter="replicate", chroma_loc="left"):
         """A conversion of a frame in HBM queued IN FRONT of this net (include/uva.h uva_pix_convert_device), like
         denoise_u8_device: `after` (a net, or None) comes first, this net's next work waits for the frame."""
         _lib.check(self._L.uva_pix_convert_device(self.device_index, ctypes.c_void_p(d_in), PIX_FORMATS_ALL[in_fmt], ctypes.c_void_p(d_out),
-                                                  PIX_FORMATS_ALL[out_fmt], h, w, colour_word(colour, color_range),
+                                                  PIX_FORMATS_ALL[out_fmt], h, w,
+                                                  colour_word(colour, color_range, chroma_filter, chroma_loc),
                                                   after._h if after is not None else None, self._h))
 
     def collect_u8(self, ticket):

@@ -19,6 +19,12 @@ p010le; --colorspace bt601|bt709, --color-range tv|pc, default bt601 / tv: DESIG
 --bit-depth 16 runs the 2x / 4x net on 16-bit samples so that 10-bit frames (p010le, yuv420p10le) keep their depth
 (no -m option with it).
 
+--chroma-filter bilinear interpolates the 4:2:0 chroma on the way in and filters it on the way out for where its samples sit
+ instead of repeating every chroma sample over its 2x2 block and averaging the block: the net then
+sees no 2x2 colour steps to sharpen, and colour stays registered with luma.  --chroma-loc names the siting (ffmpeg's
+chroma_sample_location): left (default) for video from H.264 / HEVC, center for JPEG / MPEG-1 material, topleft for UHD
+BT.2020 material.  The default, replicate, keeps the earlier releases' bytes.
+
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
 conversions run on the net's stream around its kernels); nets in between pass u8 BGR.  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
@@ -66,7 +72,8 @@ PIPE_DEPTH = 3   # include/uva.h: at most 3 frames in flight per net
 class PixFormats:
     """the raw-video formats of a stream's two ends and the colour arithmetic between them (ncnn.PIX_FORMATS_ALL etc.)"""
 
-    def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv", bit_depth=8):
+    def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv", bit_depth=8, chroma_filter="replicate",
+                 chroma_loc="left"):
         for f in (in_fmt, out_fmt):
             if f not in ncnn.PIX_FORMATS_ALL:
                 raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(ncnn.PIX_FORMATS_ALL)))
@@ -75,13 +82,20 @@ class PixFormats:
         for f in (in_fmt, out_fmt):
             if bit_depth == 8 and f in ncnn.PIX16_ONLY:
                 raise ValueError("%s is a 16-bit format: it needs --bit-depth 16" % f)
-        ncnn.colour_word(colour, color_range)              # (checks both names)
+        ncnn.colour_word(colour, color_range, chroma_filter, chroma_loc)              # (checks the names)
+        self.chroma_filter, self.chroma_loc = chroma_filter, chroma_loc
         self.in_fmt, self.out_fmt, self.colour, self.color_range = in_fmt, out_fmt, colour, color_range
         self.bit_depth = bit_depth     # 16: the net runs on u16 BGR, no 8-bit hop at either end
 
     def depth_kw(self):
         """the keyword the 16-bit calls take (none at 8 bits: those calls are the first pixel-format release's)"""
         return {"bit_depth": 16} if self.bit_depth == 16 else {}
+
+    def chroma_kw(self):
+        """the keywords of the interpolating chroma modes (none for replicate: those calls are the earlier releases')"""
+        if self.chroma_filter == "replicate":
+            return {}
+        return {"chroma_filter": self.chroma_filter, "chroma_loc": self.chroma_loc}
 
     def frame_bytes(self, h, w, out=False):
         return ncnn.pix_frame_bytes(self.out_fmt if out else self.in_fmt, h, w)
@@ -141,7 +155,8 @@ class Stage:
         else:
             self.inflight.append(self.net.submit_pix(frame, self.h, self.w, self.in_fmt, out=out, out_fmt=self.out_fmt,
                                                      colour=self.pix.colour, color_range=self.pix.color_range,
-                                                     tile_size=self.tile, border=border, **self.pix.depth_kw()))
+                                                     tile_size=self.tile, border=border, **self.pix.depth_kw(),
+                                                     **self.pix.chroma_kw()))
 
     def collect(self):
         return self.net.collect_u8(self.inflight.pop(0))
@@ -177,12 +192,13 @@ class DenoiseStage:
         h, w = self.h, self.w
         pix = self.pix
         if self.in_fmt != "bgr24":
-            frame = ncnn.convert_pix(frame, h, w, self.in_fmt, "bgr24", pix.colour, pix.color_range, out=self._bgr_in, gpu=self.gpu)
+            frame = ncnn.convert_pix(frame, h, w, self.in_fmt, "bgr24", pix.colour, pix.color_range, out=self._bgr_in, gpu=self.gpu,
+                                     **pix.chroma_kw())
         dst = out if self.out_fmt == "bgr24" else self._bgr_out
         _lib.check(_lib.load().uva_denoise_u8(self.gpu, frame.ctypes.data, h, w, frame.strides[0], dst.ctypes.data, dst.strides[0],
                                               self.strength, self.strength))
         if self.out_fmt != "bgr24":
-            ncnn.convert_pix(dst, h, w, "bgr24", self.out_fmt, pix.colour, pix.color_range, out=out, gpu=self.gpu)
+            ncnn.convert_pix(dst, h, w, "bgr24", self.out_fmt, pix.colour, pix.color_range, out=out, gpu=self.gpu, **pix.chroma_kw())
         self.inflight.append(out)
 
     def collect(self):
@@ -627,7 +643,7 @@ def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
             fout.write(buf)
         else:
             ncnn.convert_pix(np.frombuffer(buf, np.uint8), h, w, pix.in_fmt, pix.out_fmt, pix.colour, pix.color_range, out=res, gpu=gpu,
-                             **pix.depth_kw())
+                             **pix.depth_kw(), **pix.chroma_kw())
             fout.write(memoryview(res).cast("B"))
         n += 1
     fout.flush()
@@ -666,13 +682,23 @@ def main(argv=None):
                     help="16: the 2x / 4x net runs on 16-bit samples, so 10-bit frames (p010le, yuv420p10le) keep their depth "
                          "(default 8); takes no -m option")
     ap.add_argument("--model-path", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models"))
+    ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS),
+                    help="4:2:0 chroma resampling in the Y'CbCr conversions: replicate (default: every chroma sample repeated over its "
+                         "2x2 block coming in, the block's average going out; the earlier releases' bytes) or bilinear (interpolated "
+                         "for where the chroma samples sit, so the net is not fed 2x2 colour steps and colour stays registered with "
+                         "luma; DESIGN.md section 7.5)")
+    ap.add_argument("--chroma-loc", default=None, choices=list(ncnn.CHROMA_LOCS),
+                    help="with --chroma-filter bilinear: where the chroma samples sit (ffmpeg's chroma_sample_location).  left "
+                         "(default): video from H.264 / HEVC; center: JPEG / MPEG-1; topleft: UHD BT.2020 material")
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
     for f in (a.in_pix_fmt, a.out_pix_fmt):
         if f in ncnn.PIX16_ONLY and a.bit_depth != 16:
             ap.error("%s is a 16-bit format: it needs --bit-depth 16" % f)
-    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range, a.bit_depth)
+    if a.chroma_loc is not None and a.chroma_filter != "bilinear":
+        ap.error("--chroma-loc needs --chroma-filter bilinear: replicate knows no siting")
+    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range, a.bit_depth, a.chroma_filter, a.chroma_loc or "left")
     # upscale_video.py -m: a (anime pass), n=K (film-grain denoise, K = 1..30, :782-789), r (the x_Valar_v1 model instead of
     # x_Compact_Pretrain, :913-916); the reference runs them in the order n, a, upscale (:880-920) whatever the order given
     models = [m for m in a.models.split(",") if m]
