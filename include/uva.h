@@ -46,7 +46,9 @@ extern "C" {
                                15 + 16-bit route: + UVA_PIX_YUV420P10LE, UVA_PIX_BGR48LE, uva_net_process_u16_device,
                                    uva_net_process_u16, uva_net_submit_pix16, uva_pix_convert16 (additive as well)
                                15 + chroma siting: + UVA_CHROMA_BILINEAR, UVA_CHROMA_CENTER, UVA_CHROMA_TOPLEFT in the colour word of
-                                   every pixel-format entry (additive: colour words 0-3 mean what they meant) */
+                                   every pixel-format entry (additive: colour words 0-3 mean what they meant)
+                               15 + resampler: + uva_resize_taps, uva_resize, uva_resize_device, uva_net_submit_pix_sized, UVA_RESIZE_*
+                                   (additive: every earlier entry keeps its signature and its bytes) */
 
 typedef struct uva_net uva_net;
 
@@ -195,6 +197,33 @@ long long uva_net_submit_pix16(uva_net* net, const void* in, int in_fmt, int h, 
                                int tile_size, int border);
 /* uva_pix_convert through u16 BGR (any two formats, UVA_PIX_BGR48LE included). */
 int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour);
+
+/* ---- the resampler (csrc/uva_resize.hip; the arithmetic: DESIGN.md section 7.6) ------------------------------------
+ * BGR frames (u8 [h][w][3] with bits = 8, u16 with bits = 16; channels independent, code values as they are) to any oh x ow with
+ * 1/4 <= oh / h <= 4 and 1/4 <= ow / w <= 4, by a separable polyphase filter with integer taps (every row of a table sums to
+ * 2^14; shrinking widens the filter).  Pixel centres: output sample d sits at (d + 0.5) n_in / n_out - 0.5; a tap beyond the
+ * plane reads the nearest sample inside.  Sizes below 1, a ratio outside [1/4, 4], an unknown filter, bits other than 8 / 16 and
+ * odd strides or addresses at 16 bits are refused with uva_last_error set. */
+#define UVA_RESIZE_LANCZOS 0    /* sinc(x) sinc(x / 3), |x| < 3 */
+#define UVA_RESIZE_BICUBIC 1    /* Keys, a = -0.5, |x| < 2 */
+#define UVA_RESIZE_BILINEAR 2   /* triangle, |x| < 1 */
+/* Host only, no device needed: the table of one axis as the kernel uses it.  *ntaps receives T = 2 ceil(a max(1, n_in / n_out))
+ * (also when the call then fails for want of room: first needs n_out ints, taps n_out * T <= cap int16s); output sample d is
+ * sum_k taps[d * T + k] * in[clamp(first[d] + k, 0, n_in - 1)] / 2^14. */
+int uva_resize_taps(int n_in, int n_out, int filter, int32_t* first, int16_t* taps, size_t cap, int* ntaps);
+/* Frames resident in `device`'s HBM, asynchronous on the conversions' stream (uva_pix_convert_device's); strides in bytes;
+ * `after` / `before` (may be null) as in uva_pix_convert_device. */
+int uva_resize_device(int device, const void* d_in, int h, int w, size_t in_stride, void* d_out, int oh, int ow, size_t out_stride,
+                      int filter, int bits, uva_net* after, uva_net* before);
+/* Host to host, synchronous (tests, Python, `-s 1` without a net).  Bytes between the rows of a padded `out` are left alone. */
+int uva_resize(int device, const void* in, int h, int w, size_t in_stride, void* out, int oh, int ow, size_t out_stride, int filter,
+               int bits);
+/* uva_net_submit_pix (bits = 8) / uva_net_submit_pix16 (bits = 16) with the resampler between the net's tail and the output
+ * conversion, on the net's stream: `out` receives one dense oh x ow frame of out_fmt; chroma is subsampled and sited at the
+ * output size.  Collected by uva_net_collect_u8; slots, streams, the 3 frames in flight and the pinned / pageable rules are
+ * uva_net_submit_u8's.  oh == h*s and ow == w*s: the resampler is skipped, the bytes are uva_net_submit_pix's. */
+long long uva_net_submit_pix_sized(uva_net* net, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
+                                   int tile_size, int border, int oh, int ow, int filter, int bits);
 
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 

@@ -22,6 +22,8 @@ SYMBOLS = [
     "uva_pix_frame_bytes", "uva_net_submit_pix", "uva_pix_convert", "uva_pix_convert_device",
     # 15 + the 16-bit route (additive as well)
     "uva_net_process_u16_device", "uva_net_process_u16", "uva_net_submit_pix16", "uva_pix_convert16",
+    # 15 + the resampler (additive as well)
+    "uva_resize_taps", "uva_resize", "uva_resize_device", "uva_net_submit_pix_sized",
 ]
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -83,6 +85,10 @@ def load():
     decl("uva_net_process_u16", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i])
     decl("uva_net_process_u16_device", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i])
     decl("uva_pix_convert_device", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p])
+    decl("uva_resize_taps", [c_i, c_i, c_i, c_p, c_p, c_sz, pi])
+    decl("uva_resize", [c_i, c_p, c_i, c_i, c_sz, c_p, c_i, c_i, c_sz, c_i, c_i])
+    decl("uva_resize_device", [c_i, c_p, c_i, c_i, c_sz, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p])
+    decl("uva_net_submit_pix_sized", [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i], ctypes.c_longlong)
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

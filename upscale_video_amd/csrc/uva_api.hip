@@ -11,6 +11,7 @@
 #include "uva_kernels.hip.h"
 #include "uva_model.h"
 #include "uva_pixfmt.h"
+#include "uva_resize.h"
 #include "uva_png.hip.h"
 #include "uva_wino.h"
 #include "uva_sub5.h"
@@ -188,7 +189,8 @@ struct uva_net {
         uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;   // h_*: pinned staging
         uint8_t* d_png = nullptr;        // the PNG encoder's blocks: [meta][slots], then [the blocks packed end to end]
         uint8_t *d_pin = nullptr, *d_pout = nullptr;   // uva_net_submit_pix: the packed frames (d_in / d_out hold their BGR)
-        size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0, d_png_cap = 0, d_pin_cap = 0, d_pout_cap = 0;
+        uint8_t* d_rs = nullptr;         // uva_net_submit_pix_sized: the net's result resampled to the output size (BGR)
+        size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0, d_png_cap = 0, d_pin_cap = 0, d_pout_cap = 0, d_rs_cap = 0;
         uint8_t* png_ws = nullptr;       // PNG submit: the caller's workspace, how many packed bytes went there with the
         size_t png_sent = 0;             // frame's download, and the frame size (collect fetches the rest, if any)
         int png_h = 0, png_w = 0;
@@ -248,6 +250,7 @@ struct uva_net {
             if (ps.d_png) (void)hipFree(ps.d_png);
             if (ps.d_pin) (void)hipFree(ps.d_pin);
             if (ps.d_pout) (void)hipFree(ps.d_pout);
+            if (ps.d_rs) (void)hipFree(ps.d_rs);
             if (ps.h_in) (void)hipHostFree(ps.h_in);
             if (ps.h_out) (void)hipHostFree(ps.h_out);
             if (ps.ev_h2d) (void)hipEventDestroy(ps.ev_h2d);
@@ -2650,6 +2653,7 @@ void uva_destroy_gpu_instance(void)
     denoise_release_all();
     png_release_all();
     pix_release_all();
+    resize_release_all();
 }
 
 uva_net* uva_net_create(void)
@@ -2897,9 +2901,11 @@ namespace {
 // behind the net and d_pout comes back)
 // u16: the 16-bit route -- the net's frames are u16 BGR (BGR48LE), in_stride / out_stride are in bytes, and a packed frame
 // (bgr24 included) is converted to and from u16 BGR
+// rs_oh, rs_ow > 0 and other than the net's result size (uva_net_submit_pix_sized): the net's BGR result is resampled to
+// rs_oh x rs_ow into d_rs on the net's stream, and what follows -- the output conversion, the download -- takes d_rs at that size
 long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out, size_t out_stride,
                     int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
-                    int colour = 0, bool u16 = false)
+                    int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0)
 {
     if (check_dims(n, h, w)) return -1;
     if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
@@ -2909,12 +2915,15 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     const int s = uva_net_scale(n);
     const size_t bps = u16 ? 2 : 1;        // bytes per sample of the net's frames
     const size_t in_row = (size_t)w * 3 * bps, out_row = (size_t)w * s * 3 * bps;
+    const bool rs = rs_oh > 0 && rs_ow > 0 && !(rs_oh == h * s && rs_ow == w * s);
+    const int res_h = rs ? rs_oh : h * s, res_w = rs ? rs_ow : w * s;     // the frame that leaves
+    const size_t res_row = (size_t)res_w * 3 * bps, res_bytes = res_row * (size_t)res_h;
     if (png_ws) out_stride = out_row;
-    if (in_stride < in_row || out_stride < out_row) { fail("row stride too small"); return -1; }
+    if (in_stride < in_row || out_stride < res_row) { fail("row stride too small"); return -1; }
     const size_t in_bytes = in_row * h, out_bytes = out_row * (size_t)h * s;
     const int native = u16 ? PIX_BGR48LE : PIX_BGR24;
     const bool pin = in_fmt != native, pout = out_fmt != native;
-    const size_t pin_bytes = pix_frame_bytes(in_fmt, h, w), pout_bytes = pix_frame_bytes(out_fmt, h * s, w * s);
+    const size_t pin_bytes = pix_frame_bytes(in_fmt, h, w), pout_bytes = pix_frame_bytes(out_fmt, res_h, res_w);
     if (pout_bytes > (size_t)INT_MAX) { fail("result frame of 2 GB or more"); return -1; }
     uva_net::PipeSlot* free_slot = nullptr;
     for (auto& c : n->pipe)
@@ -2932,6 +2941,9 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     }
     if (grow_dev(&ps.d_in, &ps.d_in_cap, in_bytes) || grow_dev(&ps.d_out, &ps.d_out_cap, out_bytes)) return -1;
     if ((pin && grow_dev(&ps.d_pin, &ps.d_pin_cap, pin_bytes)) || (pout && grow_dev(&ps.d_pout, &ps.d_pout_cap, pout_bytes))) return -1;
+    if (rs && grow_dev(&ps.d_rs, &ps.d_rs_cap, res_bytes)) return -1;
+    const uint8_t* d_res = rs ? ps.d_rs : ps.d_out;                        // the BGR frame that leaves
+    std::string rs_err;
     if (png_ws) {
         if (uva_png_workspace_bytes(h * s, w * s) == 0) { fail("PNG encoder: frame width out of range"); return -1; }
         if (png_ws_bytes < png_workspace_bytes(h * s, w * s)) { fail("PNG workspace too small"); return -1; }
@@ -2958,12 +2970,14 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     if (u16) {
         if (pin && tryhip(launch_pix16_to_bgr(n->stream, in_fmt, colour, ps.d_pin, (uint16_t*)ps.d_in, h, w), "pix16_to_bgr")) return -1;
         if (uva_net_process_u16_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
-        if (pout && tryhip(launch_pix16_from_bgr(n->stream, out_fmt, colour, (const uint16_t*)ps.d_out, ps.d_pout, h * s, w * s), "pix16_from_bgr"))
+        if (rs && launch_resize(n->stream, n->device, ps.d_out, h * s, w * s, out_row, ps.d_rs, res_h, res_w, res_row, rs_filter, 16, &rs_err)) { fail(rs_err); return -1; }
+        if (pout && tryhip(launch_pix16_from_bgr(n->stream, out_fmt, colour, (const uint16_t*)d_res, ps.d_pout, res_h, res_w), "pix16_from_bgr"))
             return -1;
     } else {
         if (pin && tryhip(launch_pix_to_bgr(n->stream, in_fmt, colour, ps.d_pin, ps.d_in, h, w), "pix_to_bgr")) return -1;
         if (uva_net_process_u8_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
-        if (pout && tryhip(launch_pix_from_bgr(n->stream, out_fmt, colour, ps.d_out, ps.d_pout, h * s, w * s), "pix_from_bgr")) return -1;
+        if (rs && launch_resize(n->stream, n->device, ps.d_out, h * s, w * s, out_row, ps.d_rs, res_h, res_w, res_row, rs_filter, 8, &rs_err)) { fail(rs_err); return -1; }
+        if (pout && tryhip(launch_pix_from_bgr(n->stream, out_fmt, colour, d_res, ps.d_pout, res_h, res_w), "pix_from_bgr")) return -1;
     }
     // png: the deflate kernel follows the net on its stream and leaves the blocks in HBM, packed end to end by a second
     // (device-to-device) kernel: 0.15 ms per 4K frame together
@@ -2992,13 +3006,13 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     ps.png_ws = nullptr;
     // what comes down: the BGR rows of d_out, or the packed frame d_pout -- as "rows" of one byte, so that a band is a byte
     // range (collect copies it with one memcpy)
-    const uint8_t* d_src = pout ? ps.d_pout : ps.d_out;
-    const size_t dl_bytes = pout ? pout_bytes : out_bytes;
+    const uint8_t* d_src = pout ? ps.d_pout : d_res;
+    const size_t dl_bytes = pout ? pout_bytes : res_bytes;
     if (!is_pinned_host(out)) {
         if (grow_host(&ps.h_out, &ps.h_out_cap, dl_bytes)) return -1;
-        dst = ps.h_out; dst_stride = out_row;
-        ps.user_out = out; ps.user_out_stride = pout ? 1 : out_stride; ps.out_row = pout ? 1 : out_row;
-        ps.out_rows = pout ? (int)pout_bytes : h * s;
+        dst = ps.h_out; dst_stride = res_row;
+        ps.user_out = out; ps.user_out_stride = pout ? 1 : out_stride; ps.out_row = pout ? 1 : res_row;
+        ps.out_rows = pout ? (int)pout_bytes : res_h;
     }
     if (ps.user_out) {
         const int rows = ps.out_rows, per = (rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
@@ -3012,7 +3026,7 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
         }
     } else if (pout) {
         if (tryhip(hipMemcpyAsync(dst, d_src, dl_bytes, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return -1;
-    } else if (tryhip(hipMemcpy2DAsync(dst, dst_stride, ps.d_out, out_row, out_row, (size_t)h * s, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) {
+    } else if (tryhip(hipMemcpy2DAsync(dst, dst_stride, d_res, res_row, res_row, (size_t)res_h, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) {
         return -1;
     }
     if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return -1;
@@ -3136,6 +3150,104 @@ int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out
     HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// ---- the resampler (csrc/uva_resize.hip) ----------------------------------------------------------
+int uva_resize_taps(int n_in, int n_out, int filter, int32_t* first, int16_t* taps, size_t cap, int* ntaps)
+{
+    if (const char* e = resize_axis_error(n_in, n_out, filter)) return fail(e);
+    const int t = resize_ntaps(n_in, n_out, filter);
+    if (ntaps) *ntaps = t;
+    if (!first || !taps || cap < (size_t)n_out * t) return fail("uva_resize_taps: the table needs n_out firsts and n_out * ntaps taps");
+    std::vector<int32_t> f;
+    std::vector<int16_t> tp;
+    if (resize_build_taps(n_in, n_out, filter, f, tp) != t) return fail("uva_resize_taps: the taps of a row do not fit");
+    std::copy(f.begin(), f.end(), first);
+    std::copy(tp.begin(), tp.end(), taps);
+    return 0;
+}
+
+namespace {
+int resize_check(const void* in, int h, int w, size_t in_stride, const void* out, int oh, int ow, size_t out_stride, int filter, int bits)
+{
+    if (!in || !out) return fail("null frame pointer");
+    if (bits != 8 && bits != 16) return fail("resize: bits must be 8 or 16");
+    if (const char* e = resize_axis_error(h, oh, filter)) return fail(e);
+    if (const char* e = resize_axis_error(w, ow, filter)) return fail(e);
+    if ((long long)h * w > (1ll << 28) || (long long)oh * ow > (1ll << 28)) return fail("bad image size");
+    const size_t bps = bits / 8;
+    if (in_stride < (size_t)w * 3 * bps || out_stride < (size_t)ow * 3 * bps) return fail("row stride too small");
+    if (bits == 16 && ((((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 1) != 0)) return fail("16-bit frames need 2-byte aligned rows");
+    return 0;
+}
+}  // namespace
+
+int uva_resize_device(int device, const void* d_in, int h, int w, size_t in_stride, void* d_out, int oh, int ow, size_t out_stride,
+                      int filter, int bits, uva_net* after, uva_net* before)
+{
+    if (resize_check(d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits)) return 1;
+    for (uva_net* n : {after, before})
+        if (n) {
+            if (ensure_device(n)) return 1;
+            if (n->device != device) return fail("uva_resize_device: the net is on another device");
+        }
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    if (after) {
+        SyncEventScope ev(after);
+        if (!ev.e) return 1;
+        HIP_TRY(hipEventRecord(ev.e, after->stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, ev.e, 0));
+    }
+    std::string err;
+    if (launch_resize(c->stream, device, d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits, &err)) return fail(err);
+    if (before) {
+        SyncEventScope ev(before);
+        if (!ev.e) return 1;
+        HIP_TRY(hipEventRecord(ev.e, c->stream));
+        HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
+    }
+    return 0;
+}
+
+int uva_resize(int device, const void* in, int h, int w, size_t in_stride, void* out, int oh, int ow, size_t out_stride, int filter,
+               int bits)
+{
+    if (resize_check(in, h, w, in_stride, out, oh, ow, out_stride, filter, bits)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    // the frames go up and come down with their row padding, so that the kernel works on the caller's strides; a padded
+    // result buffer goes up first (what lies between its rows comes back as it was)
+    const size_t in_row = (size_t)w * 3 * (bits / 8), out_row = (size_t)ow * 3 * (bits / 8);
+    const size_t nin = in_stride * (size_t)(h - 1) + in_row, nout = out_stride * (size_t)(oh - 1) + out_row;
+    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
+    if (out_stride != out_row) HIP_TRY(hipMemcpyAsync(c->d_out, out, nout, hipMemcpyHostToDevice, c->stream));
+    std::string err;
+    if (launch_resize(c->stream, device, c->d_in, h, w, in_stride, c->d_out, oh, ow, out_stride, filter, bits, &err)) return fail(err);
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+long long uva_net_submit_pix_sized(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
+                                   int tile_size, int border, int oh, int ow, int filter, int bits)
+{
+    if (bits != 8 && bits != 16) { fail("uva_net_submit_pix_sized: bits must be 8 or 16"); return -1; }
+    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
+    if (bits == 8 && (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE)) { fail("bgr48le is a 16-bit format: it needs bits = 16"); return -1; }
+    if (!pix_colour_ok(colour)) { fail("bad colour word"); return -1; }
+    if (check_dims(n, h, w)) return -1;
+    if (bits == 16 && (ensure_device(n) || check_u16_net(n))) return -1;
+    const int s = uva_net_scale(n);
+    if (s <= 0) { fail("net has no graph"); return -1; }
+    if (const char* e = resize_axis_error(h * s, oh, filter)) { fail(e); return -1; }
+    if (const char* e = resize_axis_error(w * s, ow, filter)) { fail(e); return -1; }
+    const size_t bps = bits / 8;
+    return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3 * bps, (uint8_t*)out, (size_t)ow * 3 * bps, tile_size, border, nullptr, 0,
+                     in_fmt, out_fmt, colour, bits == 16, oh, ow, filter);
 }
 
 size_t uva_png_workspace_bytes(int h, int w)

@@ -128,6 +128,8 @@ COLOR_RANGES = {"tv": 0, "pc": 2}                                   # ffmpeg's -
 # names; H.264 / HEVC video is left, JPEG / MPEG-1 center, UHD BT.2020 material topleft)
 CHROMA_FILTERS = {"replicate": 0, "bilinear": 4}
 CHROMA_LOCS = {"left": 0, "center": 8, "topleft": 16}
+# the resampler's filters (include/uva.h UVA_RESIZE_*)
+RESIZE_FILTERS = {"lanczos": 0, "bicubic": 1, "bilinear": 2}
 
 
 def pix_frame_bytes(fmt, h, w):
@@ -197,6 +199,60 @@ def convert_pix(buf, h, w, in_fmt, out_fmt, colour="bt601", color_range="tv", ou
         raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, h, w))
     fn = _lib.load().uva_pix_convert16 if bit_depth == 16 else _lib.load().uva_pix_convert
     _lib.check(fn(int(gpu), src.ctypes.data, PIX_FORMATS_ALL[in_fmt], out.ctypes.data, PIX_FORMATS_ALL[out_fmt], h, w, cw))
+    return out
+
+
+def _resize_filter(name):
+    if name not in RESIZE_FILTERS:
+        raise ValueError("unknown resize filter %r (%s)" % (name, ", ".join(RESIZE_FILTERS)))
+    return RESIZE_FILTERS[name]
+
+
+def _resize_axis(n_in, n_out, what):
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("resize: %s must be at least 1 (%d -> %d)" % (what, n_in, n_out))
+    if n_out * 4 < n_in or n_out > n_in * 4:
+        raise ValueError("resize: %s %d -> %d is outside the ratios [1/4, 4]" % (what, n_in, n_out))
+
+
+def resize_taps(n_in, n_out, filter="lanczos"):
+    """The tap table of one axis as the library builds it on the host (include/uva.h uva_resize_taps; no GPU needed):
+    -> (first int32 [n_out], taps int16 [n_out][T]); output sample d is sum_k taps[d][k] * in[clamp(first[d] + k)] / 2^14."""
+    f = _resize_filter(filter)
+    _resize_axis(n_in, n_out, "axis")
+    L = _lib.load()
+    t = ctypes.c_int(0)
+    L.uva_resize_taps(int(n_in), int(n_out), f, None, None, 0, ctypes.byref(t))          # size query (fails by design)
+    if t.value <= 0:
+        raise _lib.UvaError(L.uva_last_error().decode(errors="replace"))
+    first = np.empty(int(n_out), np.int32)
+    taps = np.empty((int(n_out), t.value), np.int16)
+    _lib.check(L.uva_resize_taps(int(n_in), int(n_out), f, first.ctypes.data, taps.ctypes.data, taps.size, ctypes.byref(t)))
+    return first, taps
+
+
+def resize(img, size, filter="lanczos", gpu=0, out=None):
+    """A BGR frame, u8 or u16 [h][w][3], resampled to size = (oh, ow) on HIP device `gpu` (include/uva.h uva_resize; DESIGN.md
+    section 7.6): separable lanczos / bicubic / bilinear with an anti-aliasing support, per axis within the ratios [1/4, 4].
+    `img` and `out` may be row-padded views (last two axes contiguous); what lies between the rows of `out` is left alone."""
+    f = _resize_filter(filter)
+    a = np.asarray(img)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("frame must be u8 or u16 [h][w][3]")
+    if a.strides[2] != a.itemsize or a.strides[1] != 3 * a.itemsize or a.strides[0] < a.shape[1] * 3 * a.itemsize:
+        a = np.ascontiguousarray(a)
+    oh, ow = (int(v) for v in size)
+    h, w, _ = a.shape
+    _resize_axis(h, oh, "height")
+    _resize_axis(w, ow, "width")
+    if out is None:
+        out = np.empty((oh, ow, 3), a.dtype)
+    if (out.dtype != a.dtype or out.shape != (oh, ow, 3) or out.strides[2] != a.itemsize or out.strides[1] != 3 * a.itemsize
+            or out.strides[0] < ow * 3 * a.itemsize):
+        raise ValueError("out must be a %s [%d][%d][3] array with contiguous rows" % (a.dtype, oh, ow))
+    _lib.check(_lib.load().uva_resize(int(gpu), a.ctypes.data, h, w, a.strides[0], out.ctypes.data, oh, ow, out.strides[0], f,
+                                      8 * a.itemsize))
     return out
 
 
@@ -405,23 +461,37 @@ class Net:
         return Ticket(t, img, out)
 
     def submit_pix(self, buf, h, w, in_fmt, out=None, out_fmt="bgr24", colour="bt601", color_range="tv", tile_size=0, border=0,
-                   bit_depth=8, chroma_filter="replicate", chroma_loc="left"):
+                   bit_depth=8, chroma_filter="replicate", chroma_loc="left", out_size=None, resize_filter="lanczos"):
         """submit_u8 with a rawvideo pixel format on either end (include/uva.h uva_net_submit_pix): `buf` holds one dense
         h x w frame of in_fmt, the result is one dense (h*s) x (w*s) frame of out_fmt; both conversions run on the GPU around
         the net.  `out`: optional preallocated result buffer of pix_frame_bytes(out_fmt, h*s, w*s) bytes (pix_empty; pinned
         memory avoids the staging copy).  Returns a Ticket that collect_u8 takes.  bit_depth=16: the 16-bit route
         (uva_net_submit_pix16): the frame reaches the net as u16 BGR and leaves it as u16 BGR, no 8-bit hop.
-        chroma_filter="bilinear": both conversions interpolate chroma sited at chroma_loc."""
+        chroma_filter="bilinear": both conversions interpolate chroma sited at chroma_loc.
+        out_size=(oh, ow): the net's result is resampled to oh x ow with resize_filter between the net and the output
+        conversion (uva_net_submit_pix_sized); the result is then one dense oh x ow frame of out_fmt."""
         _bit_depth(bit_depth, (in_fmt, out_fmt))
         cw = colour_word(colour, color_range, chroma_filter, chroma_loc)
         s = self.scale
         if s <= 0:
             raise _lib.UvaError("net has no graph: load_param/load_model failed or were not called")
         src = _pix_frame(buf, in_fmt, h, w, "input")
+        rh, rw = h * s, w * s
+        if out_size is not None:
+            rf = _resize_filter(resize_filter)
+            rh, rw = (int(v) for v in out_size)
+            _resize_axis(h * s, rh, "height")
+            _resize_axis(w * s, rw, "width")
         if out is None:
-            out = pix_empty(out_fmt, h * s, w * s)
-        if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(out_fmt, h * s, w * s):
-            raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, h * s, w * s))
+            out = pix_empty(out_fmt, rh, rw)
+        if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(out_fmt, rh, rw):
+            raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(out_fmt, rh, rw))
+        if out_size is not None:
+            t = self._L.uva_net_submit_pix_sized(self._h, src.ctypes.data, PIX_FORMATS_ALL[in_fmt], h, w, out.ctypes.data,
+                                                 PIX_FORMATS_ALL[out_fmt], cw, int(tile_size), int(border), rh, rw, rf, int(bit_depth))
+            if t < 0:
+                raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
+            return Ticket(t, src, out)
         fn = self._L.uva_net_submit_pix16 if bit_depth == 16 else self._L.uva_net_submit_pix
         t = fn(self._h, src.ctypes.data, PIX_FORMATS_ALL[in_fmt], h, w, out.ctypes.data, PIX_FORMATS_ALL[out_fmt], cw, int(tile_size), int(border))
         if t < 0:
@@ -436,6 +506,15 @@ class Net:
                                                   PIX_FORMATS_ALL[out_fmt], h, w,
                                                   colour_word(colour, color_range, chroma_filter, chroma_loc),
                                                   after._h if after is not None else None, self._h))
+
+    def resize_device(self, d_in, h, w, d_out, oh, ow, filter="lanczos", bit_depth=8, after=None, in_stride=None, out_stride=None):
+        """The resampler on a BGR frame in HBM queued IN FRONT of this net (include/uva.h uva_resize_device), like
+        convert_pix_device: `after` (a net, or None) comes first, this net's next work waits for the frame.  Raw device
+        pointers (ints); strides in bytes (default: dense rows)."""
+        bps = bit_depth // 8
+        _lib.check(self._L.uva_resize_device(self.device_index, ctypes.c_void_p(d_in), h, w, in_stride or w * 3 * bps, ctypes.c_void_p(d_out),
+                                             oh, ow, out_stride or ow * 3 * bps, _resize_filter(filter), int(bit_depth),
+                                             after._h if after is not None else None, self._h))
 
     def collect_u8(self, ticket):
         """Waits for the frame of `ticket` and returns its u8 result array (submit_u8, submit_pix) or its PNG workspace

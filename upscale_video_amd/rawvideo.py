@@ -25,6 +25,15 @@ sees no 2x2 colour steps to sharpen, and colour stays registered with luma.  --c
 chroma_sample_location): left (default) for video from H.264 / HEVC, center for JPEG / MPEG-1 material, topleft for UHD
 BT.2020 material.  The default, replicate, keeps the earlier releases' bytes.
 
+--out-size WxH (or --out-scale F, the total scale relative to the input frame, as Real-ESRGAN's --outscale) resamples the net's
+2x / 4x result to the size asked for on the GPU, between the net and the output conversion (DESIGN.md section 7.6;
+--resize-filter lanczos|bicubic|bilinear), so that no `-vf scale=` pass over 4K frames is left to the ffmpeg behind the pipe
+and the pipe carries frames of the final size:
+
+    ffmpeg -i in.mkv -f rawvideo -pix_fmt yuv420p - \\
+      | python -m upscale_video_amd.rawvideo -W 1280 -H 720 -s 2 --out-size 2560x1440 --in-pix-fmt yuv420p --out-pix-fmt p010le \\
+      | ffmpeg -f rawvideo -pix_fmt p010le -s 2560x1440 -r 24 -i - -c:v libx265 out.mkv
+
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
 conversions run on the net's stream around its kernels); nets in between pass u8 BGR.  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
@@ -73,7 +82,7 @@ class PixFormats:
     """the raw-video formats of a stream's two ends and the colour arithmetic between them (ncnn.PIX_FORMATS_ALL etc.)"""
 
     def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv", bit_depth=8, chroma_filter="replicate",
-                 chroma_loc="left"):
+                 chroma_loc="left", out_size=None, resize_filter="lanczos"):
         for f in (in_fmt, out_fmt):
             if f not in ncnn.PIX_FORMATS_ALL:
                 raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(ncnn.PIX_FORMATS_ALL)))
@@ -86,6 +95,13 @@ class PixFormats:
         self.chroma_filter, self.chroma_loc = chroma_filter, chroma_loc
         self.in_fmt, self.out_fmt, self.colour, self.color_range = in_fmt, out_fmt, colour, color_range
         self.bit_depth = bit_depth     # 16: the net runs on u16 BGR, no 8-bit hop at either end
+        if resize_filter not in ncnn.RESIZE_FILTERS:
+            raise ValueError("unknown resize filter %r (%s)" % (resize_filter, ", ".join(ncnn.RESIZE_FILTERS)))
+        if out_size is not None and (len(out_size) != 2 or min(out_size) < 1):
+            raise ValueError("out_size must be (height, width), both at least 1")
+        # (oh, ow): a lane's last stage resamples its result to this size; None: the nets' own size
+        self.out_size = None if out_size is None else (int(out_size[0]), int(out_size[1]))
+        self.resize_filter = resize_filter
 
     def depth_kw(self):
         """the keyword the 16-bit calls take (none at 8 bits: those calls are the first pixel-format release's)"""
@@ -96,6 +112,19 @@ class PixFormats:
         if self.chroma_filter == "replicate":
             return {}
         return {"chroma_filter": self.chroma_filter, "chroma_loc": self.chroma_loc}
+
+    def resize_kw(self):
+        """the keywords of the resampler (none without an output size: those calls are the earlier releases')"""
+        if self.out_size is None:
+            return {}
+        kw = {"out_size": self.out_size}
+        if self.resize_filter != "lanczos":
+            kw["resize_filter"] = self.resize_filter
+        return kw
+
+    def result_size(self, h, w):
+        """the size of the frames that leave a lane whose nets produce h x w"""
+        return self.out_size if self.out_size is not None else (h, w)
 
     def frame_bytes(self, h, w, out=False):
         return ncnn.pix_frame_bytes(self.out_fmt if out else self.in_fmt, h, w)
@@ -131,15 +160,18 @@ def read_exact(f, view):
 class Stage:
     """One net with its own ring of page-locked result buffers and up to PIPE_DEPTH frames in flight."""
 
-    def __init__(self, net, h, w, tile_size, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR):
+    def __init__(self, net, h, w, tile_size, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR, resize=False):
         self.net, self.tile = net, tile_size
         self.h, self.w, self.in_fmt, self.out_fmt, self.pix = h, w, in_fmt, out_fmt, pix
         s = net.scale
+        # resize: the lane's last stage, whose result is resampled to pix.out_size behind the net (Net.submit_pix(out_size=...))
+        self.resize_kw = pix.resize_kw() if resize else {}
+        oh, ow = pix.result_size(h * s, w * s) if resize else (h * s, w * s)
         # A result buffer stays in use while its frame is in flight here (<= depth frames) and then
         # while the consumer holds it -- the next stage reads it as pinned input until that stage's
         # collect (<= depth frames), or the writer thread (queue of 2 + 1 being written).  Frames stay
         # in order, so 2*depth + 2 buffers can never wrap onto a live one.
-        self.outs = [ncnn.pix_empty(out_fmt, h * s, w * s, alloc) for _ in range(2 * PIPE_DEPTH + 2)]
+        self.outs = [ncnn.pix_empty(out_fmt, oh, ow, alloc) for _ in range(2 * PIPE_DEPTH + 2)]
         self.n = 0
         self.inflight = []
 
@@ -150,13 +182,13 @@ class Stage:
         out = self.outs[self.n % len(self.outs)]
         self.n += 1
         border = TILE_BORDER if self.tile else 0
-        if self.in_fmt == self.out_fmt == "bgr24" and self.pix.bit_depth == 8:
+        if self.in_fmt == self.out_fmt == "bgr24" and self.pix.bit_depth == 8 and not self.resize_kw:
             self.inflight.append(self.net.submit_u8(frame, out=out, tile_size=self.tile, border=border))
         else:
             self.inflight.append(self.net.submit_pix(frame, self.h, self.w, self.in_fmt, out=out, out_fmt=self.out_fmt,
                                                      colour=self.pix.colour, color_range=self.pix.color_range,
                                                      tile_size=self.tile, border=border, **self.pix.depth_kw(),
-                                                     **self.pix.chroma_kw()))
+                                                     **self.pix.chroma_kw(), **self.resize_kw))
 
     def collect(self):
         return self.net.collect_u8(self.inflight.pop(0))
@@ -216,9 +248,12 @@ class Lane:
             # the first stage takes the stream's input format, the last one produces its output format, u8 BGR in between
             fmts = dict(in_fmt=pix.in_fmt if k == 0 else "bgr24", out_fmt=pix.out_fmt if k == last else "bgr24", pix=pix)
             if isinstance(net, tuple):         # ("denoise", gpu, K): the `-m n=K` stage
+                if k == last and pix.out_size is not None:
+                    raise ValueError("--out-size / --out-scale: the resampler sits behind a net, and this lane ends in the denoise "
+                                     "stage (-s 1 -m n=K): add -m a or -s 2|4, or resize the denoised frames in a second run")
                 self.stages.append(DenoiseStage(net[1], net[2], h, w, alloc, **fmts))
                 continue
-            self.stages.append(Stage(net, h, w, tile, alloc, **fmts))
+            self.stages.append(Stage(net, h, w, tile, alloc, **fmts, **({"resize": True} if k == last and pix.out_size is not None else {})))
             h, w = h * net.scale, w * net.scale
         self.count = 0                         # frames inside
 
@@ -445,7 +480,7 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
     full-size file of zeros and holes is worse than none).  pix: PixFormats of the two ends (default bgr24).  Returns the number
     of frames written."""
     pix = pix or BGR
-    fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(h * scale_total, w * scale_total, out=True)
+    fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(*pix.result_size(h * scale_total, w * scale_total), out=True)
     nl = len(lanes_spec)
     ins = list(in_path) if isinstance(in_path, (list, tuple)) else None
     outs = list(out_path) if isinstance(out_path, (list, tuple)) else None
@@ -631,8 +666,11 @@ class PipeSink:
 def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
     """`-s 1` without `-m a`: the reference renames the frames, nothing is computed (:924-929).  Formats that differ at the two
     ends (pix): every frame is converted once on HIP device `gpu` (include/uva.h uva_pix_convert; with pix.bit_depth 16
-    uva_pix_convert16, through u16 BGR)."""
+    uva_pix_convert16, through u16 BGR).  With pix.out_size every frame is converted to BGR, resampled (include/uva.h uva_resize)
+    and converted to the output format at the new size."""
     pix = pix or BGR
+    if pix.out_size is not None and pix.out_size != (h, w):
+        return _copy_through_sized(fin, fout, h, w, max_frames, pix, gpu)
     buf = bytearray(pix.frame_bytes(h, w))
     res = ncnn.pix_empty(pix.out_fmt, h, w) if pix.in_fmt != pix.out_fmt else None
     n = 0
@@ -648,6 +686,34 @@ def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
         n += 1
     fout.flush()
     return n
+
+
+def _copy_through_sized(fin, fout, h, w, max_frames, pix, gpu):
+    """copy_through with a resampler: in_fmt -> BGR (u8, or u16 at 16 bits) -> pix.out_size -> out_fmt, synchronous calls"""
+    oh, ow = pix.out_size
+    native = "bgr48le" if pix.bit_depth == 16 else "bgr24"
+    kw = dict(colour=pix.colour, color_range=pix.color_range, gpu=gpu, **pix.depth_kw(), **pix.chroma_kw())
+    buf = ncnn.pix_empty(pix.in_fmt, h, w)
+    small = ncnn.pix_empty(native, h, w)
+    big = ncnn.pix_empty(native, oh, ow)
+    res = ncnn.pix_empty(pix.out_fmt, oh, ow)
+    n = 0
+    while max_frames is None or n < max_frames:
+        if not read_exact(fin, memoryview(buf).cast("B")):
+            break
+        bgr = buf if pix.in_fmt == native else ncnn.convert_pix(buf, h, w, pix.in_fmt, native, out=small, **kw)
+        ncnn.resize(bgr, (oh, ow), pix.resize_filter, gpu=gpu, out=big)
+        done = big if pix.out_fmt == native else ncnn.convert_pix(big, oh, ow, native, pix.out_fmt, out=res, **kw)
+        fout.write(memoryview(done).cast("B"))
+        n += 1
+    fout.flush()
+    return n
+
+
+def out_scale_size(h, w, f):
+    """--out-scale F at an h x w input: per axis 2 floor(n F / 2 + 0.5), at least 2 (even sizes: 4:2:0 formats, encoders)"""
+    import math
+    return tuple(max(2, 2 * int(math.floor(n * f / 2 + 0.5))) for n in (h, w))
 
 
 def main(argv=None):
@@ -690,15 +756,46 @@ def main(argv=None):
     ap.add_argument("--chroma-loc", default=None, choices=list(ncnn.CHROMA_LOCS),
                     help="with --chroma-filter bilinear: where the chroma samples sit (ffmpeg's chroma_sample_location).  left "
                          "(default): video from H.264 / HEVC; center: JPEG / MPEG-1; topleft: UHD BT.2020 material")
+    ap.add_argument("--out-size", default=None, metavar="WxH",
+                    help="resample the result to this size on the GPU, behind the net and in front of the output conversion "
+                         "(e.g. -s 2 --out-size 2560x1440 at 720p input; each axis within [1/4, 4] of the net's result; DESIGN.md "
+                         "section 7.6)")
+    ap.add_argument("--out-scale", type=float, default=None, metavar="F",
+                    help="the same, as the total scale relative to the INPUT frame (Real-ESRGAN's --outscale): per axis "
+                         "2 floor(n F / 2 + 0.5), at least 2; not together with --out-size")
+    ap.add_argument("--resize-filter", default="lanczos", choices=list(ncnn.RESIZE_FILTERS),
+                    help="the resampler's filter (default lanczos: sinc(x) sinc(x/3); bicubic: Keys, a = -0.5; bilinear); widened when "
+                         "an axis shrinks")
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
+    out_size = None
+    if a.out_size is not None and a.out_scale is not None:
+        ap.error("--out-size and --out-scale exclude each other")
+    if a.out_size is not None:
+        import re
+        m = re.fullmatch(r"(\d+)[xX](\d+)", a.out_size.strip())
+        if not m or int(m.group(1)) < 1 or int(m.group(2)) < 1:
+            ap.error("--out-size takes WIDTHxHEIGHT, both at least 1 (e.g. 2560x1440), not %r" % a.out_size)
+        out_size = (int(m.group(2)), int(m.group(1)))
+    elif a.out_scale is not None:
+        if not a.out_scale > 0 or a.out_scale != a.out_scale or a.out_scale == float("inf"):
+            ap.error("--out-scale takes a positive number")
+        out_size = out_scale_size(a.height, a.width, a.out_scale)
+    if out_size is not None:
+        flag = "--out-size" if a.out_size is not None else "--out-scale"
+        for n_out, n_net, what in ((out_size[0], a.height * a.scale, "height"), (out_size[1], a.width * a.scale, "width")):
+            if n_out * 4 < n_net or n_out > n_net * 4:
+                ap.error("%s: %s %d is outside [1/4, 4] of the net's result (%d with -s %d)" % (flag, what, n_out, n_net, a.scale))
+        if out_size == (a.height * a.scale, a.width * a.scale):
+            out_size = None                     # the nets' own size: nothing to resample, today's calls
     for f in (a.in_pix_fmt, a.out_pix_fmt):
         if f in ncnn.PIX16_ONLY and a.bit_depth != 16:
             ap.error("%s is a 16-bit format: it needs --bit-depth 16" % f)
     if a.chroma_loc is not None and a.chroma_filter != "bilinear":
         ap.error("--chroma-loc needs --chroma-filter bilinear: replicate knows no siting")
-    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range, a.bit_depth, a.chroma_filter, a.chroma_loc or "left")
+    pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range, a.bit_depth, a.chroma_filter, a.chroma_loc or "left",
+                     out_size, a.resize_filter)
     # upscale_video.py -m: a (anime pass), n=K (film-grain denoise, K = 1..30, :782-789), r (the x_Valar_v1 model instead of
     # x_Compact_Pretrain, :913-916); the reference runs them in the order n, a, upscale (:880-920) whatever the order given
     models = [m for m in a.models.split(",") if m]
@@ -715,6 +812,9 @@ def main(argv=None):
             ap.error("unknown model option %r (a, n=K, r)" % m)
     if models and a.bit_depth == 16:
         ap.error("--bit-depth 16 takes the 2x and 4x Compact nets only: -m a, -m n=K and -m r run at 8 bits (-m %s)" % a.models)
+    if out_size is not None and a.scale == 1 and denoise is not None and "a" not in models:
+        ap.error("--out-size / --out-scale: the resampler sits behind a net, and -s 1 -m n=K ends in the denoise stage: add -m a or "
+                 "-s 2|4")
     final_stem = MODEL_FILES[a.scale]
     if "r" in models:
         if a.scale != 4:
