@@ -139,6 +139,10 @@ void uva_host_free(void* p);
  *   UVA_PIX_P010LE   nv12's layout in little-endian 16-bit words, value << 6        2 (wh + 2 cw ch)
  *   UVA_PIX_YUV420P10LE  yuv420p's layout in little-endian 16-bit words, the value in the low 10 bits   2 (wh + 2 cw ch)
  *   UVA_PIX_BGR48LE  u16 [h][w][3], unorm16 (what the _u16 calls take; the 16-bit entries only)  6wh
+ *   UVA_PIX_YUV422P  Y u8 [h][w], then U [h][cw], then V [h][cw]: 4:2:2, one chroma row per luma row   wh + 2 cw h
+ *   UVA_PIX_YUV422P10LE  yuv422p's layout in little-endian 16-bit words, the value in the low 10 bits   2 (wh + 2 cw h)
+ * The two 4:2:2 formats resample chroma along the row alone: the pair's average / replication, or with
+ * UVA_CHROMA_BILINEAR the horizontal half of the siting's filters (left and topleft then give the same bytes).
  * colour = UVA_CSP_BT601 or UVA_CSP_BT709, | UVA_RANGE_FULL for full ("pc") range instead of limited ("tv": Y 16-235,
  * C 16-240, x4 at 10 bits).  BGR -> Y'CbCr: fixed-point textbook formulas, chroma of a 2x2 block from the block's sums;
  * Y'CbCr -> BGR: chroma replicated over its 2x2 block.  The reference's frames are untagged rgb24 PNGs, which ffmpeg merges
@@ -154,6 +158,8 @@ void uva_host_free(void* p);
 #define UVA_PIX_P010LE 3
 #define UVA_PIX_YUV420P10LE 5   /* (4 is not assigned) */
 #define UVA_PIX_BGR48LE 6
+#define UVA_PIX_YUV422P 7
+#define UVA_PIX_YUV422P10LE 8
 #define UVA_CSP_BT601 0
 #define UVA_CSP_BT709 1
 #define UVA_RANGE_FULL 2

@@ -1,8 +1,8 @@
 """Rate of the rawvideo streamer (python -m upscale_video_amd.rawvideo -s 2) at 1080p -> 2x per pair of pixel formats
 (--in-pix-fmt / --out-pix-fmt), file -> /dev/null and pipe -> pipe, frames held in /dev/shm: whole process wall time minus
 the wall time of a 1-frame run (interpreter start, model load, first-use allocations), as tools/rawvideo_bench.py.
-Argument: frames (default 600).  --formats in:out[,in:out...] picks the rows; --chroma-filter / --chroma-loc go to the streamer
-(DESIGN.md section 7.5)."""
+Argument: frames (default 600).  --formats in:out[,in:out...] picks the rows; --chroma-filter / --chroma-loc / --bit-depth go to
+the streamer (DESIGN.md sections 7.4, 7.5)."""
 import argparse
 import os
 import subprocess
@@ -19,6 +19,7 @@ ap.add_argument("frames", nargs="?", type=int, default=600)
 ap.add_argument("--formats", default="bgr24:bgr24,yuv420p:yuv420p,yuv420p:p010le")
 ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS))
 ap.add_argument("--chroma-loc", default="left", choices=list(ncnn.CHROMA_LOCS))
+ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16])
 a = ap.parse_args()
 N = a.frames
 h, w = 1080, 1920
@@ -34,6 +35,9 @@ def wall(cmd, shell=False):
     return time.perf_counter() - t0
 
 
+if a.bit_depth == 16:
+    base += ["--bit-depth", "16"]
+    print("bit depth 16", flush=True)
 fr = [synthetic_frame(h, w, seed=i) for i in range(4)]
 for fin, fout in (tuple(x.split(":")) for x in a.formats.split(",")):
     src = "/dev/shm/uva_in.%s" % fin
@@ -45,9 +49,9 @@ for fin, fout in (tuple(x.split(":")) for x in a.formats.split(",")):
     t1 = wall(base + fmts + ["-i", src, "-o", "/dev/null", "--frames", "1"])
     tn = wall(base + fmts + ["-i", src, "-o", "/dev/null"])
     mb = (ncnn.pix_frame_bytes(fin, h, w) + ncnn.pix_frame_bytes(fout, 2 * h, 2 * w)) / 1e6
-    print(f"{fin:8s} -> {fout:8s} ({mb:5.1f} MB/frame) file -> /dev/null : {N} frames in {tn:6.2f} s (start-up {t1:5.2f} s) = "
+    print(f"{fin:11s} -> {fout:11s} ({mb:5.1f} MB/frame) file -> /dev/null : {N} frames in {tn:6.2f} s (start-up {t1:5.2f} s) = "
           f"{(N - 1) / (tn - t1):7.1f} frames/s", flush=True)
     tn = wall(f"cat {src} | {' '.join(base + fmts)} 2>/dev/null | cat > /dev/null", shell=True)
-    print(f"{fin:8s} -> {fout:8s} ({mb:5.1f} MB/frame) pipe -> pipe      : {N} frames in {tn:6.2f} s = {(N - 1) / (tn - t1):7.1f} frames/s",
+    print(f"{fin:11s} -> {fout:11s} ({mb:5.1f} MB/frame) pipe -> pipe      : {N} frames in {tn:6.2f} s = {(N - 1) / (tn - t1):7.1f} frames/s",
           flush=True)
     os.remove(src)

@@ -7,6 +7,8 @@
 //   p010le   nv12's layout in 16-bit little-endian words, the 10-bit value in the high bits (v << 6)
 //   yuv420p10le  yuv420p's layout in 16-bit little-endian words, the 10-bit value in the low bits
 //   bgr48le  [h][w][3] u16 (unorm16): the 16-bit route's BGR (section 7.4)
+//   yuv422p  Y [h][w] u8, then U [h][cw], then V [h][cw]: one chroma row per luma row (section 7.7)
+//   yuv422p10le  yuv422p's layout in 16-bit little-endian words, the 10-bit value in the low bits
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -14,7 +16,8 @@
 
 namespace uva {
 
-enum { PIX_BGR24 = 0, PIX_YUV420P = 1, PIX_NV12 = 2, PIX_P010LE = 3, PIX_YUV420P10LE = 5, PIX_BGR48LE = 6, PIX_NFMT = 7 };   // (4: never assigned)
+enum { PIX_BGR24 = 0, PIX_YUV420P = 1, PIX_NV12 = 2, PIX_P010LE = 3, PIX_YUV420P10LE = 5, PIX_BGR48LE = 6, PIX_YUV422P = 7,
+       PIX_YUV422P10LE = 8, PIX_NFMT = 9 };   // (4: never assigned)
 // colour word: matrix in bit 0 (0 BT.601, 1 BT.709), bit 1 set = full ("pc") range, clear = limited ("tv") range; bit 2 set =
 // chroma interpolated for its siting instead of replicated / box-averaged, the siting in bits 3 and 4
 // (neither: left, as H.264 / HEVC video; bit 3: center; bit 4: topleft)

@@ -7,6 +7,7 @@
 // chroma sited left, center or topleft (section 7.5).
 // Both families are templated on the BGR sample type S: u8, or u16 (unorm16) for the 16-bit route (section 7.4).  Beside them
 //   pix_widen / pix_narrow  u8 BGR <-> u16 BGR (v * 257, rint(v / 257))
+// yuv422p / yuv422p10le (section 7.7) have twin kernels of their own, pix422_from_bgr / pix422_to_bgr, further down.
 // One thread covers 8 pixels of two rows -- a 2x2 block per chroma sample, so every chroma sample is read or written once.  Both
 // are memory-bound: with w % 8 == 0 (and 16-byte aligned bases) a thread's bytes move as 8- and 16-byte accesses, lanes side by
 // side along the row; elsewhere (odd sizes, the frame's right / bottom edge) byte by byte with bounds checks.
@@ -548,6 +549,261 @@ __global__ __launch_bounds__(BX * BY) void pix_to_bgr(const uint8_t* __restrict_
     }
 }
 
+// ---- 4:2:2: yuv422p, yuv422p10le ---------------------------------------------------------------
+// One chroma row per luma row, so the vertical axis is the identity and a thread covers 8 pixels of ONE row: 8 luma and 4
+// chroma samples per plane, every one read or written once.  HM is the horizontal chroma mode: 0 replicates / averages the
+// pair, 1 is co-sited (`left` and `topleft`: the same bytes), 2 centred.  W16: the planes hold 16-bit words, the 10-bit value
+// in the low bits.  Fixed point and coefficients are sections 7.3 / 7.4's; the interpolating modes' sums go unrounded into
+// the matrix (section 7.5).  int32 everywhere but the u16 inverse of HM 1 / 2, whose sums (section 7.4's 2^13 scale times 2
+// or 4) need int64; the u16 forward sums are at most section 7.4's 2x2 sum, which its 2^19 scale was sized for.
+template <typename S, int HM> struct Acc422 { typedef int type; };
+template <> struct Acc422<uint16_t, 1> { typedef long long type; };
+template <> struct Acc422<uint16_t, 2> { typedef long long type; };
+
+// BGR row `line`, pixels x0 .. x0 + 7 (clamped into the row) -> b[1..8], g[1..8], r[1..8]; LEFT: pixel x0 - 1 (clamped) -> [0]
+template <typename S, bool LEFT>
+__device__ __forceinline__ void bgr422_row(const S* __restrict__ line, int x0, int w, bool whole, int* b, int* g, int* r)
+{
+    if (LEFT) {
+        const S* l = line + 3 * (size_t)max(x0 - 1, 0);
+        b[0] = l[0]; g[0] = l[1]; r[0] = l[2];
+    }
+    if (whole) {
+        const S* row = line + 3 * (size_t)x0;
+        if constexpr (sizeof(S) == 1) {
+            uint32_t d[6];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const uint2 v = reinterpret_cast<const uint2*>(row)[q];
+                d[2 * q] = v.x; d[2 * q + 1] = v.y;
+            }
+#pragma unroll
+            for (int i = 0; i < PX; ++i) { b[i + 1] = byte_of(d, 3 * i); g[i + 1] = byte_of(d, 3 * i + 1); r[i + 1] = byte_of(d, 3 * i + 2); }
+        } else {
+            uint32_t d[12];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const uint4 v = reinterpret_cast<const uint4*>(row)[q];
+                d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+            }
+#pragma unroll
+            for (int i = 0; i < PX; ++i) { b[i + 1] = half_of(d, 3 * i); g[i + 1] = half_of(d, 3 * i + 1); r[i + 1] = half_of(d, 3 * i + 2); }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < PX; ++i) {
+            const S* p = line + 3 * (size_t)min(x0 + i, w - 1);
+            b[i + 1] = p[0]; g[i + 1] = p[1]; r[i + 1] = p[2];
+        }
+    }
+}
+
+// BGR [h][w][3] of S -> Y [h][w], U [h][cw], V [h][cw]
+template <bool W16, bool VEC, typename S, int HM>
+__global__ __launch_bounds__(BX * BY) void pix422_from_bgr(const S* __restrict__ bgr, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
+                                                            uint8_t* __restrict__ vp, int h, int w, FwdCoef c)
+{
+    constexpr int SH = sizeof(S) == 1 ? 16 : FWD16_SH;
+    const int x0 = (blockIdx.x * BX + threadIdx.x) * PX, y = blockIdx.y * BY + threadIdx.y;
+    if (x0 >= w || y >= h) return;
+    const int cw = (w + 1) >> 1, cx0 = x0 >> 1;
+    const bool whole = VEC && x0 + PX <= w;
+    int r[PX + 1], g[PX + 1], b[PX + 1];        // [0]: the pixel left of the eight (HM 1 alone)
+    bgr422_row<S, HM == 1>(bgr + (size_t)y * w * 3, x0, w, whole, b, g, r);
+    int yv[PX];
+#pragma unroll
+    for (int i = 0; i < PX; ++i)
+        yv[i] = clampi((c.yr * r[i + 1] + c.yg * g[i + 1] + c.yb * b[i + 1] + (c.yoff << SH) + (1 << (SH - 1))) >> SH, c.maxv);
+    const size_t o = (size_t)y * w + x0;
+    if (W16) {
+        uint16_t* dst = reinterpret_cast<uint16_t*>(yp) + o;
+        if (whole) {
+            reinterpret_cast<uint4*>(dst)[0] = make_uint4(pack2(yv[0], yv[1]), pack2(yv[2], yv[3]), pack2(yv[4], yv[5]), pack2(yv[6], yv[7]));
+        } else {
+#pragma unroll
+            for (int i = 0; i < PX; ++i)
+                if (x0 + i < w) dst[i] = (uint16_t)yv[i];
+        }
+    } else {
+        uint8_t* dst = yp + o;
+        if (whole) {
+            reinterpret_cast<uint2*>(dst)[0] = make_uint2(pack4(yv[0], yv[1], yv[2], yv[3]), pack4(yv[4], yv[5], yv[6], yv[7]));
+        } else {
+#pragma unroll
+            for (int i = 0; i < PX; ++i)
+                if (x0 + i < w) dst[i] = (uint8_t)yv[i];
+        }
+    }
+    // chroma sample j from pixels 2j, 2j + 1 (HM 0: one pixel at an odd right edge; HM 2: [1 1]) or 2j - 1, 2j, 2j + 1 ([1 2 1])
+    int cu[PX / 2], cv[PX / 2];
+#pragma unroll
+    for (int j = 0; j < PX / 2; ++j) {
+        int sr, sg, sb, s;
+        if (HM == 1) {
+            sr = r[2 * j] + 2 * r[2 * j + 1] + r[2 * j + 2]; sg = g[2 * j] + 2 * g[2 * j + 1] + g[2 * j + 2];
+            sb = b[2 * j] + 2 * b[2 * j + 1] + b[2 * j + 2];
+            s = SH + 2;
+        } else if (HM == 2) {
+            sr = r[2 * j + 1] + r[2 * j + 2]; sg = g[2 * j + 1] + g[2 * j + 2]; sb = b[2 * j + 1] + b[2 * j + 2];
+            s = SH + 1;
+        } else {
+            const bool two = x0 + 2 * j + 1 < w;
+            sr = r[2 * j + 1] + (two ? r[2 * j + 2] : 0); sg = g[2 * j + 1] + (two ? g[2 * j + 2] : 0);
+            sb = b[2 * j + 1] + (two ? b[2 * j + 2] : 0);
+            s = SH + (two ? 1 : 0);
+        }
+        cu[j] = clampi((c.ur * sr + c.ug * sg + c.ub * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
+        cv[j] = clampi((c.vr * sr + c.vg * sg + c.vb * sb + (c.coff << s) + (1 << (s - 1))) >> s, c.maxv);
+    }
+    const size_t co = (size_t)y * cw + cx0;
+    if (W16) {
+        uint16_t* du = reinterpret_cast<uint16_t*>(up) + co;
+        uint16_t* dv = reinterpret_cast<uint16_t*>(vp) + co;
+        if (whole) {
+            reinterpret_cast<uint2*>(du)[0] = make_uint2(pack2(cu[0], cu[1]), pack2(cu[2], cu[3]));
+            reinterpret_cast<uint2*>(dv)[0] = make_uint2(pack2(cv[0], cv[1]), pack2(cv[2], cv[3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j)
+                if (cx0 + j < cw) { du[j] = (uint16_t)cu[j]; dv[j] = (uint16_t)cv[j]; }
+        }
+    } else {
+        uint8_t* du = up + co;
+        uint8_t* dv = vp + co;
+        if (whole) {
+            reinterpret_cast<uint32_t*>(du)[0] = pack4(cu[0], cu[1], cu[2], cu[3]);
+            reinterpret_cast<uint32_t*>(dv)[0] = pack4(cv[0], cv[1], cv[2], cv[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j)
+                if (cx0 + j < cw) { du[j] = (uint8_t)cu[j]; dv[j] = (uint8_t)cv[j]; }
+        }
+    }
+}
+
+// one sample of a chroma plane row (cx inside the row)
+template <bool W16> __device__ __forceinline__ int chroma422_at(const uint8_t* __restrict__ row, int cx)
+{
+    return W16 ? reinterpret_cast<const uint16_t*>(row)[cx] & 1023 : row[cx];
+}
+
+// Y [h][w], U [h][cw], V [h][cw] -> BGR [h][w][3] of S
+template <bool W16, bool VEC, typename S, int HM>
+__global__ __launch_bounds__(BX * BY) void pix422_to_bgr(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
+                                                          const uint8_t* __restrict__ vp, S* __restrict__ bgr, int h, int w, InvCoef c)
+{
+    constexpr int SH = sizeof(S) == 1 ? 16 : INV16_SH;
+    constexpr int VMAX = sizeof(S) == 1 ? 255 : 65535;
+    const int x0 = (blockIdx.x * BX + threadIdx.x) * PX, y = blockIdx.y * BY + threadIdx.y;
+    if (x0 >= w || y >= h) return;
+    const int cw = (w + 1) >> 1, cx0 = x0 >> 1;
+    const bool whole = VEC && x0 + PX <= w;
+    // chroma samples cx0 .. cx0 + 3 -> [1..4] (clamped into the row); the neighbours the mode taps, each one clamped load:
+    // cx0 - 1 -> [0] (HM 2), cx0 + 4 -> [5] (HM 1, 2)
+    int nu[PX / 2 + 2], nv[PX / 2 + 2];
+    const uint8_t* ur = up + (size_t)y * cw * (W16 ? 2 : 1);
+    const uint8_t* vr = vp + (size_t)y * cw * (W16 ? 2 : 1);
+    if (whole) {
+        if (W16) {
+            const uint2 qu = *reinterpret_cast<const uint2*>(ur + 2 * cx0), qv = *reinterpret_cast<const uint2*>(vr + 2 * cx0);
+            const uint32_t du[2] = {qu.x, qu.y}, dv[2] = {qv.x, qv.y};
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j) { nu[j + 1] = half_of(du, j) & 1023; nv[j + 1] = half_of(dv, j) & 1023; }
+        } else {
+            const uint32_t du = *reinterpret_cast<const uint32_t*>(ur + cx0), dv = *reinterpret_cast<const uint32_t*>(vr + cx0);
+#pragma unroll
+            for (int j = 0; j < PX / 2; ++j) { nu[j + 1] = byte_of(&du, j); nv[j + 1] = byte_of(&dv, j); }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < PX / 2; ++j) {
+            const int cx = min(cx0 + j, cw - 1);
+            nu[j + 1] = chroma422_at<W16>(ur, cx); nv[j + 1] = chroma422_at<W16>(vr, cx);
+        }
+    }
+    if (HM == 2) { const int cx = max(cx0 - 1, 0); nu[0] = chroma422_at<W16>(ur, cx); nv[0] = chroma422_at<W16>(vr, cx); }
+    if (HM != 0) { const int cx = min(cx0 + PX / 2, cw - 1); nu[PX / 2 + 1] = chroma422_at<W16>(ur, cx); nv[PX / 2 + 1] = chroma422_at<W16>(vr, cx); }
+    const size_t o = (size_t)y * w + x0;
+    int yv[PX];
+    if (W16) {
+        const uint16_t* s = reinterpret_cast<const uint16_t*>(yp) + o;
+        if (whole) {
+            const uint4 v = reinterpret_cast<const uint4*>(s)[0];
+            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < PX; ++i) yv[i] = half_of(d, i) & 1023;
+        } else {
+#pragma unroll
+            for (int i = 0; i < PX; ++i) yv[i] = x0 + i < w ? s[i] & 1023 : 0;
+        }
+    } else {
+        const uint8_t* s = yp + o;
+        if (whole) {
+            const uint2 v = reinterpret_cast<const uint2*>(s)[0];
+            const uint32_t d[2] = {v.x, v.y};
+#pragma unroll
+            for (int i = 0; i < PX; ++i) yv[i] = byte_of(d, i);
+        } else {
+#pragma unroll
+            for (int i = 0; i < PX; ++i) yv[i] = x0 + i < w ? s[i] : 0;
+        }
+    }
+    int px[3 * PX];
+    if constexpr (HM == 0) {
+        // the chroma terms of a sample are shared by its two pixels
+#pragma unroll
+        for (int j = 0; j < PX / 2; ++j) {
+            const int u = nu[j + 1] - c.coff, v = nv[j + 1] - c.coff;
+            const int tr = c.rv * v + (1 << (SH - 1)), tg = c.gu * u + c.gv * v + (1 << (SH - 1)), tb = c.bu * u + (1 << (SH - 1));
+#pragma unroll
+            for (int i = 2 * j; i < 2 * j + 2; ++i) {
+                const int yy = c.ky * (yv[i] - c.yoff);
+                px[3 * i] = clampi((yy + tb) >> SH, VMAX);
+                px[3 * i + 1] = clampi((yy + tg) >> SH, VMAX);
+                px[3 * i + 2] = clampi((yy + tr) >> SH, VMAX);
+            }
+        }
+    } else {
+        typedef typename Acc422<S, HM>::type Acc;
+        constexpr int DL = HM == 1 ? 1 : 2, s = SH + DL;
+#pragma unroll
+        for (int i = 0; i < PX; ++i) {
+            const int j = (i >> 1) + 1;
+            int u, v;
+            if (HM == 1) {
+                u = i & 1 ? nu[j] + nu[j + 1] : 2 * nu[j];
+                v = i & 1 ? nv[j] + nv[j + 1] : 2 * nv[j];
+            } else {
+                u = i & 1 ? 3 * nu[j] + nu[j + 1] : nu[j - 1] + 3 * nu[j];
+                v = i & 1 ? 3 * nv[j] + nv[j + 1] : nv[j - 1] + 3 * nv[j];
+            }
+            u -= c.coff << DL; v -= c.coff << DL;
+            const Acc yy = (Acc)(c.ky * (yv[i] - c.yoff)) * (1 << DL) + ((Acc)1 << (s - 1));
+            px[3 * i] = clampi((int)((yy + (Acc)c.bu * u) >> s), VMAX);
+            px[3 * i + 1] = clampi((int)((yy + (Acc)c.gu * u + (Acc)c.gv * v) >> s), VMAX);
+            px[3 * i + 2] = clampi((int)((yy + (Acc)c.rv * v) >> s), VMAX);
+        }
+    }
+    S* dst = bgr + o * 3;
+    if (whole) {
+        if constexpr (sizeof(S) == 1) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                reinterpret_cast<uint2*>(dst)[q] = make_uint2(pack4(px[8 * q], px[8 * q + 1], px[8 * q + 2], px[8 * q + 3]),
+                                                              pack4(px[8 * q + 4], px[8 * q + 5], px[8 * q + 6], px[8 * q + 7]));
+        } else {
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                reinterpret_cast<uint4*>(dst)[q] = make_uint4(pack2(px[8 * q], px[8 * q + 1]), pack2(px[8 * q + 2], px[8 * q + 3]),
+                                                              pack2(px[8 * q + 4], px[8 * q + 5]), pack2(px[8 * q + 6], px[8 * q + 7]));
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3 * PX; ++i)
+            if (x0 + i / 3 < w) dst[i] = (S)px[i];
+    }
+}
+
 // u8 BGR <-> u16 BGR, 8 samples per thread: v * 257 is exact (v / 255 = 257 v / 65535); rint(v / 257) never meets a tie (257 is
 // odd), so it is floor((v + 128) / 257)
 constexpr int WN = 8;
@@ -590,6 +846,8 @@ void planes(int fmt, const uint8_t* base, int h, int w, const uint8_t** yp, cons
     if (fmt == PIX_YUV420P) { *up = base + wh; *vp = base + wh + cw * ch; }
     else if (fmt == PIX_YUV420P10LE) { *up = base + 2 * wh; *vp = base + 2 * (wh + cw * ch); }
     else if (fmt == PIX_NV12) { *up = base + wh; *vp = nullptr; }
+    else if (fmt == PIX_YUV422P) { *up = base + wh; *vp = base + wh + cw * h; }
+    else if (fmt == PIX_YUV422P10LE) { *up = base + 2 * wh; *vp = base + 2 * (wh + cw * h); }
     else { *up = base + 2 * wh; *vp = nullptr; }
 }
 
@@ -598,28 +856,103 @@ bool vec_ok(const void* a, const void* b, int w) { return w % PX == 0 && ((uintp
 
 dim3 grid_of(int h, int w) { return dim3((unsigned)((w + PX * BX - 1) / (PX * BX)), (unsigned)((h + 2 * BY - 1) / (2 * BY))); }
 
+// 4:2:2: a thread's 4 chroma samples move as one access of 4 bytes (8 bits) or 8 (10 bits), so the U and V planes -- w h and
+// w h + cw h samples into the frame -- must start on such a multiple as well; a row of threads covers one row
+bool is422(int fmt) { return fmt == PIX_YUV422P || fmt == PIX_YUV422P10LE; }
+bool vec422_ok(const void* bgr, const void* frame, const uint8_t* up, const uint8_t* vp, int w, int fmt)
+{
+    const uintptr_t ca = fmt == PIX_YUV422P10LE ? 8 : 4;
+    return vec_ok(bgr, frame, w) && ((uintptr_t)up | (uintptr_t)vp) % ca == 0;
+}
+dim3 grid422_of(int h, int w) { return dim3((unsigned)((w + PX * BX - 1) / (PX * BX)), (unsigned)((h + BY - 1) / BY)); }
+
 }  // namespace
 
 size_t pix_frame_bytes(int fmt, int h, int w)
 {
     if (h <= 0 || w <= 0) return 0;
-    const size_t wh = (size_t)w * h, c = 2 * ((size_t)(w + 1) / 2) * ((size_t)(h + 1) / 2);
+    const size_t wh = (size_t)w * h, c = 2 * ((size_t)(w + 1) / 2) * ((size_t)(h + 1) / 2), c422 = 2 * ((size_t)(w + 1) / 2) * (size_t)h;
     switch (fmt) {
     case PIX_BGR24: return 3 * wh;
     case PIX_YUV420P: case PIX_NV12: return wh + c;
     case PIX_P010LE: case PIX_YUV420P10LE: return 2 * (wh + c);
+    case PIX_YUV422P: return wh + c422;
+    case PIX_YUV422P10LE: return 2 * (wh + c422);
     case PIX_BGR48LE: return 6 * wh;
     default: return 0;
     }
 }
 
 namespace {
-int depth_of(int fmt) { return fmt == PIX_P010LE || fmt == PIX_YUV420P10LE ? 10 : 8; }
+int depth_of(int fmt) { return fmt == PIX_P010LE || fmt == PIX_YUV420P10LE || fmt == PIX_YUV422P10LE ? 10 : 8; }
+
+// pix_chroma_mode -> the 4:2:2 kernels' horizontal mode: left and topleft are both co-sited on this axis
+int hmode422(int colour) { const int m = pix_chroma_mode(colour); return m == 0 ? 0 : (m == 2 ? 2 : 1); }
+
+template <typename S>
+hipError_t from_bgr422(hipStream_t stream, int fmt, int colour, const S* bgr, void* dst, int h, int w)
+{
+    if (grid422_of(h, w).y > 65535) return hipErrorInvalidValue;
+    const uint8_t *yp, *up, *vp;
+    planes(fmt, (const uint8_t*)dst, h, w, &yp, &up, &vp);
+    const FwdCoef c = fwd_coef(colour, depth_of(fmt), sizeof(S) == 2);
+    const bool vec = vec422_ok(bgr, dst, up, vp, w, fmt);
+    const dim3 grid = grid422_of(h, w), block(BX, BY);
+    uint8_t *y = const_cast<uint8_t*>(yp), *u = const_cast<uint8_t*>(up), *v = const_cast<uint8_t*>(vp);
+#define UVA_PIX422_LAUNCH_M(W16, M)                                                                                         \
+    do {                                                                                                                    \
+        if (vec) hipLaunchKernelGGL((pix422_from_bgr<W16, true, S, M>), grid, block, 0, stream, bgr, y, u, v, h, w, c);    \
+        else hipLaunchKernelGGL((pix422_from_bgr<W16, false, S, M>), grid, block, 0, stream, bgr, y, u, v, h, w, c);       \
+    } while (0)
+#define UVA_PIX422_LAUNCH(W16)                                                                                              \
+    do {                                                                                                                    \
+        switch (hmode422(colour)) {                                                                                         \
+        case 0: UVA_PIX422_LAUNCH_M(W16, 0); break;                                                                         \
+        case 1: UVA_PIX422_LAUNCH_M(W16, 1); break;                                                                         \
+        default: UVA_PIX422_LAUNCH_M(W16, 2); break;                                                                        \
+        }                                                                                                                   \
+    } while (0)
+    if (fmt == PIX_YUV422P10LE) UVA_PIX422_LAUNCH(true);
+    else UVA_PIX422_LAUNCH(false);
+#undef UVA_PIX422_LAUNCH
+#undef UVA_PIX422_LAUNCH_M
+    return hipGetLastError();
+}
+
+template <typename S>
+hipError_t to_bgr422(hipStream_t stream, int fmt, int colour, const void* src, S* bgr, int h, int w)
+{
+    if (grid422_of(h, w).y > 65535) return hipErrorInvalidValue;
+    const uint8_t *y, *u, *v;
+    planes(fmt, (const uint8_t*)src, h, w, &y, &u, &v);
+    const InvCoef c = inv_coef(colour, depth_of(fmt), sizeof(S) == 2);
+    const bool vec = vec422_ok(bgr, src, u, v, w, fmt);
+    const dim3 grid = grid422_of(h, w), block(BX, BY);
+#define UVA_PIX422_LAUNCH_M(W16, M)                                                                                         \
+    do {                                                                                                                    \
+        if (vec) hipLaunchKernelGGL((pix422_to_bgr<W16, true, S, M>), grid, block, 0, stream, y, u, v, bgr, h, w, c);      \
+        else hipLaunchKernelGGL((pix422_to_bgr<W16, false, S, M>), grid, block, 0, stream, y, u, v, bgr, h, w, c);         \
+    } while (0)
+#define UVA_PIX422_LAUNCH(W16)                                                                                              \
+    do {                                                                                                                    \
+        switch (hmode422(colour)) {                                                                                         \
+        case 0: UVA_PIX422_LAUNCH_M(W16, 0); break;                                                                         \
+        case 1: UVA_PIX422_LAUNCH_M(W16, 1); break;                                                                         \
+        default: UVA_PIX422_LAUNCH_M(W16, 2); break;                                                                        \
+        }                                                                                                                   \
+    } while (0)
+    if (fmt == PIX_YUV422P10LE) UVA_PIX422_LAUNCH(true);
+    else UVA_PIX422_LAUNCH(false);
+#undef UVA_PIX422_LAUNCH
+#undef UVA_PIX422_LAUNCH_M
+    return hipGetLastError();
+}
 
 template <typename S>
 hipError_t from_bgr(hipStream_t stream, int fmt, int colour, const S* bgr, void* dst, int h, int w)
 {
     if (h <= 0 || w <= 0 || !pix_colour_ok(colour) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
+    if (is422(fmt)) return from_bgr422<S>(stream, fmt, colour, bgr, dst, h, w);
     const uint8_t *yp, *up, *vp;
     planes(fmt, (const uint8_t*)dst, h, w, &yp, &up, &vp);
     const FwdCoef c = fwd_coef(colour, depth_of(fmt), sizeof(S) == 2);
@@ -656,6 +989,7 @@ template <typename S>
 hipError_t to_bgr(hipStream_t stream, int fmt, int colour, const void* src, S* bgr, int h, int w)
 {
     if (h <= 0 || w <= 0 || !pix_colour_ok(colour) || grid_of(h, w).y > 65535) return hipErrorInvalidValue;
+    if (is422(fmt)) return to_bgr422<S>(stream, fmt, colour, src, bgr, h, w);
     const uint8_t *y, *u, *v;
     planes(fmt, (const uint8_t*)src, h, w, &y, &u, &v);
     const InvCoef c = inv_coef(colour, depth_of(fmt), sizeof(S) == 2);

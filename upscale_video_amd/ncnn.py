@@ -117,15 +117,17 @@ def png_encode_u8(img_bgr, gpu=0, workspace=None):
 
 # ---- raw-video pixel formats (include/uva.h UVA_PIX_*) -----------------------------------------
 PIX_FORMATS = {"bgr24": 0, "yuv420p": 1, "nv12": 2, "p010le": 3}     # ffmpeg's -pix_fmt names (the first four)
-# every format the calls take: + yuv420p10le (both routes) and bgr48le (u16 BGR: the 16-bit route's own, bit_depth=16).  Kept
-# apart so that PIX_FORMATS still lists exactly the formats of the first pixel-format release
-PIX_FORMATS_ALL = dict(PIX_FORMATS, yuv420p10le=5, bgr48le=6)      # (code 4 is not assigned)
+# every format the calls take: + yuv420p10le (both routes), bgr48le (u16 BGR: the 16-bit route's own, bit_depth=16) and the
+# 4:2:2 formats yuv422p / yuv422p10le (both routes).  Kept apart so that PIX_FORMATS still lists exactly
+# the formats of the first pixel-format release
+PIX_FORMATS_ALL = dict(PIX_FORMATS, yuv420p10le=5, bgr48le=6, yuv422p=7, yuv422p10le=8)      # (code 4 is not assigned)
 PIX16_ONLY = ("bgr48le",)
 COLORSPACES = {"bt601": 0, "bt709": 1}                              # ffmpeg's -colorspace names
 COLOR_RANGES = {"tv": 0, "pc": 2}                                   # ffmpeg's -color_range names (limited, full)
 # 4:2:0 chroma resampling: replicate = chroma repeated over its 2x2 block coming in and the 2x2 box
 # going out (sections 7.3, 7.4); bilinear = interpolated for where the chroma samples sit (ffmpeg's chroma_sample_location
-# names; H.264 / HEVC video is left, JPEG / MPEG-1 center, UHD BT.2020 material topleft)
+# names; H.264 / HEVC video is left, JPEG / MPEG-1 center, UHD BT.2020 material topleft).  A 4:2:2 format takes the horizontal
+# half of either (section 7.7): left and topleft are the same there
 CHROMA_FILTERS = {"replicate": 0, "bilinear": 4}
 CHROMA_LOCS = {"left": 0, "center": 8, "topleft": 16}
 # the resampler's filters (include/uva.h UVA_RESIZE_*)
@@ -133,14 +135,16 @@ RESIZE_FILTERS = {"lanczos": 0, "bicubic": 1, "bilinear": 2}
 
 
 def pix_frame_bytes(fmt, h, w):
-    """bytes of one dense h x w rawvideo frame of `fmt` (chroma planes ceil(w/2) x ceil(h/2); include/uva.h uva_pix_frame_bytes)"""
+    """bytes of one dense h x w rawvideo frame of `fmt` (chroma planes ceil(w/2) x ceil(h/2), ceil(w/2) x h for the 4:2:2
+    formats; include/uva.h uva_pix_frame_bytes)"""
     if fmt not in PIX_FORMATS_ALL:
         raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
     if h <= 0 or w <= 0:
         raise ValueError("frame size must be positive")
     c = 2 * ((w + 1) // 2) * ((h + 1) // 2)
+    c422 = 2 * ((w + 1) // 2) * h
     return {"bgr24": 3 * w * h, "yuv420p": w * h + c, "nv12": w * h + c, "p010le": 2 * (w * h + c), "yuv420p10le": 2 * (w * h + c),
-            "bgr48le": 6 * w * h}[fmt]
+            "bgr48le": 6 * w * h, "yuv422p": w * h + c422, "yuv422p10le": 2 * (w * h + c422)}[fmt]
 
 
 def colour_word(colour="bt601", color_range="tv", chroma_filter="replicate", chroma_loc="left"):

@@ -10,20 +10,23 @@ This module is the same per-frame arithmetic fed by a raw pipe instead, ffmpeg i
       | ffmpeg -f rawvideo -pix_fmt bgr24 -s 3840x2160 -r 24 -i - out.mkv
 
 or, with the colour conversion on the GPU and half the pipe bytes (--in-pix-fmt / --out-pix-fmt: bgr24, yuv420p, nv12,
-p010le; --colorspace bt601|bt709, --color-range tv|pc, default bt601 / tv: DESIGN.md section 7.3):
+p010le, yuv420p10le, and the 4:2:2 formats of capture and mezzanine material yuv422p, yuv422p10le; --colorspace bt601|bt709,
+--color-range tv|pc, default bt601 / tv: DESIGN.md sections 7.3, 7.7):
 
     ffmpeg -i in.mkv -f rawvideo -pix_fmt yuv420p - \\
       | python -m upscale_video_amd.rawvideo -W 1920 -H 1080 -s 2 --in-pix-fmt yuv420p --out-pix-fmt p010le \\
       | ffmpeg -f rawvideo -pix_fmt p010le -s 3840x2160 -r 24 -i - -c:v libx265 out.mkv
 
---bit-depth 16 runs the 2x / 4x net on 16-bit samples so that 10-bit frames (p010le, yuv420p10le) keep their depth
+--bit-depth 16 runs the 2x / 4x net on 16-bit samples so that 10-bit frames (p010le, yuv420p10le, yuv422p10le) keep their depth
 (no -m option with it).
 
 --chroma-filter bilinear interpolates the 4:2:0 chroma on the way in and filters it on the way out for where its samples sit
  instead of repeating every chroma sample over its 2x2 block and averaging the block: the net then
 sees no 2x2 colour steps to sharpen, and colour stays registered with luma.  --chroma-loc names the siting (ffmpeg's
 chroma_sample_location): left (default) for video from H.264 / HEVC, center for JPEG / MPEG-1 material, topleft for UHD
-BT.2020 material.  The default, replicate, keeps the earlier releases' bytes.
+BT.2020 material.  The default, replicate, keeps the earlier releases' bytes.  A 4:2:2 format (one chroma row per luma row)
+takes the horizontal half of either mode: the pair instead of the 2x2 block, and left and topleft are the same there (DESIGN.md
+section 7.7).
 
 --out-size WxH (or --out-scale F, the total scale relative to the input frame, as Real-ESRGAN's --outscale) resamples the net's
 2x / 4x result to the size asked for on the GPU, between the net and the output conversion (DESIGN.md section 7.6;
@@ -737,19 +740,21 @@ def main(argv=None):
                     help="file to file with several -g entries: deal the frames out one by one through ONE reader and ONE writer "
                          "(what pipes get) instead of one contiguous segment of frames, reader and writer per entry")
     ap.add_argument("--in-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS_ALL),
-                    help="ffmpeg -pix_fmt of the input frames (default bgr24); converted to BGR on the GPU")
+                    help="ffmpeg -pix_fmt of the input frames (default bgr24; 4:2:0: yuv420p, nv12, p010le, yuv420p10le; 4:2:2: yuv422p, "
+                         "yuv422p10le); converted to BGR on the GPU")
     ap.add_argument("--out-pix-fmt", default="bgr24", choices=list(ncnn.PIX_FORMATS_ALL),
-                    help="ffmpeg -pix_fmt of the output frames (default bgr24); converted from the net's BGR on the GPU")
+                    help="ffmpeg -pix_fmt of the output frames (default bgr24; the same names); converted from the net's BGR on the GPU")
     ap.add_argument("--colorspace", default="bt601", choices=list(ncnn.COLORSPACES),
-                    help="Y'CbCr matrix of yuv420p / nv12 / p010le frames (default bt601: what ffmpeg applies to the reference's "
+                    help="Y'CbCr matrix of the Y'CbCr formats' frames (default bt601: what ffmpeg applies to the reference's "
                          "untagged PNGs)")
     ap.add_argument("--color-range", default="tv", choices=list(ncnn.COLOR_RANGES), help="tv = limited (default), pc = full")
     ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
-                    help="16: the 2x / 4x net runs on 16-bit samples, so 10-bit frames (p010le, yuv420p10le) keep their depth "
-                         "(default 8); takes no -m option")
+                    help="16: the 2x / 4x net runs on 16-bit samples, so 10-bit frames (p010le, yuv420p10le, yuv422p10le) keep their "
+                         "depth (default 8); takes no -m option")
     ap.add_argument("--model-path", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models"))
     ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS),
-                    help="4:2:0 chroma resampling in the Y'CbCr conversions: replicate (default: every chroma sample repeated over its "
+                    help="chroma resampling in the Y'CbCr conversions (4:2:2 formats: along the row alone; DESIGN.md section 7.7): "
+                         "replicate (default: every chroma sample repeated over its "
                          "2x2 block coming in, the block's average going out; the earlier releases' bytes) or bilinear (interpolated "
                          "for where the chroma samples sit, so the net is not fed 2x2 colour steps and colour stays registered with "
                          "luma; DESIGN.md section 7.5)")
