@@ -41,16 +41,35 @@ def slack(model, route, what, fallback):
     return float(e["bar"]) if e else fallback
 
 
-def fp32_bar(model, route):
+LARGE_SAMPLES = 10 ** 6     # a comparison of at least this many samples is "large": counting noise no longer sets its distance
+
+
+def size_class(samples):
+    return "large" if samples is not None and samples >= LARGE_SAMPLES else "small"
+
+
+def fp32_bar(model, route, input_class=None, samples=None):
     """Bars of a comparison with the fp32 oracle (kernel-independent) as keyword arguments of check_u8: the measured worst
     case of `model` on `route` -/+ a margin (tests/golden/parity_slack.json "fp32_bars", tools/parity_slack.py), never looser
-    than the fixed bars they replace; those fixed bars where nothing has been measured yet."""
+    than the fixed bars they replace; those fixed bars where nothing has been measured yet.
+    With `input_class` (the content of the frame as the CALL SITE knows it: "smooth", "random", ...; never read off a record's
+    name) and `samples` (how many are compared: size_class) the entry "{model}/{route}/{input_class}/{size}" applies where there
+    is one -- white noise then no longer sets the bar of a smooth 2160p frame -- and the "{model}/{route}" entry where there
+    is none.  A class entry only ever tightens: each field is the stricter of the two."""
     slack("", "", "", 0)                                    # loads the file
-    e = _SLACK.get("fp32_bars", {}).get(f"{model}/{route}")
+    bars = _SLACK.get("fp32_bars", {})
+    e = bars.get(f"{model}/{route}")
     chain = model == "chain"
     if not e:
-        return {"max_lsb": 3 if chain else 2, "min_psnr": 48.0 if chain else 50.0}
-    return {"max_lsb": int(e["max_lsb"]), "min_psnr": float(e["min_psnr_db"]), "max_share": float(e["max_differ_share"])}
+        out = {"max_lsb": 3 if chain else 2, "min_psnr": 48.0 if chain else 50.0}
+    else:
+        out = {"max_lsb": int(e["max_lsb"]), "min_psnr": float(e["min_psnr_db"]), "max_share": float(e["max_differ_share"])}
+    c = bars.get(f"{model}/{route}/{input_class}/{size_class(samples)}") if input_class is not None else None
+    if c:
+        out["max_lsb"] = min(out["max_lsb"], int(c["max_lsb"]))
+        out["min_psnr"] = max(out["min_psnr"], float(c["min_psnr_db"]))
+        out["max_share"] = min(out.get("max_share", 1.0), float(c["max_differ_share"]))
+    return out
 
 
 def record(name, **fields):
@@ -94,19 +113,21 @@ def structure_u8(d):
             "col_ratio": float(col.max() / floor), "row_ratio": float(row.max() / floor)}
 
 
-def check_u8(name, got, want, vs, max_lsb, min_psnr=None, max_share=None, model=None, route=None, structure=True):
+def check_u8(name, got, want, vs, max_lsb, min_psnr=None, max_share=None, model=None, route=None, structure=True,
+             input_class=None):
     """u8 frames: record, then hold to the bars (max |diff| in LSB, PSNR in dB, share of samples that differ) and -- on
     frames of at least 48 x 48 -- to "the error has no spatial structure" (structure_u8: a row or column whose mean |diff|
     stands STRUCTURE_Z standard errors above its neighbours fails, whatever the LSB and dB bars say: round 5's folded-strip
-    bug was one wrong column in 74 inside <= 2 LSB / >= 50 dB)."""
+    bug was one wrong column in 74 inside <= 2 LSB / >= 50 dB).  `input_class` (what the frame holds: "smooth", "random", ...)
+    goes into the record: tools/parity_slack.py derives the fp32 bars per class from it (fp32_bar)."""
     assert got.shape == want.shape and got.dtype == np.uint8, (name, got.shape, want.shape, got.dtype)
     d = np.abs(got.astype(np.int16) - want.astype(np.int16))
     worst = int(d.max()) if d.size else 0
     share = float((d > 0).mean()) if d.size else 0.0
     p = psnr_u8(got, want)
     st = structure_u8(d) if structure else None
-    record(name, kind="u8", vs=vs, model=model, route=route, samples=int(d.size), max_lsb=worst, psnr_db=p, differ_share=share,
-           bar_max_lsb=max_lsb, bar_min_psnr_db=min_psnr, bar_max_share=max_share, structure=st,
+    record(name, kind="u8", vs=vs, model=model, route=route, input_class=input_class, samples=int(d.size), max_lsb=worst,
+           psnr_db=p, differ_share=share, bar_max_lsb=max_lsb, bar_min_psnr_db=min_psnr, bar_max_share=max_share, structure=st,
            bar_structure_z=(STRUCTURE_Z if st else None))
     if st:
         assert st["col_z"] <= STRUCTURE_Z, (name, vs, "structured error: column", st["col_at"], "stands", st["col_z"], "s.e. above its neighbours", st)
@@ -203,7 +224,8 @@ def summary_lines():
             yield ("parity %-58s vs %-34s max %d LSB (bar %s)  PSNR %6.2f dB (bar %s)  differ %.3f %% (bar %s)%s" % (
                 r["name"][:58], r["vs"][:34], r["max_lsb"], r["bar_max_lsb"], r["psnr_db"], r["bar_min_psnr_db"],
                 100 * r["differ_share"], ("%.1f %%" % (100 * r["bar_max_share"])) if r["bar_max_share"] is not None else "-",
-                ("  structure z col %.1f row %.1f (bar %.0f)" % (st["col_z"], st["row_z"], r["bar_structure_z"])) if st else ""))
+                ("  structure z col %.1f row %.1f (bar %.0f)" % (st["col_z"], st["row_z"], r["bar_structure_z"])) if st else "")
+                   + (("  [%s/%s]" % (r["input_class"], size_class(r.get("samples")))) if r.get("input_class") else ""))
         elif r.get("kind") == "u16":
             st = r.get("structure")
             bar = lambda k, f, m=1: ("bar " + f % (m * r[k])) if r.get(k) is not None else "bar -"   # noqa: E731
@@ -214,6 +236,10 @@ def summary_lines():
                        100 * r["x257_share"], bar("bar_x257_share", "%.2f %%", 100),
                        ("  structure z col %.1f row %.1f (bar %.0f)" % (st["col_z"], st["row_z"], r["bar_structure_z"])) if st else "",
                        "  8-bit COUNTERFACTUAL (fails its depth bars)" if r.get("counterfactual") else ""))
+        elif r.get("kind") == "pair":           # two distances from one reference side by side, no bar (tests/test_parity_bars.py)
+            yield ("parity %-58s vs %-34s GPU max %d LSB, %.2f dB, %.3f %%  |  product-mode oracle max %d LSB, %.2f dB, %.3f %%" % (
+                r["name"][:58], r["vs"][:34], r["gpu_max_lsb"], r["gpu_psnr_db"], 100 * r["gpu_differ_share"],
+                r["oracle_max_lsb"], r["oracle_psnr_db"], 100 * r["oracle_differ_share"]))
         else:
             yield ("parity %-58s vs %-34s max |err| %.3e (bar %.3e)%s" % (
                 r["name"][:58], r["vs"][:34], r["max_abs_err"], r["bar_max_abs"],

@@ -55,7 +55,7 @@ def test_full_size_batch_of_four_against_the_oracle_in_windows(net1x, oracle_mod
         cy0, cx0, cy1, cx1 = max(0, y0 - rad), max(0, x0 - rad), min(h, y0 + win + rad), min(w, x0 + win + rad)
         want = oracle_models["1x"].apply_model(np.ascontiguousarray(frames[k][cy0:cy1, cx0:cx1]))[y0 - cy0:y0 - cy0 + win, x0 - cx0:x0 - cx0 + win]
         check_u8(f"1x batch of 4, frame {k}, 1080p window ({y0},{x0})", np.ascontiguousarray(got[k][y0:y0 + win, x0:x0 + win]),
-                 np.ascontiguousarray(want), vs="fp32 oracle", max_lsb=1, min_psnr=55, model="1x", route="whole")
+                 np.ascontiguousarray(want), vs="fp32 oracle", max_lsb=1, min_psnr=55, model="1x", route="whole", input_class="smooth")
 
 
 def test_padded_strides_and_aliasing_free_outputs(net1x, oracle):

@@ -450,10 +450,11 @@ def test_config3_every_sample_at_1080p(uva, net2x, oracle_models, oracle):
     mid = pre.process_u8(img, tile_size=0)
     out = net2x.process_u8(mid, tile_size=960, border=10)
     omid = oracle_models["1x"].apply_model(img)
-    check_u8("config 3: 1x stage, WHOLE 1080p frame, every sample", mid, omid, vs="fp32 oracle", model="1x", route="whole", **fp32_bar("1x", "whole"))
+    check_u8("config 3: 1x stage, WHOLE 1080p frame, every sample", mid, omid, vs="fp32 oracle", model="1x", route="whole",
+             input_class="smooth", **fp32_bar("1x", "whole", "smooth", mid.size))
     want = oracle_models["2x"].upscale_image(omid, tile_size=960, border=10)
     check_u8("config 3: 1x -> u8 -> 2x (960/10), WHOLE 1080p frame, every sample", out, want, vs="fp32 oracle chain", model="chain", route="tiled",
-             **fp32_bar("chain", "tiled"))
+             input_class="smooth", **fp32_bar("chain", "tiled", "smooth", out.size))
 
 
 def test_config5_every_sample_of_the_2160p_frame(net2x, oracle_models, oracle):
@@ -465,7 +466,8 @@ def test_config5_every_sample_of_the_2160p_frame(net2x, oracle_models, oracle):
     img = oracle.synthetic_frame(2160, 3840, seed=55)
     got = net2x.process_u8(img, tile_size=960, border=10)
     want = oracle_models["2x"].upscale_image(img, tile_size=960, border=10)
-    check_u8("config 5: 2x (960/10), WHOLE 2160p frame, every sample", got, want, vs="fp32 oracle", model="2x", route="tiled", **fp32_bar("2x", "tiled"))
+    check_u8("config 5: 2x (960/10), WHOLE 2160p frame, every sample", got, want, vs="fp32 oracle", model="2x", route="tiled",
+             input_class="smooth", **fp32_bar("2x", "tiled", "smooth", got.size))
 
 
 def test_config4_valar_at_1080p(uva, tmp_path):

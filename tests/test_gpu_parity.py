@@ -108,7 +108,8 @@ def test_process_u8_whole_frame_matches_oracle(nets, oracle_models, oracle, key,
     want32 = om.apply_model(img)
     want16 = om.apply_model(img, flags=oracle.product_flags())
     assert got.shape == want32.shape and got.dtype == np.uint8
-    check_u8(f"{key} apply_model {w}x{h} {kind}", got, want32, vs=FP32, model=key, route="whole", **fp32_bar(key, "whole"))
+    check_u8(f"{key} apply_model {w}x{h} {kind}", got, want32, vs=FP32, model=key, route="whole", input_class=kind,
+             **fp32_bar(key, "whole", kind, got.size))
     check_u8(f"{key} apply_model {w}x{h} {kind}", got, want16, vs=PRODUCT, max_lsb=1, max_share=U8_DIFFER(oracle, key, "whole"),
              model=key, route="whole")
 
@@ -150,7 +151,8 @@ def test_tiled_frame_matches_oracle_tiling(nets, oracle_models, oracle, key, h, 
     want32 = om.upscale_image(img, tile_size=ts, border=10)
     check_u8(f"{key} upscale_image {w}x{h} t{ts}", got, want16, vs=PRODUCT, max_lsb=1, max_share=U8_DIFFER(oracle, key, "tiled"),
              model=key, route="tiled")
-    check_u8(f"{key} upscale_image {w}x{h} t{ts}", got, want32, vs=FP32, model=key, route="tiled", **fp32_bar(key, "tiled"))
+    check_u8(f"{key} upscale_image {w}x{h} t{ts}", got, want32, vs=FP32, model=key, route="tiled", input_class="random",
+             **fp32_bar(key, "tiled", "random", got.size))
 
 
 @pytest.mark.parametrize("key", ["2x", "4x"])
@@ -205,16 +207,16 @@ def test_structure_detector_catches_the_fold14_schedule(uva, nets, oracle, oracl
     import parity_report
     monkeypatch.setenv("UVA_TW_FOLD", "14")
     bad = load_net(uva, "2x")             # (the schedule is built, and the switch read, when a geometry is first seen)
-    cases = [(oracle.synthetic_frame(128, 128, seed=31), 64), (oracle.synthetic_frame(384, 128, seed=32), 64),
-             (oracle.synthetic_frame(128, 128, seed=33, kind="random"), 64)]
-    bad_out = [bad.process_u8(img, tile_size=t, border=10) for img, t in cases]
+    cases = [(oracle.synthetic_frame(128, 128, seed=31), 64, "smooth"), (oracle.synthetic_frame(384, 128, seed=32), 64, "smooth"),
+             (oracle.synthetic_frame(128, 128, seed=33, kind="random"), 64, "random")]
+    bad_out = [bad.process_u8(img, tile_size=t, border=10) for img, t, _ in cases]
     monkeypatch.delenv("UVA_TW_FOLD")
-    for (img, t), b in zip(cases, bad_out):
+    for (img, t, kind), b in zip(cases, bad_out):
         want = oracle_models["2x"].upscale_image(img, tile_size=t, border=10)
         good = nets["2x"].process_u8(img, tile_size=t, border=10)
         assert not np.array_equal(good, b), "UVA_TW_FOLD=14 did not change the frame: the known-bad schedule is not being built"
         st_good = check_u8(f"2x {img.shape[1]}x{img.shape[0]} t{t}: shipped schedule", good, want, vs=FP32, model="2x", route="tiled",
-                           **fp32_bar("2x", "tiled"))
+                           input_class=kind, **fp32_bar("2x", "tiled", kind, good.size))
         d = np.abs(b.astype(np.int16) - want.astype(np.int16))
         st = parity_report.structure_u8(d)
         record(f"2x {img.shape[1]}x{img.shape[0]} t{t}: fold-14 schedule (KNOWN BAD, must be caught)", kind="u8", vs=FP32, model=None, route=None,
@@ -223,7 +225,7 @@ def test_structure_detector_catches_the_fold14_schedule(uva, nets, oracle, oracl
         assert st["col_z"] > 2 * parity_report.STRUCTURE_Z, ("the detector does not see the wrong columns", st)
         with pytest.raises(AssertionError, match="structured error"):
             check_u8("fold-14 through the bars (recorded again on purpose)", b, want, vs=FP32 + " [expected to fail]", model=None, route=None,
-                     **fp32_bar("2x", "tiled"))
+                     input_class=kind, **fp32_bar("2x", "tiled", kind, b.size))
 
 
 @pytest.mark.parametrize("key", ["2x", "4x"])
@@ -269,8 +271,10 @@ def test_chain_1x_then_2x(nets, oracle_models, oracle):
     out = nets["2x"].process_u8(mid, tile_size=960, border=10)
     omid = oracle_models["1x"].apply_model(img)
     want = oracle_models["2x"].upscale_image(omid)
-    check_u8("chain: 1x stage 80x48", mid, omid, vs=FP32, model="1x", route="whole", **fp32_bar("1x", "whole"))
-    check_u8("chain: 1x -> u8 -> 2x 80x48", out, want, vs=FP32 + " chain", model="chain", route="tiled", **fp32_bar("chain", "tiled"))
+    check_u8("chain: 1x stage 80x48", mid, omid, vs=FP32, model="1x", route="whole", input_class="smooth",
+             **fp32_bar("1x", "whole", "smooth", mid.size))
+    check_u8("chain: 1x -> u8 -> 2x 80x48", out, want, vs=FP32 + " chain", model="chain", route="tiled", input_class="smooth",
+             **fp32_bar("chain", "tiled", "smooth", out.size))
 
 
 def test_row_strides_and_repeatability(nets, uva, oracle):
@@ -315,7 +319,7 @@ def test_full_size_frame_properties(nets, oracle_models, oracle, key):
         want = om.apply_model(crop)[(y0 - cy0) * s:(y0 - cy0 + win) * s, (x0 - cx0) * s:(x0 - cx0 + win) * s]
         got = whole[y0 * s:(y0 + win) * s, x0 * s:(x0 + win) * s]
         check_u8(f"{key} 1080p whole frame, window ({y0},{x0})", np.ascontiguousarray(got), np.ascontiguousarray(want), vs=FP32,
-                 model=key, route="whole", **fp32_bar(key, "whole"))
+                 model=key, route="whole", input_class="smooth", **fp32_bar(key, "whole", "smooth", got.size))
     if s > 1:
         tiled = net.process_u8(img, tile_size=960, border=10)
         d = np.abs(tiled.astype(int) - whole.astype(int))
@@ -468,7 +472,8 @@ def test_random_geometries_match_oracle(nets, oracle_models, oracle, key):
         if case == 0: h, w = 1, 17
         if case == 1: h, w = 5, 1
         ts = int(rng.choice([0, 24, 32, 48, 64]))
-        img = oracle.synthetic_frame(h, w, kind="random" if case % 2 else "smooth", seed=1000 * case + h)
+        kind = "random" if case % 2 else "smooth"
+        img = oracle.synthetic_frame(h, w, kind=kind, seed=1000 * case + h)
         want = om.upscale_image(img, tile_size=ts, border=10) if ts else om.apply_model(img)
         # padded row strides on both sides, through the raw C entry point
         in_stride, out_stride = w * 3 + int(rng.integers(0, 9)), w * s * 3 + int(rng.integers(0, 9))
@@ -480,7 +485,8 @@ def test_random_geometries_match_oracle(nets, oracle_models, oracle, key):
         got = dst[:, :w * s * 3].reshape(h * s, w * s, 3)
         assert (dst[:, w * s * 3:] == 0xA5).all(), (key, case, "row padding was written")
         check_u8(f"{key} sweep case {case}: {w}x{h} t{ts}", np.ascontiguousarray(got), want, vs=FP32,
-                 model=key, route="tiled" if ts else "whole", **fp32_bar(key, "tiled" if ts else "whole"))
+                 model=key, route="tiled" if ts else "whole", input_class=kind,
+                 **fp32_bar(key, "tiled" if ts else "whole", kind, got.size))
 
 
 @pytest.mark.parametrize("key", ["2x", "1x"])
@@ -521,7 +527,10 @@ def test_whole_1080p_frame_against_the_oracle(nets, oracle_models, oracle, key):
     want = oracle_models[key].upscale_image(img, tile_size=960, border=10)
     assert got.shape == (1080 * s, 1920 * s, 3)
     # bars: the measured distance of this frame (2x: 71.3 dB, 0.48 % of the samples one level apart; 4x: 69.9 dB, 0.66 %) less a
-    # margin, and no row or column standing out of its neighbourhood (parity_report.structure_u8)
-    worst, psnr, share = check_u8(f"{key} WHOLE 1080p frame, reference tiling 960/10, every sample", got, want, vs=FP32, max_lsb=1,
-                                  min_psnr={"2x": 69.3, "4x": 67.9}[key], max_share=0.02, model=key, route="tiled")
+    # margin, and no row or column standing out of its neighbourhood (parity_report.structure_u8); the bar of the frame's
+    # class (smooth, large) holds as well: per field, the tighter of the two
+    cb = fp32_bar(key, "tiled", "smooth", got.size)
+    worst, psnr, share = check_u8(f"{key} WHOLE 1080p frame, reference tiling 960/10, every sample", got, want, vs=FP32,
+                                  max_lsb=min(1, cb["max_lsb"]), min_psnr=max({"2x": 69.3, "4x": 67.9}[key], cb["min_psnr"]),
+                                  max_share=min(0.02, cb.get("max_share", 0.02)), model=key, route="tiled", input_class="smooth")
     print(f"whole 1080p frame, {key}: max |diff| {worst} LSB, PSNR {psnr:.2f} dB, {100 * share:.3f} % of the samples differ")

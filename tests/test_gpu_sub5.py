@@ -40,7 +40,8 @@ def test_two_launches_of_five_layers_give_the_bytes_of_the_one_launch_kernel(bot
     b = whole.process_u8(img, tile_size=0)
     assert np.array_equal(a, b), (h, w, int(np.abs(a.astype(int) - b.astype(int)).max()), float((a != b).mean()))
     if h * w <= 130 * 216:
-        check_u8(f"1x sub5_kernel {w}x{h} {kind}", a, oracle_models["1x"].apply_model(img), vs=FP32, model="1x", route="whole", **fp32_bar("1x", "whole"))
+        check_u8(f"1x sub5_kernel {w}x{h} {kind}", a, oracle_models["1x"].apply_model(img), vs=FP32, model="1x", route="whole",
+                 input_class=kind, **fp32_bar("1x", "whole", kind, a.size))
 
 
 def test_full_size_frame_equals_the_one_launch_kernel_and_the_oracle_in_windows(both, oracle_models, oracle):
@@ -56,7 +57,7 @@ def test_full_size_frame_equals_the_one_launch_kernel_and_the_oracle_in_windows(
         cy0, cx0, cy1, cx1 = max(0, y0 - rad), max(0, x0 - rad), min(h, y0 + win + rad), min(w, x0 + win + rad)
         want = oracle_models["1x"].apply_model(np.ascontiguousarray(img[cy0:cy1, cx0:cx1]))[y0 - cy0:y0 - cy0 + win, x0 - cx0:x0 - cx0 + win]
         check_u8(f"1x sub5_kernel 1080p window ({y0},{x0})", np.ascontiguousarray(a[y0:y0 + win, x0:x0 + win]), np.ascontiguousarray(want),
-                 vs=FP32, max_lsb=1, min_psnr=55, model="1x", route="whole")
+                 vs=FP32, max_lsb=1, min_psnr=55, model="1x", route="whole", input_class="smooth")
 
 
 def test_other_frame_sizes_in_turn_reuse_nothing_stale(both, oracle):

@@ -1,0 +1,353 @@
+"""Do the fp32-oracle bars bite?  (tests/parity_report.py fp32_bar, tests/golden/parity_slack.json, tools/parity_slack.py)
+
+Keyed by (model, route) alone, the worst small white-noise frame of a route set the bar of every smooth frame on it: 57-60 dB
+and 5-9 % of the samples against a measured 70-73 dB and 0.3-0.7 %.  A net whose output is shifted by 0.06 of a level passed all
+of them.  The bars are now keyed by input class as well ("{model}/{route}/{smooth|random}/{large|small}"), and this file shows,
+with MUTANT NETS (tests/mutant_net.py: a shipped .bin with one array rewritten, the shapes untouched), that a class bar fails
+what the (model, route) bar let through:
+
+    A  tail_bias  every bias of the last convolution + 0.03 / 255: a DC offset of 0.03 level
+    B  slope      the PReLU slopes of the middle trunk layer x (1 + SLOPE_AMOUNT): an error that follows the content
+
+Frames: synthetic_frame(seed=5), smooth; 270 x 480 for 2x / 4x (the smallest whose result is "large": >= 10^6 samples), 540 x 960
+for 1x.  Measured on the CPU, oracle(mutant) against oracle(shipped), both fp32 -- every mutant at most 1 LSB away:
+
+                 A, 0.03 level             B, amount            its distance             (shipped, product mode vs fp32)
+    2x           63.35 dB, 3.01 %          0.016                64.59 dB, 2.26 %         71.29 dB, 0.48 %
+    4x           63.35 dB, 3.01 %          0.016                63.51 dB, 2.90 %         69.90 dB, 0.66 %
+    1x           63.33 dB, 3.02 %          0.012                65.76 dB, 1.73 %         73.23 dB, 0.31 %   (540 x 960; 73.41 dB at 270 x 480)
+
+(run in product mode the mutants land on the same figures against the shipped fp32 result: A 63.34 / 63.36 / 63.33 dB, B 64.50 dB
+2.31 %, 63.33 dB 3.02 %, 65.69 dB 1.75 %.)
+
+B's amounts were found by bisection on the share of differing samples, to land between twice the class bar's share and half of
+the (model, route) bar's (2x: 1.2 .. 3.2 %, 4x: 1.7 .. 4.5 %, 1x: 0.9 .. 2.6 %); the tests assert that window for B and A's figures
+(A_PSNR, A_SHARE).
+
+Without a GPU the product-mode oracle (the oracle run with the kernels' rounding points) stands in for the kernel; -m gpu loads
+the mutant .bin into ncnn.Net and runs the kernels themselves.  Every mutant record is named KNOWN BAD and carries no model, so
+tools/parity_slack.py never harvests it."""
+import functools
+import importlib.util
+import json
+import os
+
+import numpy as np
+import pytest
+
+import mutant_net
+import parity_report as pr
+from conftest import ROOT
+from oracle import uvoracle
+
+FP32 = "fp32 oracle"
+SEED = 5
+FRAMES = {"2x": (270, 480), "4x": (270, 480), "1x": (540, 960)}
+TAIL_AMOUNT = 0.03                                       # levels
+A_PSNR, A_SHARE = 63.35, 0.0301                          # A against the shipped fp32 result (an offset of 0.03 level flips 3 % of the roundings)
+SLOPE_AMOUNT = {"2x": 0.016, "4x": 0.016, "1x": 0.012}   # (the measured distance of each: the table above)
+KEYS = ("2x", "4x", "1x")
+MUTANTS = [(k, m) for k in KEYS for m in mutant_net.KINDS]
+
+
+def amount(key, kind):
+    return TAIL_AMOUNT if kind == "tail_bias" else SLOPE_AMOUNT[key]
+
+
+@functools.lru_cache(maxsize=None)
+def frame(key):
+    return uvoracle.synthetic_frame(*FRAMES[key], seed=SEED)
+
+
+_MUTANT_DIR = None
+
+
+@pytest.fixture(scope="session")
+def mutants(tmp_path_factory):
+    """the directory the mutant .bin files of this session are written to (mutant_bin); every test that uses a mutant asks for it"""
+    global _MUTANT_DIR
+    _MUTANT_DIR = str(tmp_path_factory.mktemp("mutants"))
+    return _MUTANT_DIR
+
+
+@functools.lru_cache(maxsize=None)
+def mutant_bin(key, kind):
+    """path of the mutant .bin, written once per session"""
+    dst = os.path.join(_MUTANT_DIR, f"{key}_{kind}.bin")
+    mutant_net.write_mutant_bin(key, dst, kind, amount(key, kind))
+    return dst
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_model(key, kind=None):
+    return uvoracle.load_model(key) if kind is None else uvoracle.Model(mutant_net.model_paths(key)[0], mutant_bin(key, kind))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_u8(key, kind=None, product=False, tile=0):
+    """the oracle's u8 result on frame(key): shipped net (kind None) or a mutant, fp32 or product mode, whole frame or tiled"""
+    uvoracle.build()
+    flags = uvoracle.product_flags() if product else 0
+    m = oracle_model(key, kind)
+    out = m.upscale_image(frame(key), tile_size=tile, border=10, flags=flags) if tile else m.apply_model(frame(key), flags=flags)
+    out.setflags(write=False)
+    return out
+
+
+def has_class_bar(key, route):
+    pr.slack("", "", "", 0)
+    return f"{key}/{route}/smooth/large" in pr._SLACK.get("fp32_bars", {})
+
+
+def class_bar(key, route):
+    n = FRAMES[key][0] * FRAMES[key][1] * 3 * oracle_model(key).scale ** 2
+    assert pr.size_class(n) == "large"
+    assert has_class_bar(key, route), "no class bar: the comparison would fall back to (model, route)"
+    return pr.fp32_bar(key, route, "smooth", n)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the bars' plumbing: records carry a class, fp32_bar looks it up, tools/parity_slack.py derives it
+# ------------------------------------------------------------------------------------------------------------------
+def _tool():
+    spec = importlib.util.spec_from_file_location("parity_slack", os.path.join(ROOT, "tools", "parity_slack.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture
+def records(monkeypatch):
+    monkeypatch.setattr(pr, "RECORDS", [])
+    return pr.RECORDS
+
+
+def _u8(model, route, psnr, share, lsb=1, input_class=None, samples=5000, vs=FP32):
+    r = {"name": "r", "kind": "u8", "vs": vs, "model": model, "route": route, "samples": samples, "max_lsb": lsb, "psnr_db": psnr,
+         "differ_share": share}
+    if input_class is not None:
+        r["input_class"] = input_class
+    return r
+
+
+NEW = [_u8("2x", "tiled", 71.3, 0.0048, input_class="smooth", samples=3 * 10 ** 6),
+       _u8("2x", "tiled", 71.9, 0.0041, input_class="smooth", samples=10 ** 6),             # 10^6 is large
+       _u8("2x", "tiled", 69.1, 0.008, input_class="smooth", samples=10 ** 6 - 1),          # ... and one fewer is small
+       _u8("2x", "tiled", 60.8, 0.0545, lsb=2, input_class="random", samples=30000),
+       _u8("2x", "tiled", 60.9, 0.08, input_class="random", samples=2 * 10 ** 6),
+       _u8("2x", "tiled", 40.0, 0.5, lsb=9, input_class="smooth", samples=10 ** 7, vs="golden fixture"),   # not an fp32-oracle record
+       _u8(None, None, 41.0, 0.4, lsb=5, input_class="smooth", samples=10 ** 7),                           # a KNOWN BAD record
+       _u8("1x", "whole", 72.7, 0.0035, input_class="smooth", samples=6 * 10 ** 6)]
+OLD = [_u8("2x", "tiled", 59.0, 0.07, lsb=2), _u8("1x", "whole", 62.35, 0.03789), _u8("4x", "whole", 59.4, 0.0749)]
+
+
+def _run_tool(tmp_path, name, *record_lists):
+    paths = []
+    for i, recs in enumerate(record_lists):
+        p = tmp_path / f"{name}{i}.json"
+        p.write_text(json.dumps({"records": recs}))
+        paths.append(str(p))
+    return _tool().main(paths, str(tmp_path / f"{name}.out.json"))
+
+
+def test_parity_slack_groups_the_fp32_records_by_class(tmp_path):
+    tool = _tool()
+    for n in (None, 0, 1728, 10 ** 6 - 1, 10 ** 6, 10 ** 6 + 1, 10 ** 8):        # one rule, written in the tool and in the tests
+        assert tool.size_class(n) == pr.size_class(n), n
+    out = _run_tool(tmp_path, "new", NEW)
+    bars, meas = out["fp32_bars"], out["fp32_measured"]
+    assert set(bars) == {"2x/tiled", "1x/whole", "2x/tiled/smooth/large", "2x/tiled/smooth/small", "2x/tiled/random/small",
+                         "2x/tiled/random/large", "1x/whole/smooth/large"}
+    # large: min PSNR - 1.0 dB, max share x 1.25; max_lsb = measured + 1, capped at 2
+    assert meas["2x/tiled/smooth/large"]["comparisons"] == 2 and meas["2x/tiled/smooth/large"]["min_psnr_db"] == 71.3
+    assert bars["2x/tiled/smooth/large"] == {"max_lsb": 2, "min_psnr_db": 70.3, "max_differ_share": 0.006}
+    assert meas["2x/tiled/smooth/large"]["margins"] == {"psnr_db": 1.0, "differ_share_factor": 1.25}
+    assert bars["1x/whole/smooth/large"] == {"max_lsb": 2, "min_psnr_db": 71.7, "max_differ_share": round(0.0035 * 1.25, 5)}
+    # small: - 2.0 dB, + 0.015
+    assert bars["2x/tiled/smooth/small"] == {"max_lsb": 2, "min_psnr_db": 67.1, "max_differ_share": 0.023}
+    assert meas["2x/tiled/smooth/small"]["margins"] == {"psnr_db": 2.0, "differ_share": 0.015}
+    # the (model, route) entry: over all fp32-oracle records, as before
+    assert meas["2x/tiled"]["comparisons"] == 5 and meas["2x/tiled"]["max_lsb"] == 2
+    assert bars["2x/tiled"] == {"max_lsb": 2, "min_psnr_db": 58.8, "max_differ_share": 0.095}
+    # never looser, field by field: 0.08 x 1.25 = 0.1 would be; the (model, route) share holds instead
+    assert bars["2x/tiled/random/large"] == {"max_lsb": 2, "min_psnr_db": 59.9, "max_differ_share": 0.095}
+    for k, b in bars.items():
+        if k.count("/") == 3:
+            base = bars[k.rsplit("/", 2)[0]]
+            assert b["max_lsb"] <= base["max_lsb"] and b["min_psnr_db"] >= base["min_psnr_db"] and b["max_differ_share"] <= base["max_differ_share"], k
+
+
+def test_reports_without_classes_feed_only_the_model_route_entries(tmp_path):
+    new = _run_tool(tmp_path, "new", NEW)
+    both = _run_tool(tmp_path, "both", OLD, NEW)
+    old = _run_tool(tmp_path, "old", OLD)
+    assert set(old["fp32_bars"]) == {"2x/tiled", "1x/whole", "4x/whole"}                    # an old report alone: no class entry
+    assert set(both["fp32_bars"]) == set(new["fp32_bars"]) | {"4x/whole"}
+    assert both["fp32_bars"]["2x/tiled"] == {"max_lsb": 2, "min_psnr_db": 57.0, "max_differ_share": 0.095}   # the old record counts here
+    assert both["fp32_measured"]["2x/tiled"]["comparisons"] == 6
+    for k in new["fp32_bars"]:
+        if k.count("/") == 3:
+            assert both["fp32_measured"][k] == new["fp32_measured"][k], k                   # ... and nowhere in the classes
+            if k != "2x/tiled/random/large":                                                # (that one is held by the (model, route) bar)
+                assert both["fp32_bars"][k] == new["fp32_bars"][k], k
+    assert both["fp32_bars"]["2x/tiled/random/large"]["min_psnr_db"] == 59.9
+
+
+def test_fp32_bar_looks_up_the_class_and_falls_back(tmp_path, monkeypatch):
+    out = _run_tool(tmp_path, "new", NEW)
+    pr.slack("", "", "", 0)
+    monkeypatch.setattr(pr, "_SLACK", out)
+    base = {"max_lsb": 2, "min_psnr": 58.8, "max_share": 0.095}
+    assert pr.fp32_bar("2x", "tiled") == base
+    assert pr.fp32_bar("2x", "tiled", "smooth", 10 ** 6) == {"max_lsb": 2, "min_psnr": 70.3, "max_share": 0.006}
+    assert pr.fp32_bar("2x", "tiled", "smooth", 10 ** 6 - 1) == {"max_lsb": 2, "min_psnr": 67.1, "max_share": 0.023}
+    assert pr.fp32_bar("2x", "tiled", "ref_host", 10 ** 7) == base                           # a class without an entry
+    assert pr.fp32_bar("2x", "tiled", "smooth") == pr.fp32_bar("2x", "tiled", "smooth", None) == {"max_lsb": 2, "min_psnr": 67.1, "max_share": 0.023}
+    assert pr.fp32_bar("2x", "whole", "smooth", 10 ** 7) == {"max_lsb": 2, "min_psnr": 50.0}  # nothing measured: the fixed bars
+    assert pr.fp32_bar("chain", "tiled", "smooth", 10 ** 7) == {"max_lsb": 3, "min_psnr": 48.0}
+    # a class entry looser than its (model, route) entry (a hand-edited file) still cannot loosen anything
+    loose = json.loads(json.dumps(out))
+    loose["fp32_bars"]["2x/tiled/smooth/large"] = {"max_lsb": 3, "min_psnr_db": 40.0, "max_differ_share": 0.5}
+    monkeypatch.setattr(pr, "_SLACK", loose)
+    assert pr.fp32_bar("2x", "tiled", "smooth", 10 ** 6) == base
+
+
+def test_check_u8_records_the_class(records):
+    a = np.full((8, 8, 3), 7, np.uint8)
+    pr.check_u8("with", a, a, vs=FP32, max_lsb=0, input_class="random")
+    pr.check_u8("without", a, a, vs=FP32, max_lsb=0)
+    assert [r["input_class"] for r in records] == ["random", None]
+    lines = list(pr.summary_lines())
+    assert "[random/small]" in lines[0] and "[" not in lines[1].split("differ")[1]
+
+
+def test_committed_class_bars_are_derived_and_never_looser():
+    """tests/golden/parity_slack.json: the smooth / large entries the every-sample comparisons are held to exist, each is its
+    measured figure less the margin, and no class entry is looser than the (model, route) entry it refines"""
+    tool = _tool()
+    committed = json.load(open(os.path.join(ROOT, "tests", "golden", "parity_slack.json")))
+    bars, meas = committed["fp32_bars"], committed["fp32_measured"]
+    for k in ("2x/tiled/smooth/large", "4x/tiled/smooth/large", "1x/whole/smooth/large"):
+        assert bars[k]["min_psnr_db"] == pytest.approx(meas[k]["min_psnr_db"] - tool.FP32_LARGE_PSNR_MARGIN, abs=0.006), k
+        assert bars[k]["max_differ_share"] == pytest.approx(meas[k]["max_differ_share"] * tool.FP32_LARGE_SHARE_FACTOR, abs=1e-5), k
+    for k, b in bars.items():
+        if k.count("/") == 3:
+            base = bars[k.rsplit("/", 2)[0]]
+            assert b["max_lsb"] <= base["max_lsb"] and b["min_psnr_db"] >= base["min_psnr_db"] and b["max_differ_share"] <= base["max_differ_share"], k
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# without a GPU: the product-mode oracle stands in for the kernel
+# ------------------------------------------------------------------------------------------------------------------
+def test_the_mutant_writer_changes_one_array(tmp_path):
+    """(write_mutant_bin checks itself through the oracle's loader; here: the file differs from the shipped one in exactly the
+    bytes of that array, and an unknown kind is refused)"""
+    for key, kind in MUTANTS:
+        param, src = mutant_net.model_paths(key)
+        dst = str(tmp_path / f"{key}_{kind}.bin")
+        what, idx = mutant_net.write_mutant_bin(key, dst, kind, 0.25)
+        layout, n_conv, n_prelu = mutant_net.bin_layout(param, src)
+        assert (what, idx) == (("bias", n_conv - 1) if kind == "tail_bias" else ("slopes", n_prelu // 2))
+        (off, n), = [(o, c) for w, i, o, c in layout if (w, i) == (what, idx)]
+        a, b = np.fromfile(src, np.uint8), np.fromfile(dst, np.uint8)
+        changed = np.nonzero(a != b)[0]
+        assert a.size == b.size and changed.size and off <= changed.min() and changed.max() < off + 4 * n
+    with pytest.raises(AssertionError):
+        mutant_net.write_mutant_bin("2x", str(tmp_path / "x.bin"), "weights", 0.1)
+
+
+# whole frame for every net, and for 2x / 4x the reference tiling (960 / 10) the every-sample 1080p and 2160p comparisons use
+CPU_ROUTES = [(k, "whole", 0) for k in KEYS] + [(k, "tiled", 960) for k in ("2x", "4x")]
+
+
+@pytest.mark.parametrize("key,route,tile", CPU_ROUTES)
+def test_shipped_net_in_product_mode_passes_the_class_bar(key, route, tile):
+    pr.check_u8(f"{key} {FRAMES[key][1]}x{FRAMES[key][0]} smooth t{tile}: shipped net, product-mode oracle as the kernel's stand-in",
+                oracle_u8(key, product=True, tile=tile), oracle_u8(key, tile=tile), vs=FP32, model=None, route=None, input_class="smooth",
+                **class_bar(key, route))
+
+
+@pytest.mark.parametrize("kind", mutant_net.KINDS)
+@pytest.mark.parametrize("key,route,tile", CPU_ROUTES)
+def test_mutant_passes_the_model_route_bar_and_fails_the_class_bar(mutants, key, route, tile, kind):
+    """the gap, stated: the mutant -- at most 1 LSB from the shipped net's fp32 result -- is inside the (model, route) bar every
+    smooth frame was held to, and outside the committed bar of its class"""
+    name = f"{key} mutant {kind} {amount(key, kind)} t{tile} (KNOWN BAD), product-mode oracle as the kernel's stand-in"
+    got, want = oracle_u8(key, kind, product=True, tile=tile), oracle_u8(key, tile=tile)
+    old, new = pr.fp32_bar(key, route), class_bar(key, route)
+    worst, psnr, share = pr.check_u8(name + ": the (model, route) bar lets it through", got, want, vs=FP32, model=None, route=None, **old)
+    assert worst <= 1
+    if kind == "slope":                       # B's amount was chosen for this window
+        assert 2 * new["max_share"] <= share <= old["max_share"] / 2, (key, kind, share, new, old)
+    else:                                     # A: the offset's own figures, the stand-in's rounding noise on top
+        assert psnr == pytest.approx(A_PSNR, abs=0.1) and share == pytest.approx(A_SHARE, abs=0.001), (key, psnr, share)
+    with pytest.raises(AssertionError, match="PSNR"):
+        pr.check_u8(name + ": the class bar [expected to fail]", got, want, vs=FP32, model=None, route=None, input_class="smooth", **new)
+    with pytest.raises(AssertionError, match="differing share"):
+        pr.check_u8(name + ": the class bar's share alone [expected to fail]", got, want, vs=FP32, model=None, route=None,
+                    input_class="smooth", max_lsb=new["max_lsb"], max_share=new["max_share"])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# -m gpu: the kernels themselves on the mutant nets
+# ------------------------------------------------------------------------------------------------------------------
+def _load(uva, key, kind=None):
+    net = uva.Net()
+    net.opt.use_vulkan_compute = True
+    net.set_vulkan_device(0)
+    param, shipped = mutant_net.model_paths(key)
+    assert net.load_param(param) == 0, getattr(net, "last_error", "")
+    assert net.load_model(shipped if kind is None else mutant_bin(key, kind)) == 0, getattr(net, "last_error", "")
+    return net
+
+
+def _routes(key):
+    return (("whole", 0),) if key == "1x" else (("whole", 0), ("tiled", 64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", KEYS)
+def test_gpu_shipped_net_passes_the_class_bars(uva, key):
+    """the shipped net on the mutants' frame, whole and (2x, 4x) with 64 / 10 tiles, inside the bar of its class; and the GPU's
+    distance from the fp32 oracle next to the product-mode oracle's (recorded without a bar: it predicts the kernel to ~0.02 dB)"""
+    assert uva.get_gpu_count() > 0
+    net = _load(uva, key)
+    tag = f"{key} {FRAMES[key][1]}x{FRAMES[key][0]} smooth"
+    for route, ts in _routes(key):
+        got = net.process_u8(frame(key), tile_size=ts, border=10 if ts else 0)
+        # (measured first, asked for the class entry afterwards: this record is what tools/parity_slack.py derives that entry from)
+        pr.check_u8(f"{tag} t{ts}: shipped net", got, oracle_u8(key, tile=ts), vs=FP32, model=key, route=route, input_class="smooth",
+                    **pr.fp32_bar(key, route, "smooth", got.size))
+        if not ts:
+            _side_by_side(f"{tag}: shipped net", got, oracle_u8(key, product=True), oracle_u8(key))
+    assert all(has_class_bar(key, route) for route, _ in _routes(key)), "no class bar: the comparisons fell back to (model, route)"
+
+
+def _side_by_side(name, gpu, product, want):
+    g, p = mutant_net.distance_u8(gpu, want), mutant_net.distance_u8(product, want)
+    pr.record(name + ": GPU | product-mode oracle, both against the shipped net's fp32 result", kind="pair", vs=FP32, model=None, route=None,
+              gpu_max_lsb=g[0], gpu_psnr_db=g[1], gpu_differ_share=g[2], oracle_max_lsb=p[0], oracle_psnr_db=p[1], oracle_differ_share=p[2])
+    print(f"{name}: GPU {g[1]:.2f} dB, {100 * g[2]:.3f} % | product-mode oracle {p[1]:.2f} dB, {100 * p[2]:.3f} %")
+    # the stand-in has to predict the kernel inside the margin of a large class (1.0 dB, a factor 1.25 in the share); if it does
+    # not, that is a finding about the kernel or about the oracle's product mode, not a number to widen
+    assert abs(g[1] - p[1]) <= 1.0 and max(g[2], p[2]) <= 1.25 * min(g[2], p[2]), (name, "GPU", g, "product-mode oracle", p)
+    return g, p
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key,kind", MUTANTS)
+def test_gpu_mutant_fails_the_class_bar(uva, mutants, key, kind):
+    """the mutant .bin through ncnn.Net -- the shipped shapes, so every kernel runs as it does on the shipped net -- against the
+    SHIPPED net's fp32 oracle: inside the (model, route) bar, and check_u8 under the class bar raises, whole-frame and tiled"""
+    assert uva.get_gpu_count() > 0
+    net = _load(uva, key, kind)
+    tag = f"{key} mutant {kind} {amount(key, kind)} (KNOWN BAD)"
+    for route, ts in _routes(key):
+        got = net.process_u8(frame(key), tile_size=ts, border=10 if ts else 0)
+        want = oracle_u8(key, tile=ts)
+        pr.check_u8(f"{tag} t{ts}: the (model, route) bar lets it through", got, want, vs=FP32, model=None, route=None, **pr.fp32_bar(key, route))
+        with pytest.raises(AssertionError, match="PSNR"):
+            pr.check_u8(f"{tag} t{ts}: the class bar [expected to fail]", got, want, vs=FP32, model=None, route=None, input_class="smooth",
+                        **class_bar(key, route))
+        if not ts:
+            _side_by_side(tag, got, oracle_u8(key, kind, product=True), want)
