@@ -67,6 +67,9 @@ enum {
     UVO_PRELU_F16 = 8,   /* with UVO_WINOGRAD_F23: the PReLU behind such a convolution on fp16 values, as trunkw_kernel's
                             TW_ACT_F16 modes do it (csrc/uva_wino.h): the sum rounded to fp16, times the slope rounded to
                             fp16, product rounded to fp16, then max (slope <= 1) or min (slope > 1) of the two */
+    UVO_SUB_PRELU_F16 = 16, /* with UVO_F16_STORAGE: every PReLU of the 24-feature 1x net on fp16 values in the same way, as
+                            sub10_kernel and sub5_kernel evaluate it (csrc/uva_sub10.hip.h sub10_store) -- the u8 route of a
+                            whole frame; the float route and the pair path keep the fp32 PReLU */
 };
 
 typedef enum {
@@ -668,6 +671,7 @@ static int run_graph(const uvo_model* m, const float* in_chw, int h, int w, int 
         }
         case L_PRELU: { /* in-place in ncnn as well */
             if (last_wino && (flags & UVO_PRELU_F16)) prelu_f16(L, a);
+            else if (f16 && (flags & UVO_SUB_PRELU_F16) && m->nf == 24 && m->scale == 1 && m->nconv == 10) prelu_f16(L, a);
             else prelu(L, a, f16);
             snprintf(a->name, UVO_NAME, "%s", L->out[0]);
             if (convs - 1 == tap_conv) { result = a; tapped = 1; }

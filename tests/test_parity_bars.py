@@ -15,10 +15,11 @@ for 1x.  Measured on the CPU, oracle(mutant) against oracle(shipped), both fp32 
                  A, 0.03 level             B, amount            its distance             (shipped, product mode vs fp32)
     2x           63.35 dB, 3.01 %          0.016                64.59 dB, 2.26 %         71.29 dB, 0.48 %
     4x           63.35 dB, 3.01 %          0.016                63.51 dB, 2.90 %         69.90 dB, 0.66 %
-    1x           63.33 dB, 3.02 %          0.012                65.76 dB, 1.73 %         73.23 dB, 0.31 %   (540 x 960; 73.41 dB at 270 x 480)
+    1x           63.33 dB, 3.02 %          0.012                65.76 dB, 1.73 %         72.68 dB, 0.35 %   (540 x 960)
 
 (run in product mode the mutants land on the same figures against the shipped fp32 result: A 63.34 / 63.36 / 63.33 dB, B 64.50 dB
-2.31 %, 63.33 dB 3.02 %, 65.69 dB 1.75 %.)
+2.31 %, 63.33 dB 3.02 %, 65.67 dB 1.76 %.  The 1x figures: with sub10_kernel's PReLU on packed halves in the product mode,
+oracle SUB_PRELU_F16; without it the stand-in stood at 73.23 dB, 0.31 %, half a dB closer to fp32 than the kernel.)
 
 B's amounts were found by bisection on the share of differing samples, to land between twice the class bar's share and half of
 the (model, route) bar's (2x: 1.2 .. 3.2 %, 4x: 1.7 .. 4.5 %, 1x: 0.9 .. 2.6 %); the tests assert that window for B and A's figures
