@@ -48,7 +48,9 @@ extern "C" {
                                15 + chroma siting: + UVA_CHROMA_BILINEAR, UVA_CHROMA_CENTER, UVA_CHROMA_TOPLEFT in the colour word of
                                    every pixel-format entry (additive: colour words 0-3 mean what they meant)
                                15 + resampler: + uva_resize_taps, uva_resize, uva_resize_device, uva_net_submit_pix_sized, UVA_RESIZE_*
-                                   (additive: every earlier entry keeps its signature and its bytes) */
+                                   (additive: every earlier entry keeps its signature and its bytes)
+                               15 + repeated frames: + uva_frame_diff, uva_frame_diff_device, uva_net_set_skip_repeats,
+                                   uva_net_reset_reference, uva_net_skip_stats (additive: off unless asked for) */
 
 typedef struct uva_net uva_net;
 
@@ -230,6 +232,34 @@ int uva_resize(int device, const void* in, int h, int w, size_t in_stride, void*
  * uva_net_submit_u8's.  oh == h*s and ow == w*s: the resampler is skipped, the bytes are uva_net_submit_pix's. */
 long long uva_net_submit_pix_sized(uva_net* net, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
                                    int tile_size, int border, int oh, int ow, int filter, int bits);
+
+/* ---- repeated frames (csrc/uva_repeat.hip) ---------------------------------------------------
+ * Two dense h x w frames of one pixel format compared sample by sample in code values, as the input conversion reads them: bytes
+ * for the 8-bit formats, word >> 6 for p010le, word & 1023 for yuv420p10le / yuv422p10le (bits the converter ignores make no
+ * difference), whole words for bgr48le.  stats[0] = over, the samples with |a - b| > threshold; stats[1] = max_abs, the largest
+ * |a - b|; stats[2] = sad, the sum of |a - b|.  Integer sums: exact and the same on every call.  Null pointers, an unknown
+ * format, a size below 1 and a threshold outside 0 ... 65535 are refused with uva_last_error set. */
+/* Host to host on HIP device `device`, synchronous. */
+int uva_frame_diff(int device, const void* a, const void* b, int fmt, int h, int w, int threshold, unsigned long long* stats);
+/* The same with d_a / d_b resident in `device`'s HBM at 16-byte aligned addresses and complete (the call orders itself behind no
+ * stream of the caller's); stats is host memory.  Synchronous as well. */
+int uva_frame_diff_device(int device, const void* d_a, const void* d_b, int fmt, int h, int w, int threshold,
+                          unsigned long long* stats);
+/* Repeated frames on the pipelined route.  threshold -1: off, the default; 0 ... 65535: on -- every uva_net_submit_* entry except
+ * uva_net_submit_u8_png then compares the frame it is given with the net's KEPT frame, the last frame the net actually ran on
+ * (never merely the predecessor: with threshold 1 the frames x, x + 1, x + 2 run, skip, run).  A frame of which no sample differs
+ * from the kept frame's by more than threshold, submitted with the same h, w, in_fmt, out_fmt, colour word, bit depth, tile_size,
+ * border, output size and filter, is not computed: the kept frame's result bytes are downloaded into its `out` from a copy in
+ * HBM (the kept frame's own `out` plays no part, callers reuse their rings).  It still takes a slot and a ticket and is collected
+ * like any other.  Any other frame runs as always and becomes the kept frame.  With threshold 0 the stream of results is byte for
+ * byte what it is with skipping off.  Cost when on: the host waits in submit for the comparison, and the net holds one input and
+ * one result frame more in HBM.  The synchronous uva_net_process_* calls and the PNG entry ignore the setting.  Setting it (to
+ * any value) forgets the kept frame and zeroes the counters; another value is refused.  Host only: works with no GPU present. */
+int uva_net_set_skip_repeats(uva_net* net, int threshold);
+/* Forgets the kept frame: the next frame runs whatever it holds (a segment's start, a seek). */
+int uva_net_reset_reference(uva_net* net);
+/* Frames that went through the comparison's route since uva_net_set_skip_repeats, and how many of them were skipped. */
+int uva_net_skip_stats(uva_net* net, long long* submitted, long long* skipped);
 
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 

@@ -24,6 +24,8 @@ SYMBOLS = [
     "uva_net_process_u16_device", "uva_net_process_u16", "uva_net_submit_pix16", "uva_pix_convert16",
     # 15 + the resampler (additive as well)
     "uva_resize_taps", "uva_resize", "uva_resize_device", "uva_net_submit_pix_sized",
+    # 15 + repeated frames (additive as well)
+    "uva_frame_diff", "uva_frame_diff_device", "uva_net_set_skip_repeats", "uva_net_reset_reference", "uva_net_skip_stats",
 ]
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -89,6 +91,11 @@ def load():
     decl("uva_resize", [c_i, c_p, c_i, c_i, c_sz, c_p, c_i, c_i, c_sz, c_i, c_i])
     decl("uva_resize_device", [c_i, c_p, c_i, c_i, c_sz, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p])
     decl("uva_net_submit_pix_sized", [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i], ctypes.c_longlong)
+    decl("uva_frame_diff", [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p])
+    decl("uva_frame_diff_device", [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p])
+    decl("uva_net_set_skip_repeats", [c_p, c_i])
+    decl("uva_net_reset_reference", [c_p])
+    decl("uva_net_skip_stats", [c_p, pll, pll])
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

@@ -11,6 +11,7 @@
 #include "uva_kernels.hip.h"
 #include "uva_model.h"
 #include "uva_pixfmt.h"
+#include "uva_repeat.h"
 #include "uva_resize.h"
 #include "uva_png.hip.h"
 #include "uva_wino.h"
@@ -205,6 +206,40 @@ struct uva_net {
     size_t png_guess = 0;                // packed bytes of the last PNG frame collected: the next download's size
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     long long next_ticket = 0;
+    // uva_net_set_skip_repeats: the kept frame -- the last frame the net ran on -- with its packed input
+    // and the bytes that were downloaded for it, both in HBM; nothing here is allocated before a frame is submitted with
+    // threshold >= 0
+    struct Repeat {
+        int threshold = -1;              // -1: off
+        bool valid = false;              // there is a kept frame, key says with which arguments it ran
+        struct Key {
+            int h, w, in_fmt, out_fmt, colour, u16, tile_size, border, res_h, res_w, filter;
+            bool operator==(const Key& o) const
+            {
+                return h == o.h && w == o.w && in_fmt == o.in_fmt && out_fmt == o.out_fmt && colour == o.colour && u16 == o.u16 &&
+                       tile_size == o.tile_size && border == o.border && res_h == o.res_h && res_w == o.res_w && filter == o.filter;
+            }
+        } key = {};
+        uint8_t *d_in = nullptr, *d_res = nullptr;
+        size_t d_in_cap = 0, d_res_cap = 0;
+        FrameDiffStats *d_stats = nullptr, *h_stats = nullptr;    // the kernel's record, and where it is read back (page-locked)
+        hipEvent_t ev_stats = nullptr, ev_written = nullptr, ev_read = nullptr;
+        bool reads_pending = false;      // ev_read has been recorded since d_res was last written
+        long long submitted = 0, skipped = 0;
+    };
+    Repeat rep;
+    void release_repeat()                // the device is current, nothing of this net is running
+    {
+        if (rep.d_in) (void)hipFree(rep.d_in);
+        if (rep.d_res) (void)hipFree(rep.d_res);
+        if (rep.d_stats) (void)hipFree(rep.d_stats);
+        if (rep.h_stats) (void)hipHostFree(rep.h_stats);
+        for (hipEvent_t e : {rep.ev_stats, rep.ev_written, rep.ev_read})
+            if (e) (void)hipEventDestroy(e);
+        Repeat fresh;
+        fresh.threshold = rep.threshold; fresh.submitted = rep.submitted; fresh.skipped = rep.skipped;
+        rep = fresh;
+    }
     // profiling
     bool prof = false;
     std::vector<hipEvent_t> ev_free;        // timing-only events (no system-scope fence: take_event)
@@ -260,6 +295,7 @@ struct uva_net {
                 if (e) (void)hipEventDestroy(e);
             ps = PipeSlot();
         }
+        release_repeat();
         if (s_h2d) (void)hipStreamDestroy(s_h2d);
         if (s_d2h) (void)hipStreamDestroy(s_d2h);
         s_h2d = s_d2h = nullptr;
@@ -2190,6 +2226,7 @@ struct PixCtx {                          // per device: the conversions' own str
     hipStream_t stream = nullptr;
     uint8_t *d_in = nullptr, *d_mid = nullptr, *d_out = nullptr;
     size_t in_cap = 0, mid_cap = 0, out_cap = 0;
+    FrameDiffStats* d_stats = nullptr;   // uva_frame_diff's record
 };
 std::mutex g_pix_mu;
 PixCtx g_pix[16];
@@ -2204,6 +2241,7 @@ void pix_release_all()
         (void)hipStreamSynchronize(c.stream);
         for (uint8_t* p : {c.d_in, c.d_mid, c.d_out})
             if (p) (void)hipFree(p);
+        if (c.d_stats) (void)hipFree(c.d_stats);
         (void)hipStreamDestroy(c.stream);
         c = PixCtx();
     }
@@ -2903,9 +2941,11 @@ namespace {
 // (bgr24 included) is converted to and from u16 BGR
 // rs_oh, rs_ow > 0 and other than the net's result size (uva_net_submit_pix_sized): the net's BGR result is resampled to
 // rs_oh x rs_ow into d_rs on the net's stream, and what follows -- the output conversion, the download -- takes d_rs at that size
+// may_skip (the uva_net_submit_* entries, not the PNG one): with uva_net_set_skip_repeats on, a frame that repeats the kept frame
+// is not computed -- the kept frame's result is downloaded for it
 long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out, size_t out_stride,
                     int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
-                    int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0)
+                    int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0, bool may_skip = false)
 {
     if (check_dims(n, h, w)) return -1;
     if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
@@ -2967,7 +3007,54 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
                                 hipMemcpyHostToDevice, n->s_h2d), "H2D") ||
         tryhip(hipEventRecord(ps.ev_h2d, n->s_h2d), "hipEventRecord") ||
         tryhip(hipStreamWaitEvent(n->stream, ps.ev_h2d, 0), "hipStreamWaitEvent")) return -1;
-    if (u16) {
+    // what comes down: the BGR rows of d_out, or the packed frame d_pout -- as "rows" of one byte, so that a band is a byte
+    // range (collect copies it with one memcpy)
+    const uint8_t* d_src = pout ? ps.d_pout : d_res;
+    const size_t dl_bytes = pout ? pout_bytes : res_bytes;
+    // --skip-repeats: the frame is compared with the kept frame's input on the upload stream, behind its own upload, and the
+    // host waits for the three numbers -- the one blocking point of the route, and only with the option on
+    uva_net::Repeat& rp = n->rep;
+    const bool rp_on = may_skip && !png_ws && rp.threshold >= 0;
+    bool repeat = false;
+    if (rp_on) {
+        const uint8_t* d_packed = pin ? ps.d_pin : ps.d_in;
+        const size_t packed_bytes = pin ? pin_bytes : in_bytes;
+        const uva_net::Repeat::Key key = {h, w, in_fmt, out_fmt, colour, u16 ? 1 : 0, tile_size, border, res_h, res_w, rs ? rs_filter : 0};
+        ++rp.submitted;
+        if (!rp.d_stats) {
+            if (tryhip(hipMalloc((void**)&rp.d_stats, sizeof(FrameDiffStats)), "hipMalloc") ||
+                tryhip(hipHostMalloc((void**)&rp.h_stats, sizeof(FrameDiffStats), hipHostMallocDefault), "hipHostMalloc") ||
+                tryhip(hipEventCreateWithFlags(&rp.ev_stats, hipEventDisableTiming), "hipEventCreate") ||
+                tryhip(hipEventCreateWithFlags(&rp.ev_written, hipEventDisableTiming), "hipEventCreate") ||
+                tryhip(hipEventCreateWithFlags(&rp.ev_read, hipEventDisableTiming), "hipEventCreate")) return -1;
+        }
+        if (rp.valid && key == rp.key) {
+            if (tryhip(launch_frame_diff(n->s_h2d, rp.d_in, d_packed, packed_bytes, in_fmt, (unsigned)rp.threshold, rp.d_stats), "frame_diff") ||
+                tryhip(hipMemcpyAsync(rp.h_stats, rp.d_stats, sizeof(FrameDiffStats), hipMemcpyDeviceToHost, n->s_h2d), "D2H") ||
+                tryhip(hipEventRecord(rp.ev_stats, n->s_h2d), "hipEventRecord") ||
+                tryhip(hipEventSynchronize(rp.ev_stats), "hipEventSynchronize")) return -1;
+            repeat = rp.h_stats->over == 0;
+        }
+        if (!repeat) {
+            // this frame runs and becomes the kept frame.  Kept input: the comparisons read it and this copy replaces it on one
+            // stream, s_h2d, so they are ordered (the slot's own upload buffer is free again once the frame is collected).
+            rp.valid = false;
+            if (rp.d_in_cap < packed_bytes || rp.d_res_cap < dl_bytes) {      // (a buffer that moves: nothing may still use it)
+                if (tryhip(hipStreamSynchronize(n->s_h2d), "hipStreamSynchronize") || tryhip(hipStreamSynchronize(n->s_d2h), "hipStreamSynchronize") ||
+                    tryhip(hipStreamSynchronize(n->stream), "hipStreamSynchronize")) return -1;
+                if (grow_dev(&rp.d_in, &rp.d_in_cap, packed_bytes) || grow_dev(&rp.d_res, &rp.d_res_cap, dl_bytes)) return -1;
+                rp.reads_pending = false;
+            }
+            if (tryhip(hipMemcpyAsync(rp.d_in, d_packed, packed_bytes, hipMemcpyDeviceToDevice, n->s_h2d), "D2D")) return -1;
+            rp.key = key;
+        }
+    }
+    if (repeat) {
+        // the kept result's bytes, by a download alone: behind the copy that wrote them (ev_written, on the net's stream)
+        ++rp.skipped;
+        d_src = rp.d_res;
+        if (tryhip(hipStreamWaitEvent(n->s_d2h, rp.ev_written, 0), "hipStreamWaitEvent")) return -1;
+    } else if (u16) {
         if (pin && tryhip(launch_pix16_to_bgr(n->stream, in_fmt, colour, ps.d_pin, (uint16_t*)ps.d_in, h, w), "pix16_to_bgr")) return -1;
         if (uva_net_process_u16_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
         if (rs && launch_resize(n->stream, n->device, ps.d_out, h * s, w * s, out_row, ps.d_rs, res_h, res_w, res_row, rs_filter, 16, &rs_err)) { fail(rs_err); return -1; }
@@ -2983,8 +3070,17 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     // (device-to-device) kernel: 0.15 ms per 4K frame together
     if (png_ws && (png_launch(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png) ||
                    png_pack_launch(n->stream, ps.d_png, h * s, w * s))) return -1;
-    if (tryhip(hipEventRecord(ps.ev_done, n->stream), "hipEventRecord") ||
-        tryhip(hipStreamWaitEvent(n->s_d2h, ps.ev_done, 0), "hipStreamWaitEvent")) return -1;
+    if (!repeat && (tryhip(hipEventRecord(ps.ev_done, n->stream), "hipEventRecord") ||
+                    tryhip(hipStreamWaitEvent(n->s_d2h, ps.ev_done, 0), "hipStreamWaitEvent"))) return -1;
+    if (rp_on && !repeat) {
+        // Kept result: skipped frames download it on s_d2h, this copy overwrites it on the net's stream.  s_d2h runs in order,
+        // so the event behind the last such download (ev_read) stands for every download of the old contents still pending.
+        if (rp.reads_pending && tryhip(hipStreamWaitEvent(n->stream, rp.ev_read, 0), "hipStreamWaitEvent")) return -1;
+        if (tryhip(hipMemcpyAsync(rp.d_res, d_src, dl_bytes, hipMemcpyDeviceToDevice, n->stream), "D2D") ||
+            tryhip(hipEventRecord(rp.ev_written, n->stream), "hipEventRecord")) return -1;
+        rp.reads_pending = false;
+        rp.valid = true;
+    }
     if (png_ws) {
         // ... and the copy engine takes them to the caller's page-locked workspace while the next frame computes.  How
         // many bytes there are is only known on the device: as many as the previous frame had (+ 6 %) go now, collect
@@ -3004,10 +3100,6 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     size_t dst_stride = out_stride;
     ps.user_out = nullptr;
     ps.png_ws = nullptr;
-    // what comes down: the BGR rows of d_out, or the packed frame d_pout -- as "rows" of one byte, so that a band is a byte
-    // range (collect copies it with one memcpy)
-    const uint8_t* d_src = pout ? ps.d_pout : d_res;
-    const size_t dl_bytes = pout ? pout_bytes : res_bytes;
     if (!is_pinned_host(out)) {
         if (grow_host(&ps.h_out, &ps.h_out_cap, dl_bytes)) return -1;
         dst = ps.h_out; dst_stride = res_row;
@@ -3026,10 +3118,14 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
         }
     } else if (pout) {
         if (tryhip(hipMemcpyAsync(dst, d_src, dl_bytes, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return -1;
-    } else if (tryhip(hipMemcpy2DAsync(dst, dst_stride, d_res, res_row, res_row, (size_t)res_h, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) {
+    } else if (tryhip(hipMemcpy2DAsync(dst, dst_stride, d_src, res_row, res_row, (size_t)res_h, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) {
         return -1;
     }
     if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return -1;
+    if (repeat) {
+        if (tryhip(hipEventRecord(rp.ev_read, n->s_d2h), "hipEventRecord")) return -1;
+        rp.reads_pending = true;
+    }
     ps.busy = true;
     ps.ticket = n->next_ticket;
     return n->next_ticket++;
@@ -3040,7 +3136,7 @@ extern "C" {
 long long uva_net_submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out,
                             size_t out_stride, int tile_size, int border)
 {
-    return submit_u8(n, in, h, w, in_stride, out, out_stride, tile_size, border, nullptr, 0);
+    return submit_u8(n, in, h, w, in_stride, out, out_stride, tile_size, border, nullptr, 0, PIX_BGR24, PIX_BGR24, 0, false, 0, 0, 0, true);
 }
 
 long long uva_net_submit_u8_png(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, void* png_ws, size_t png_ws_bytes,
@@ -3105,7 +3201,7 @@ long long uva_net_submit_pix(uva_net* n, const void* in, int in_fmt, int h, int 
     const int s = uva_net_scale(n);
     if (s <= 0) { fail("net has no graph"); return -1; }
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3, (uint8_t*)out, (size_t)w * s * 3, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour);
+                     in_fmt, out_fmt, colour, false, 0, 0, 0, true);
 }
 
 long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
@@ -3117,7 +3213,7 @@ long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, in
     if (ensure_device(n) || check_u16_net(n)) return -1;
     const int s = uva_net_scale(n);
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 6, (uint8_t*)out, (size_t)w * s * 6, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, true);
+                     in_fmt, out_fmt, colour, true, 0, 0, 0, true);
 }
 
 int uva_net_process_u16(uva_net* n, const uint16_t* in, int h, int w, size_t in_stride, uint16_t* out, size_t out_stride,
@@ -3247,7 +3343,85 @@ long long uva_net_submit_pix_sized(uva_net* n, const void* in, int in_fmt, int h
     if (const char* e = resize_axis_error(w * s, ow, filter)) { fail(e); return -1; }
     const size_t bps = bits / 8;
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3 * bps, (uint8_t*)out, (size_t)ow * 3 * bps, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, bits == 16, oh, ow, filter);
+                     in_fmt, out_fmt, colour, bits == 16, oh, ow, filter, true);
+}
+
+// ---- repeated frames (csrc/uva_repeat.hip) ---------------------------------------------------------
+namespace {
+int frame_diff_check(const void* a, const void* b, int fmt, int h, int w, int threshold, const unsigned long long* stats)
+{
+    if (!a || !b || !stats) return fail("null frame pointer");
+    if (h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image size");
+    if (!pix_frame_bytes(fmt, 1, 1) || !frame_diff_sample(fmt, nullptr, nullptr)) return fail("unknown pixel format");
+    if (threshold < 0 || threshold > 65535) return fail("uva_frame_diff: the threshold is 0 ... 65535 code values");
+    return 0;
+}
+
+// the record of the frames d_a, d_b on the conversions' stream, read back and waited for (g_pix_mu held)
+int frame_diff_run(PixCtx& c, const void* d_a, const void* d_b, int fmt, int h, int w, int threshold, unsigned long long* stats)
+{
+    if (!c.d_stats) HIP_TRY(hipMalloc((void**)&c.d_stats, sizeof(FrameDiffStats)));
+    FrameDiffStats st;
+    HIP_TRY(launch_frame_diff(c.stream, d_a, d_b, pix_frame_bytes(fmt, h, w), fmt, (unsigned)threshold, c.d_stats));
+    HIP_TRY(hipMemcpyAsync(&st, c.d_stats, sizeof st, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    stats[0] = st.over; stats[1] = st.max_abs; stats[2] = st.sad;
+    return 0;
+}
+}  // namespace
+
+int uva_frame_diff(int device, const void* a, const void* b, int fmt, int h, int w, int threshold, unsigned long long* stats)
+{
+    if (frame_diff_check(a, b, fmt, h, w, threshold, stats)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = pix_frame_bytes(fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, bytes) || pix_grow(*c, &c->d_out, &c->out_cap, bytes)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, a, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_out, b, bytes, hipMemcpyHostToDevice, c->stream));
+    return frame_diff_run(*c, c->d_in, c->d_out, fmt, h, w, threshold, stats);
+}
+
+int uva_frame_diff_device(int device, const void* d_a, const void* d_b, int fmt, int h, int w, int threshold, unsigned long long* stats)
+{
+    if (frame_diff_check(d_a, d_b, fmt, h, w, threshold, stats)) return 1;
+    if ((((uintptr_t)d_a | (uintptr_t)d_b) & 15) != 0) return fail("uva_frame_diff_device: the frames must start at 16-byte aligned addresses");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    return frame_diff_run(*c, d_a, d_b, fmt, h, w, threshold, stats);
+}
+
+int uva_net_set_skip_repeats(uva_net* n, int threshold)
+{
+    if (!n) return fail("null net");
+    if (threshold < -1 || threshold > 65535) return fail("uva_net_set_skip_repeats: the threshold is -1 (off) or 0 ... 65535 code values");
+    n->rep.threshold = threshold;
+    n->rep.valid = false;
+    n->rep.submitted = n->rep.skipped = 0;
+    if (threshold < 0 && (n->rep.d_in || n->rep.d_stats)) {     // off again: the kept frame's buffers go (there is a device: they exist)
+        HIP_TRY(hipSetDevice(n->device));
+        for (hipStream_t st : {n->s_h2d, n->s_d2h, n->stream})
+            if (st) HIP_TRY(hipStreamSynchronize(st));
+        n->release_repeat();
+    }
+    return 0;
+}
+
+int uva_net_reset_reference(uva_net* n)
+{
+    if (!n) return fail("null net");
+    n->rep.valid = false;
+    return 0;
+}
+
+int uva_net_skip_stats(uva_net* n, long long* submitted, long long* skipped)
+{
+    if (!n) return fail("null net");
+    if (submitted) *submitted = n->rep.submitted;
+    if (skipped) *skipped = n->rep.skipped;
+    return 0;
 }
 
 size_t uva_png_workspace_bytes(int h, int w)
@@ -3361,7 +3535,8 @@ int uva_net_collect_u8(uva_net* n, long long ticket)
 int uva_net_process_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out,
                        size_t out_stride, int tile_size, int border)
 {
-    const long long t = uva_net_submit_u8(n, in, h, w, in_stride, out, out_stride, tile_size, border);
+    // (not through uva_net_submit_u8: the synchronous calls take no part in uva_net_set_skip_repeats)
+    const long long t = submit_u8(n, in, h, w, in_stride, out, out_stride, tile_size, border, nullptr, 0);
     if (t < 0) return 1;
     if (uva_net_collect_u8(n, t)) return 1;
     resolve_events(n);

@@ -260,6 +260,24 @@ def resize(img, size, filter="lanczos", gpu=0, out=None):
     return out
 
 
+def frame_diff(a, b, fmt, h, w, threshold=0, gpu=0, device=False):
+    """Two dense h x w frames of `fmt` compared sample by sample on HIP device `gpu` (include/uva.h uva_frame_diff; DESIGN.md
+    section 7.8) -> (over, max_abs, sad): the samples with |a - b| > threshold, the largest |a - b| and the sum of |a - b|, in
+    code values as the input conversion reads them (p010le: word >> 6; yuv420p10le / yuv422p10le: word & 1023).
+    device=True: a and b are raw device pointers (ints) of frames in that GPU's HBM (uva_frame_diff_device)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    stats = (ctypes.c_ulonglong * 3)()
+    L = _lib.load()
+    if device:
+        _lib.check(L.uva_frame_diff_device(int(gpu), ctypes.c_void_p(int(a)), ctypes.c_void_p(int(b)), PIX_FORMATS_ALL[fmt], int(h), int(w),
+                                           int(threshold), stats))
+    else:
+        fa, fb = _pix_frame(a, fmt, h, w, "a"), _pix_frame(b, fmt, h, w, "b")
+        _lib.check(L.uva_frame_diff(int(gpu), fa.ctypes.data, fb.ctypes.data, PIX_FORMATS_ALL[fmt], int(h), int(w), int(threshold), stats))
+    return int(stats[0]), int(stats[1]), int(stats[2])
+
+
 class Ticket:
     """One frame in flight on the pipelined host route; keeps its buffers alive."""
 
@@ -519,6 +537,23 @@ class Net:
         _lib.check(self._L.uva_resize_device(self.device_index, ctypes.c_void_p(d_in), h, w, in_stride or w * 3 * bps, ctypes.c_void_p(d_out),
                                              oh, ow, out_stride or ow * 3 * bps, _resize_filter(filter), int(bit_depth),
                                              after._h if after is not None else None, self._h))
+
+    def set_skip_repeats(self, threshold):
+        """Repeated frames on the pipelined route (include/uva.h uva_net_set_skip_repeats): None or -1
+        turns it off (the default), 0 ... 65535 is the largest difference in code values at which a frame submitted with
+        submit_u8 / submit_pix still repeats the KEPT frame -- the last one the net ran on -- and gets that frame's result
+        bytes instead of a run of its own.  Forgets the kept frame and zeroes skip_stats().  Needs no GPU."""
+        _lib.check(self._L.uva_net_set_skip_repeats(self._h, -1 if threshold is None else int(threshold)))
+
+    def reset_reference(self):
+        """Forgets the kept frame: the next frame runs whatever it holds (a segment's start, a seek)."""
+        _lib.check(self._L.uva_net_reset_reference(self._h))
+
+    def skip_stats(self):
+        """-> (submitted, skipped) since set_skip_repeats"""
+        a, b = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.check(self._L.uva_net_skip_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def collect_u8(self, ticket):
         """Waits for the frame of `ticket` and returns its u8 result array (submit_u8, submit_pix) or its PNG workspace

@@ -146,6 +146,25 @@ def load_net(stem, gpu, model_path):
     return net
 
 
+def _real_nets(lanes_spec):
+    """the nets of a worker's chain, or of a list of chains (the denoise stage is no net)"""
+    chains = lanes_spec if lanes_spec and isinstance(lanes_spec[0], list) else [lanes_spec]
+    return [net for chain in chains for net, _ in chain if not isinstance(net, tuple)]
+
+
+def set_skip_repeats(lanes_spec, threshold):
+    """--skip-repeats on every net of every lane (Net.set_skip_repeats).  In the `-m a` chain the second
+    stage finds the repeats itself: the first stage's outputs for them are equal bytes."""
+    for net in _real_nets(lanes_spec):
+        net.set_skip_repeats(threshold)
+
+
+def skip_summary(lanes_spec):
+    """'skipped k of n': the net runs --skip-repeats saved, of the frames submitted to the nets (every net of a chain counts)"""
+    stats = [net.skip_stats() for net in _real_nets(lanes_spec)]
+    return "skipped %d of %d" % (sum(k for _, k in stats), sum(n for n, _ in stats))
+
+
 def read_exact(f, view):
     """Fill `view` from f; returns False on a clean EOF before the first byte, raises on a torn frame."""
     got = 0
@@ -537,6 +556,10 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
 
     def work(k):
         try:
+            # a segment starts with no kept frame (--skip-repeats; each lane has nets of its own, so this is for clarity)
+            for net in _real_nets(lanes_spec[k]):
+                if hasattr(net, "reset_reference"):
+                    net.reset_reference()
             if counts[k] == 0:
                 if outs is not None:
                     opener(outs[k], "wb").close()
@@ -771,9 +794,16 @@ def main(argv=None):
     ap.add_argument("--resize-filter", default="lanczos", choices=list(ncnn.RESIZE_FILTERS),
                     help="the resampler's filter (default lanczos: sinc(x) sinc(x/3); bicubic: Keys, a = -0.5; bilinear); widened when "
                          "an axis shrinks")
+    ap.add_argument("--skip-repeats", type=int, nargs="?", const=0, default=None, metavar="T",
+                    help="do not run a net on a frame that repeats the last frame the net ran on: its result is delivered again "
+                         "(animation on twos and threes, screen captures, telecined film).  T (default 0: exact, the output is "
+                         "byte for byte what it is without the option) is the largest difference in code values, 0 ... 65535, "
+                         "at which a sample still counts as equal; DESIGN.md section 7.8")
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
+    if a.skip_repeats is not None and not 0 <= a.skip_repeats <= 65535:
+        ap.error("--skip-repeats takes a threshold T of 0 ... 65535 code values, not %d" % a.skip_repeats)
     out_size = None
     if a.out_size is not None and a.out_scale is not None:
         ap.error("--out-size and --out-scale exclude each other")
@@ -873,8 +903,17 @@ def main(argv=None):
     one_file_on_tmpfs = (len(nets) > 1 and len(outs) == 1 and a.output != "-" and
                          filesystem_type(os.path.dirname(os.path.abspath(a.output)) or ".") in ("tmpfs", "ramfs") and
                          os.environ.get("UVA_RAW_TMPFS_SEGMENTS") != "1")
-    if nets and (len(ins) > 1 or len(outs) > 1 or (len(nets) > 1 and not a.round_robin and not one_file_on_tmpfs and
-                                                   a.input != "-" and a.output != "-" and regular)):
+    segments = bool(nets) and (len(ins) > 1 or len(outs) > 1 or (len(nets) > 1 and not a.round_robin and not one_file_on_tmpfs and
+                                                                  a.input != "-" and a.output != "-" and regular))
+    summary = lambda n: "%d frames" % n                                               # noqa: E731
+    if a.skip_repeats is not None and nets:
+        if len(nets) > 1 and not segments:
+            ap.error("--skip-repeats with %d -g entries on a route that deals the frames out one by one (pipes, --round-robin, one "
+                     "output file on tmpfs): consecutive frames land in different lanes and nothing would ever repeat.  Use one -g "
+                     "entry, or file-to-file segments" % len(nets))
+        set_skip_repeats(nets, a.skip_repeats)
+        summary = lambda n: "%d frames, %s" % (n, skip_summary(nets))                 # noqa: E731
+    if segments:
         if not regular:
             ap.error("-i / -o lists take regular files")
         scale_total = 1
@@ -882,7 +921,7 @@ def main(argv=None):
             scale_total *= 1 if isinstance(net, tuple) else net.scale
         n = stream_segments(ins if len(ins) > 1 else ins[0], outs if len(outs) > 1 else outs[0], a.height, a.width, nets, scale_total,
                             max_frames=a.frames, write_threads=wthreads, pix=pix)
-        print("%d frames" % n, file=sys.stderr)
+        print(summary(n), file=sys.stderr)
         ncnn.destroy_gpu_instance()
         return 0
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
@@ -904,7 +943,7 @@ def main(argv=None):
             fout.close()
             if not ok and created and os.path.isfile(a.output):
                 os.remove(a.output)                # half a stream under the name of a whole one helps nobody
-    print("%d frames" % n, file=sys.stderr)
+    print(summary(n), file=sys.stderr)
     ncnn.destroy_gpu_instance()
     return 0
 
