@@ -75,7 +75,7 @@ def test_config5_frame_2160p_reference_tiling(net2x, oracle_models, oracle):
 
 
 def test_schedule_limits_fail_with_messages(net2x, uva, oracle):
-    """The encodings of the tile schedules have limits (uva_api.hip: 64 planes per frame, 255 tile columns
+    """The encodings of the tile schedules have limits (csrc/uva_plan.cpp build_planes / build_sched4: 64 planes per frame, 255 tile columns
     and 4095 4-row tile rows per plane): beyond them the call fails with a message, it does not compute."""
     from upscale_video_amd import _lib
     img = oracle.synthetic_frame(90, 90)

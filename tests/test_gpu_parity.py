@@ -176,7 +176,7 @@ def test_sign_carry_between_launches_changes_no_bit(uva, nets, oracle, key, monk
 @pytest.mark.parametrize("key", ["2x", "4x"])
 def test_folded_last_strips_change_no_bit(uva, nets, oracle, key, monkeypatch):
     """trunkw_kernel walks the narrow last strips of two planes of one size in ONE pass (pairs 0..7: the first plane, 8..15: the
-    second; csrc/uva_api.hip build_trunkw_schedule).  The arithmetic per pixel is untouched, so the frame must equal, BYTE FOR
+    second; csrc/uva_plan.cpp build_trunkw_schedule).  The arithmetic per pixel is untouched, so the frame must equal, BYTE FOR
     BYTE, the one a net with UVA_TW_FOLD=0 gives -- the bar that catches what the LSB / dB bars let through (the first version
     folded strips of 13 and 14 columns, whose last producer pair reads two raw columns of the other plane: one wrong column per
     plane, inside every tolerance).  Frames of 2T x 2T pixels with tile T give four planes of (T + 10)^2: last strips of 1, 5,

@@ -1,5 +1,5 @@
 """Row lists of sub10_kernel (the whole 24-feature 1x net in one launch, csrc/uva_kernels.hip.h) -- built on the
-host by build_sub10_rows (csrc/uva_api.hip), fetched through the host-only hook uva_debug_sub10_rows and checked
+host by build_sub10_rows (csrc/uva_plan.cpp), fetched through the host-only hook uva_debug_sub10_rows and checked
 for the properties the kernel relies on: every output pixel is written exactly once, every written row is
 preceded by the 10 warm-up rows and followed by the 9 rows the layers in between still need, rows inside a
 segment are consecutive, and the work is balanced."""

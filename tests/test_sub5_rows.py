@@ -1,5 +1,5 @@
 """Row lists of sub5_kernel (the 1x net as two launches of five layers, two pipelines = a PAIR of 54-column strips per workgroup;
-csrc/uva_sub5.hip.h) -- built on the host by build_sub5_rows (csrc/uva_api.hip), fetched through the host-only hook
+csrc/uva_sub5.hip.h) -- built on the host by build_sub5_rows (csrc/uva_plan.cpp), fetched through the host-only hook
 uva_debug_sub5_rows and checked for what both launches rely on: every pixel of the plane lies in the written-out rows and the
 valid columns of exactly one (segment, strip); every segment has its 5 warm-up rows above and 5 below; rows inside a segment are
 consecutive; the work is balanced; consecutive ranges go to one XCD."""

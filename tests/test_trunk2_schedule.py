@@ -1,5 +1,5 @@
-"""CPU test of the step lists trunk2_kernel (two fused trunk layers per launch) walks: decoded through
-the host-only hook uva_debug_trunk2_schedule and checked for the properties the kernel relies on --
+"""CPU test of the step lists trunk2_kernel (two fused trunk layers per launch) walks: built on the host by
+build_trunk2_schedule (csrc/uva_plan.cpp), decoded through the host-only hook uva_debug_trunk2_schedule and checked for the properties the kernel relies on --
 every plane pixel is produced by exactly one consumer step, the two producer blocks a consumer step
 reads are the right rows of the same strip, the producer's zero masks are exactly "outside the plane",
 the dummy look-ahead entries are inert, and the work is spread evenly."""
@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
-SW = 30   # csrc/uva_kernels.hip.h T2_SW
+SW = 30   # csrc/uva_plan.h T2_SW
 
 
 def schedule(uva, h, w, tile, border, grid=256):

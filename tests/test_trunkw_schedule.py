@@ -1,5 +1,6 @@
 """CPU test of the step lists trunkw_kernel (two fused trunk layers per launch as Winograd F(2,3),
-csrc/uva_wino.hip.h) walks, decoded through the host-only hook uva_debug_trunkw_schedule.
+csrc/uva_wino.hip.h) walks, built on the host by build_trunkw_schedule
+(csrc/uva_plan.cpp) and decoded through the host-only hook uva_debug_trunkw_schedule.
 
 The kernel keeps state from step to step -- the producer's ring of six transformed input rows, of which a
 step replaces four, and the ring of ten intermediate rows between producer and consumer -- so the test does
@@ -13,7 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
-SW = 30          # csrc/uva_wino.hip.h TW_SW
+SW = 30          # csrc/uva_plan.h TW_SW
 PAD = 2          # TW_PAD_STEPS
 AROWS, BROWS = 6, 10
 

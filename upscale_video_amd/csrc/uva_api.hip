@@ -11,6 +11,7 @@
 #include "uva_kernels.hip.h"
 #include "uva_model.h"
 #include "uva_pixfmt.h"
+#include "uva_plan.h"
 #include "uva_repeat.h"
 #include "uva_resize.h"
 #include "uva_png.hip.h"
@@ -57,18 +58,11 @@ int fail(const std::string& msg)
             return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                    \
     } while (0)
 
-struct Workspace {
+struct Workspace : PlaneLayout {        // (planes, tile counts, act_pixels, guard_bytes: the planner's, uva_plan.h)
     int h = 0, w = 0, tile_size = 0, border = 0;
-    std::vector<PlaneDesc> planes;
     PlaneDesc* d_planes = nullptr;
     uint4* d_sched4 = nullptr;   // per 4-row work tile: trunk_kernel's schedule entry (ConvArgs::sched4)
-    int ntiles = 0;     // 8-row work tiles (head, tail, 24-feature trunk)
-    int ntiles4 = 0;    // 4-row work tiles (64-feature trunk kernel)
-    size_t act_pixels = 0;
-    // Activation buffers: act_base[i] is the allocation, act[i] = act_base[i] + guard the planes.  The guard
-    // (zeroed, never written) on both ends keeps trunk2_kernel's halo reads of rows -2 / h+4 and columns
-    // -2 / pitch+1 -- which only ever feed pixels it masks to zero -- inside the allocation.
-    size_t guard_bytes = 0;
+    // Activation buffers: act_base[i] is the allocation, act[i] = act_base[i] + guard_bytes the planes.
     size_t alloc_bytes = 0;      // device bytes of the two activation buffers (the cache's LRU budget)
     char* act_base[2] = {nullptr, nullptr};
     _Float16* act[2] = {nullptr, nullptr};
@@ -96,29 +90,11 @@ struct Workspace {
     int max_stepsw = 0;
     void release()
     {
-        if (d_planes) (void)hipFree(d_planes);
-        if (d_sched4) (void)hipFree(d_sched4);
-        if (d_steps2) (void)hipFree(d_steps2);
-        if (d_nsteps2) (void)hipFree(d_nsteps2);
-        if (d_stepsw) (void)hipFree(d_stepsw);
-        if (d_nstepsw) (void)hipFree(d_nstepsw);
-        d_stepsw = nullptr;
-        d_nstepsw = nullptr;
-        for (auto& q : d_rows10) { if (q) (void)hipFree(q); q = nullptr; }
-        for (auto& q : d_nrows10) { if (q) (void)hipFree(q); q = nullptr; }
-        if (d_rows5) (void)hipFree(d_rows5);
-        if (d_nrows5) (void)hipFree(d_nrows5);
-        if (d_mid5) (void)hipFree(d_mid5);
-        d_rows5 = nullptr;
-        d_nrows5 = nullptr;
-        d_mid5 = nullptr;
-        d_sched4 = nullptr;
-        d_steps2 = nullptr;
-        d_nsteps2 = nullptr;
-        if (act_base[0]) (void)hipFree(act_base[0]);
-        if (act_base[1]) (void)hipFree(act_base[1]);
-        d_planes = nullptr;
-        act_base[0] = act_base[1] = nullptr;
+        auto drop = [](auto*& p) { if (p) (void)hipFree(p); p = nullptr; };
+        drop(d_planes); drop(d_sched4); drop(d_steps2); drop(d_nsteps2); drop(d_stepsw); drop(d_nstepsw);
+        for (auto& q : d_rows10) drop(q);
+        for (auto& q : d_nrows10) drop(q);
+        drop(d_rows5); drop(d_nrows5); drop(d_mid5); drop(act_base[0]); drop(act_base[1]);
         act[0] = act[1] = nullptr;
     }
 };
@@ -461,107 +437,6 @@ int launch_trunk(uva_net* n, const Workspace* ws, ConvArgs ca, int ablate = 0)
     return launch_conv(n, 0, ca);
 }
 
-// Step lists of trunk2_kernel for one frame geometry: every plane is cut into 30-column strips, a strip
-// is a column of 4-row steps walked top to bottom, and the sequence (plane, strip, step) is dealt out to
-// the workgroups in contiguous ranges of (nearly) equal length.  A range that ends inside a strip ends a
-// SEGMENT there: k producer steps yield 4k - 2 output rows (the consumer needs one intermediate row below
-// its last output row), the next segment starts on the following row and recomputes two intermediate rows.
-// Consecutive ranges go to the workgroups of one XCD (block b runs on XCD b % 8).
-int build_trunk2_schedule(const std::vector<PlaneDesc>& planes, int grid, size_t guard_bytes, std::vector<Trunk2Step>& steps,
-                          std::vector<int>& nsteps, int* max_steps, bool narrow_ok = true)
-{
-    constexpr int PIXB = 128;
-    struct Seg { int plane, x0, ya, rows, k; };
-    // ranges of equal COST: a step of a narrow strip (<= 14 columns: one fragment column instead of two) runs its k-loops
-    // with half the MFMAs and is counted as 8 tenths of a step (measured: its phases are then bounded by the other group's epilogue)
-    constexpr int COST = 10, COST_NARROW = 8;
-    auto step_cost = [&](const PlaneDesc& p, int x0) { return (narrow_ok && p.w - x0 <= 14) ? COST_NARROW : COST; };
-    long long total = 0;
-    for (const auto& p : planes)
-        for (int x0 = 0; x0 < p.w; x0 += T2_SW) total += (long long)((p.h + 2 + 3) / 4) * step_cost(p, x0);
-    std::vector<std::vector<Seg>> per_wg;
-    int L = (int)std::max<long long>(4 * COST, (total + grid - 1) / grid);
-    for (;; ++L) {
-        per_wg.assign(1, {});
-        int cap = L;
-        auto next_wg = [&]() { per_wg.emplace_back(); cap = L; };
-        for (size_t pi = 0; pi < planes.size(); ++pi) {
-            const PlaneDesc& p = planes[pi];
-            for (int x0 = 0; x0 < p.w; x0 += T2_SW) {
-                const int c = step_cost(p, x0);
-                int y = 0;
-                while (y < p.h) {
-                    const int need = (p.h - y + 2 + 3) / 4, fit = cap / c;
-                    if (need <= fit) {
-                        per_wg.back().push_back({(int)pi, x0, y, p.h - y, need});
-                        cap -= need * c;
-                        y = p.h;
-                    } else if (fit < 2) {
-                        next_wg();
-                        continue;
-                    } else {
-                        per_wg.back().push_back({(int)pi, x0, y, 4 * fit - 2, fit});
-                        y += 4 * fit - 2;
-                        cap = 0;
-                    }
-                    if (cap < COST_NARROW) next_wg();
-                }
-            }
-        }
-        while (!per_wg.empty() && per_wg.back().empty()) per_wg.pop_back();
-        if ((int)per_wg.size() <= grid) break;
-    }
-    int most = 0;
-    for (const auto& v : per_wg) {
-        int k = 0;
-        for (const Seg& sg : v) k += sg.k;
-        most = std::max(most, k);
-    }
-    *max_steps = most;
-    const int stride = most + T2_PAD_STEPS;
-    steps.assign((size_t)grid * stride, Trunk2Step{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)});
-    nsteps.assign(grid, 0);
-    const int per_xcd = grid / 8;
-    for (size_t c = 0; c < per_wg.size(); ++c) {
-        const int b = (int)(c % per_xcd) * 8 + (int)(c / per_xcd);
-        Trunk2Step* out = steps.data() + (size_t)b * stride;
-        int g = 0;
-        for (const Seg& sg : per_wg[c]) {
-            const PlaneDesc& p = planes[sg.plane];
-            const int nb = (sg.rows + 3) / 4;
-            for (int j = 0; j < sg.k; ++j, ++g) {
-                const int yA = sg.ya - 1 + 4 * j;                        // first intermediate row of the block
-                // halo origin = input pixel (yA - 1, x0 - 2) = array position (yA, x0 - 1)
-                const long long ao = (long long)guard_bytes +
-                                     ((long long)p.act_off + (long long)yA * p.pitch + (sg.x0 - 1)) * PIXB;
-                if (ao < 0 || (ao >> 40)) return fail("activation buffer too large for the step encoding");
-                unsigned rmask = 0;
-                for (int r = 0; r < 4; ++r)
-                    if (yA + r >= 0 && yA + r < p.h) rmask |= 1u << r;
-                const unsigned c_lo = sg.x0 == 0 ? 1 : 0, c_hi = (unsigned)std::min(32, p.w - sg.x0 + 1);
-                // strips of at most 14 columns need only the first of the two 16-column fragment columns (bit 25, both halves)
-                const unsigned narrow = (p.w - sg.x0 <= 14 && narrow_ok) ? 1u << 25 : 0u;
-                out[g].a = make_uint4((unsigned)ao, (unsigned)(ao >> 32) | (rmask << 8) | (c_lo << 12) | (c_hi << 18) | (1u << 24) | narrow,
-                                      (unsigned)(p.pitch * PIXB), (unsigned)sg.plane);
-                if (j < nb) {
-                    const int yo = sg.ya + 4 * j;
-                    const long long bo = (long long)guard_bytes +
-                                         ((long long)p.act_off + (long long)(yo + 1) * p.pitch + (sg.x0 + 1)) * PIXB;
-                    const unsigned vy = (unsigned)std::min(4, sg.ya + sg.rows - yo), vx = (unsigned)std::min(T2_SW, p.w - sg.x0);
-                    out[g].b = make_uint4((unsigned)bo, (unsigned)(bo >> 32) | (vy << 8) | (vx << 11) | (1u << 24) | narrow,
-                                          (unsigned)(p.pitch * PIXB), (unsigned)sg.plane);
-                }
-            }
-        }
-        nsteps[b] = g;
-        for (int k = 0; k < T2_PAD_STEPS; ++k) {      // harmless re-fetches of the last tile, nothing active
-            out[g + k].a = out[g - 1].a;
-            out[g + k].a.y &= 0xffu;
-        }
-    }
-    return 0;
-}
-
 int launch_trunk2(uva_net* n, const Workspace* ws, const Trunk2Args& a)
 {
     const size_t lds = trunk2_lds_bytes<64>();
@@ -572,176 +447,6 @@ int launch_trunk2(uva_net* n, const Workspace* ws, const Trunk2Args& a)
     }
     hipLaunchKernelGGL(kfn, dim3(ws->grid2), dim3(512), lds, n->stream, a);
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Step lists of trunkw_kernel: the same 30-column strips and 4-row steps as trunk2_kernel's, but a segment that is not its
-// workgroup's first starts WITHOUT the two input rows a step shares with the one above it: its first producer step yields
-// two valid intermediate rows and its first consumer step nothing, so k steps yield 4 (k - 1) output rows and a segment
-// of `rows` output rows beginning at row r0 has its first intermediate block at row r0 - 3 (a workgroup's first segment:
-// r0 - 1, 4k - 2 rows -- the kernel's prologue fetches all six rows).  Step g of a segment:
-//   producer: intermediate rows yA .. yA+3, yA = r0 - 3 (- 1) + 4g, from the new input rows yA+1 .. yA+4 (+ the two above);
-//   consumer: output rows yA-1 .. yA+2, of which those inside the segment are stored, from the last two rows of block g-1
-//             and block g.
-int build_trunkw_schedule(const std::vector<PlaneDesc>& planes, int grid, size_t guard_bytes, std::vector<Trunk2Step>& steps,
-                          std::vector<int>& nsteps, int* max_steps)
-{
-    constexpr int PIXB = 128;
-    // A workgroup's FIRST segment can start with the two input rows a step shares with the one above it (the kernel's prologue
-    // fetches and transforms them: entry bit 25) and then yields 4k - 2 rows in k steps instead of 4 (k - 1).  The prologue is
-    // 0.3 % of a launch (measured), so this is done only where it shortens the LONGEST list (UVA_TW_SIX: 1 always, 0 never):
-    // a whole 1080p frame 69 -> 68 steps (+0.5 %), the reference tiling 73 -> 73 (left alone).  Also measured and not kept
-    // (profiles/r04_ab_results.txt block 20): segments at the TOP of a plane starting on two zero rows written by the consumers
-    // -- with the six-row starts 73 -> 72 steps at the reference tiling, and the same launch time: a segment's fill step, in
-    // which the consumers idle, costs about half a step.
-    const char* const sx = uva::debug_env("UVA_TW_SIX");
-    const int six_mode = sx ? (std::atoi(sx) != 0 ? 1 : 0) : -1;
-    const bool top_ok = false;
-    // FOLDED last strips (round 5).  A strip costs its 16 MFMA pair columns whatever its width, and 970 columns (the reference
-    // tiling's planes at 1080p) are 32 strips and a THIRD of one: 2 % of a launch's steps compute nothing.  Where two planes have
-    // the same size and a last strip of at most TW_FOLD_MAXW = 12 columns, ONE strip walk does both: lanes with pair index 0..7
-    // work on the first plane, 8..15 on the second.  Why 12 and not 14: v output columns need the intermediate columns -1..v,
-    // i.e. the producers' pairs 0..(v + 1) / 2, and producer pair p reads raw columns 2p..2p+3 -- for v = 13, 14 that is pair 7
-    // and raw columns 16, 17, which in a folded step hold the SECOND plane's first pixels (the first version allowed 14: one
-    // wrong column per 74-wide plane, 1.4 dB on the 128x96 probe, inside every parity bar -- found by the probe's PSNR moving,
-    // now pinned by a byte-for-byte fold on / off test).  Everything in between (rings,
-    // transforms, k-loops) is pair-wise and does not care; what differs is where the raw rows come from and where the results
-    // go: the second plane's addresses = the first's + a constant (entry .w = that constant - 2048, flags a.y bit 27 / b.y
-    // bit 25; csrc/uva_wino.hip.h).  UVA_TW_FOLD=0: off.
-    // UVA_TW_FOLD=14 (debug opt-in only) is that first version, kept as the known-bad schedule the tests' structured-error
-    // detector must catch (tests/test_gpu_parity.py::test_structure_detector_catches_the_fold14_schedule).
-    const char* const sf = uva::debug_env("UVA_TW_FOLD");
-    const bool fold_ok = !sf || std::atoi(sf) != 0;
-    const int fold_maxw = sf && std::atoi(sf) == 14 ? 14 : TW_FOLD_MAXW;
-    std::vector<int> fold_partner(planes.size(), -1);
-    std::vector<char> folded_away(planes.size(), 0);
-    auto last_x0 = [](const PlaneDesc& p) { return ((p.w + TW_SW - 1) / TW_SW - 1) * TW_SW; };
-    if (fold_ok)
-        for (size_t i = 0; i < planes.size(); ++i) {
-            if (fold_partner[i] >= 0 || folded_away[i] || planes[i].w - last_x0(planes[i]) > fold_maxw) continue;
-            for (size_t j = i + 1; j < planes.size(); ++j) {
-                if (fold_partner[j] >= 0 || folded_away[j]) continue;
-                const long long delta = ((long long)planes[j].act_off - (long long)planes[i].act_off) * PIXB;
-                if (planes[j].h == planes[i].h && planes[j].w == planes[i].w && planes[j].pitch == planes[i].pitch && delta > 2048 && delta < (1ll << 31)) {
-                    fold_partner[i] = (int)j;
-                    folded_away[j] = 1;
-                    break;
-                }
-            }
-        }
-    struct Seg { int plane, x0, r0, rows, k; bool full, zero; int fold; };
-    long long total = 0;
-    for (const auto& p : planes) total += (long long)((p.w + TW_SW - 1) / TW_SW) * ((p.h + 3) / 4 + 1);     // (an upper bound: full segments need less)
-    auto pack = [&](bool six_ok, std::vector<std::vector<Seg>>& per_wg) {
-        int L = (int)std::max<long long>(4, (total + grid - 1) / grid - 2);
-        for (;; ++L) {
-            per_wg.assign(1, {});
-            int cap = L;
-            auto next_wg = [&]() { per_wg.emplace_back(); cap = L; };
-            for (size_t pi = 0; pi < planes.size(); ++pi) {
-                const PlaneDesc& p = planes[pi];
-                for (int x0 = 0; x0 < p.w; x0 += TW_SW) {
-                    const bool last = x0 + TW_SW >= p.w;
-                    if (last && folded_away[pi]) continue;          // done by its partner's last strip
-                    const int fold = last ? fold_partner[pi] : -1;
-                    int y = 0;
-                    while (y < p.h) {
-                        const bool zero = top_ok && y == 0;
-                        const bool full = zero || (six_ok && per_wg.back().empty() && fold < 0);     // (the prologue's six-row fetch knows one plane)
-                        const int need = full ? (p.h - y + 2 + 3) / 4 : (p.h - y + 3) / 4 + 1;
-                        if (need <= cap) {
-                            per_wg.back().push_back({(int)pi, x0, y, p.h - y, need, full, zero, fold});
-                            cap -= need;
-                            y = p.h;
-                        } else if (cap < 3) {             // a segment of fewer than 3 steps is mostly pipeline fill
-                            next_wg();
-                            continue;
-                        } else {
-                            const int rows = full ? 4 * cap - 2 : 4 * (cap - 1);
-                            per_wg.back().push_back({(int)pi, x0, y, rows, cap, full, zero, fold});
-                            y += rows;
-                            cap = 0;
-                        }
-                        if (cap < 1) next_wg();
-                    }
-                }
-            }
-            while (!per_wg.empty() && per_wg.back().empty()) per_wg.pop_back();
-            if ((int)per_wg.size() <= grid) break;
-        }
-        int most = 0;
-        for (const auto& v : per_wg) {
-            int k = 0;
-            for (const Seg& sg : v) k += sg.k;
-            most = std::max(most, k);
-        }
-        return most;
-    };
-    std::vector<std::vector<Seg>> per_wg;
-    if (six_mode >= 0) pack(six_mode != 0, per_wg);
-    else {
-        std::vector<std::vector<Seg>> with_six;
-        const int m0 = pack(false, per_wg), m1 = pack(true, with_six);
-        if (m1 < m0) per_wg.swap(with_six);
-    }
-    int most = 0;
-    for (const auto& v : per_wg) {
-        int k = 0;
-        for (const Seg& sg : v) k += sg.k;
-        most = std::max(most, k);
-    }
-    *max_steps = most;
-    const int stride = most + TW_PAD_STEPS;
-    steps.assign((size_t)grid * stride, Trunk2Step{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)});
-    nsteps.assign(grid, 0);
-    const int per_xcd = grid / 8;
-    for (size_t c = 0; c < per_wg.size(); ++c) {
-        const int b = (int)(c % per_xcd) * 8 + (int)(c / per_xcd);
-        Trunk2Step* out = steps.data() + (size_t)b * stride;
-        int g = 0;
-        for (const Seg& sg : per_wg[c]) {
-            const PlaneDesc& p = planes[sg.plane];
-            for (int j = 0; j < sg.k; ++j, ++g) {
-                const int yA = sg.r0 - (sg.full ? 1 : 3) + 4 * j;        // first intermediate row of the block
-                // first new input row = pixel (yA + 1, x0 - 2) = array position (yA + 2, x0 - 1)
-                const long long ao = (long long)guard_bytes +
-                                     ((long long)p.act_off + (long long)(yA + 2) * p.pitch + (sg.x0 - 1)) * PIXB;
-                if (ao < 0 || (ao >> 40)) return fail("activation buffer too large for the step encoding");
-                unsigned rmask = 0;
-                for (int r = 0; r < 4; ++r)
-                    if (yA + r >= 0 && yA + r < p.h) rmask |= 1u << r;
-                const unsigned c_lo = sg.x0 == 0 ? 1 : 0, c_hi = (unsigned)std::min(32, p.w - sg.x0 + 1);
-                // (a folded step carries its first plane's index in .z's top byte: the debug view's, the kernel masks it off)
-                if (sg.fold >= 0 && sg.plane > 255) return fail("trunkw schedule: more than 256 planes with folded strips");
-                // a folded step: the second plane's pixels lie fold_add + 2048 bytes behind the first's
-                const unsigned fold_add = sg.fold >= 0 ? (unsigned)(((long long)planes[sg.fold].act_off - (long long)p.act_off) * PIXB - 2048) : 0u;
-                out[g].a = make_uint4((unsigned)ao, (unsigned)(ao >> 32) | (rmask << 8) | (c_lo << 12) | (c_hi << 18) | (1u << 24) |
-                                                    ((sg.full && !sg.zero && j == 0) ? 1u << 25 : 0u) | ((sg.zero && j == 0) ? 1u << 26 : 0u) |
-                                                    (sg.fold >= 0 ? 1u << 27 : 0u),
-                                      (unsigned)(p.pitch * PIXB) | (sg.fold >= 0 ? (unsigned)sg.plane << 24 : 0u),   // (folded: .w is taken, the
-                                      sg.fold >= 0 ? fold_add : (unsigned)sg.plane);                                // plane index rides in .z's top byte)
-                if ((unsigned)(p.pitch * PIXB) >> 24) return fail("plane too wide for the step encoding");
-                // the consumer step stores rows yo + [v0, v1) of its four (yo = yA - 1): those inside the segment
-                const int yo = yA - 1;
-                const int v0 = std::max(0, sg.r0 - yo), v1 = std::min(4, sg.r0 + sg.rows - yo);
-                if (v1 > v0) {
-                    const long long bo = (long long)guard_bytes +
-                                         ((long long)p.act_off + (long long)(yo + 1) * p.pitch + (sg.x0 + 1)) * PIXB;
-                    if (bo < 0 || (bo >> 40)) return fail("activation buffer too large for the step encoding");
-                    const unsigned vx = (unsigned)std::min(TW_SW, p.w - sg.x0);
-                    out[g].b = make_uint4((unsigned)bo, (unsigned)(bo >> 32) | ((unsigned)v1 << 8) | (vx << 11) | ((unsigned)v0 << 17) | (1u << 24) |
-                                                        (sg.fold >= 0 ? 1u << 25 : 0u),
-                                          (unsigned)(p.pitch * PIXB) | (sg.fold >= 0 ? (unsigned)sg.plane << 24 : 0u),
-                                          sg.fold >= 0 ? fold_add : (unsigned)sg.plane);
-                }
-            }
-        }
-        nsteps[b] = g;
-        for (int k = 0; k < TW_PAD_STEPS && g > 0; ++k) {     // harmless re-fetches of the last rows, nothing active
-            out[g + k].a = out[g - 1].a;
-            out[g + k].a.y &= 0xffu;
-        }
-    }
     return 0;
 }
 
@@ -760,99 +465,6 @@ int launch_trunkw(uva_net* n, const Workspace* ws, TrunkwArgs& a, int i, bool in
     return 0;
 }
 
-// Row descriptors of sub10_kernel for an h x w frame: 60-column strips, the sequence (strip, row) dealt out to the
-// workgroups in contiguous ranges; every range (segment) starts 10 rows early and ends 9 rows late (the rows the
-// layers in between need), only its own rows are written out.
-// `frames` frames of the one geometry in one launch: the sequence runs over (frame, strip, row); a row's frame sits in z >> 8.
-int build_sub10_rows(int h, int w, int frames, int grid, std::vector<uint4>& rows, std::vector<int>& nrows, int* max_rows)
-{
-    if (frames < 1 || frames > S10_MAXB || h > S10_MAX_H) return 2;
-    const int ns1 = (w + S10_VALID - 1) / S10_VALID;
-    const int ns = ns1 * frames;             // k = frame * ns1 + strip
-    const long long total = (long long)ns * h;
-    struct Seg { int k, y0, n; };
-    std::vector<std::vector<Seg>> per_wg;
-    int D = (int)std::max<long long>(2 * S10_NL + 4, (total + grid - 1) / grid + 2 * S10_NL);
-    for (;; ++D) {
-        per_wg.assign(1, {});
-        int cap = D;
-        for (int k = 0; k < ns; ++k) {
-            int y = 0;
-            while (y < h) {
-                if (cap < 2 * S10_NL + 1) { per_wg.emplace_back(); cap = D; }
-                const int n = std::min(h - y, cap - 2 * S10_NL);
-                per_wg.back().push_back({k, y, n});
-                cap -= n + 2 * S10_NL;
-                y += n;
-            }
-        }
-        if ((int)per_wg.size() <= grid) break;
-    }
-    if (D > S10_MAX_ROWS) return 2;      // row table does not fit the kernel's LDS copy: the caller takes the per-pair path
-    *max_rows = D;
-    rows.assign((size_t)grid * D, make_uint4(0, 0, 0, 0));
-    nrows.assign(grid, 0);
-    const int per_xcd = grid / 8;
-    for (size_t c = 0; c < per_wg.size(); ++c) {
-        const int b = (int)(c % per_xcd) * 8 + (int)(c / per_xcd);
-        uint4* out = rows.data() + (size_t)b * D;
-        int g = 0;
-        for (const Seg& sg : per_wg[c])
-            for (int y = sg.y0 - S10_NL; y < sg.y0 + sg.n + S10_NL; ++y, ++g) {
-                // w = how many rows y lies outside the segment's own rows (0 inside, 1..10): layer s (0 = the first) is needed on rows
-                // with w <= 9 - s only, and the kernel's wave of that layer skips the others
-                const int dist = y < sg.y0 ? sg.y0 - y : y >= sg.y0 + sg.n ? y - (sg.y0 + sg.n - 1) : 0;
-                out[g] = make_uint4((unsigned)y, (unsigned)((sg.k % ns1) * S10_VALID - S10_NL), (dist == 0 ? 1u : 0u) | ((unsigned)(sg.k / ns1) << 8),
-                                    (unsigned)dist);
-            }
-        nrows[b] = g;
-    }
-    return 0;
-}
-
-// Row descriptors of sub5_kernel (both launches use the same lists): PAIRS of 54-column strips, the sequence (pair, row) dealt
-// out to the workgroups in contiguous ranges; every range (segment) starts 5 rows early and ends 5 rows late -- what five
-// 3x3 layers need --, only its own rows are written out.  x = plane row, y = plane column of computed column 0 of the pair's
-// FIRST strip (the second one's is S5_VALID further right), z = 1: written out.
-int build_sub5_rows(int h, int w, int grid, std::vector<uint4>& rows, std::vector<int>& nrows, int* max_rows)
-{
-    const int np = (w + S5_PAIRW - 1) / S5_PAIRW;
-    const long long total = (long long)np * h;
-    struct Seg { int k, y0, n; };
-    std::vector<std::vector<Seg>> per_wg;
-    int D = (int)std::max<long long>(2 * S5_NL + 4, (total + grid - 1) / grid + 2 * S5_NL);
-    for (;; ++D) {
-        per_wg.assign(1, {});
-        int cap = D;
-        for (int k = 0; k < np; ++k) {
-            int y = 0;
-            while (y < h) {
-                if (cap < 2 * S5_NL + 1) { per_wg.emplace_back(); cap = D; }
-                const int n = std::min(h - y, cap - 2 * S5_NL);
-                per_wg.back().push_back({k, y, n});
-                cap -= n + 2 * S5_NL;
-                y += n;
-            }
-        }
-        if ((int)per_wg.size() <= grid) break;
-    }
-    if (D > S5_MAX_ROWS) return 2;       // the row table does not fit the kernel's LDS copy: the caller takes another path
-    *max_rows = D;
-    rows.assign((size_t)grid * D, make_uint4(0, 0, 0, 0));
-    nrows.assign(grid, 0);
-    const int per_xcd = grid / 8;
-    for (size_t c = 0; c < per_wg.size(); ++c) {
-        const int b = (int)(c % per_xcd) * 8 + (int)(c / per_xcd);
-        uint4* out = rows.data() + (size_t)b * D;
-        int g = 0;
-        for (const Seg& sg : per_wg[c])
-            for (int y = sg.y0 - S5_NL; y < sg.y0 + sg.n + S5_NL; ++y, ++g)
-                out[g] = make_uint4((unsigned)y, (unsigned)(sg.k * S5_PAIRW - S5_NL), (y >= sg.y0 && y < sg.y0 + sg.n) ? 1u : 0u, 0u);
-        nrows[b] = g;
-    }
-    return 0;
-}
-
 // the 24-feature 1x net as two launches of five layers (u8 route, one plane); returns 2 when the frame is too large for it
 int launch_sub5(uva_net* n, Workspace* ws, const void* src, size_t src_stride, void* dst, size_t dst_stride,
                 unsigned long long* dbg = nullptr, int dbg_part = -1)
@@ -862,7 +474,10 @@ int launch_sub5(uva_net* n, Workspace* ws, const void* src, size_t src_stride, v
         std::vector<uint4> rows;
         std::vector<int> nrows;
         ws->grid5 = std::max(8, (n->ncu / 8) * 8);
-        if (build_sub5_rows(ws->h, ws->w, ws->grid5, rows, nrows, &ws->max_rows5)) {
+        std::string err;
+        const int rc = build_sub5_rows(ws->h, ws->w, ws->grid5, rows, nrows, &ws->max_rows5, err);
+        if (rc == 1) return fail(err);
+        if (rc) {
             ws->sub5_unfit = true;
             return 2;
         }
@@ -914,7 +529,10 @@ int launch_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_
         std::vector<uint4> rows;
         std::vector<int> nrows;
         ws->grid10 = std::max(8, (n->ncu / 8) * 8);
-        if (build_sub10_rows(ws->h, ws->w, frames, ws->grid10, rows, nrows, &ws->max_rows10[bi])) {
+        std::string err;
+        const int rc = build_sub10_rows(ws->h, ws->w, frames, ws->grid10, rows, nrows, &ws->max_rows10[bi], err);
+        if (rc == 1) return fail(err);
+        if (rc) {
             if (frames == 1) ws->sub10_unfit = true;
             ws->sub10_max_batch = frames - 1;
             return 2;
@@ -1162,62 +780,26 @@ int ensure_device(uva_net* n)
     return 0;
 }
 
-// Plane list of one frame: the reference's tile grid (upscale_processing.py:398-434, :499-516)
-// or a single whole-frame plane (apply_model, :263-288).
-int build_planes(int h, int w, int tile_size, int border, std::vector<PlaneDesc>& out)
+// The planner's A/B switches, read per call (the tests flip them between calls): UVA_TW_SIX (1 / 0: six-row segment starts
+// always / never), UVA_TW_FOLD (0: no folded last strips; 14: the known-bad first version), UVA_T2_NARROW (0: every
+// trunk2 strip computes both fragment columns).
+PlanOpts plan_switches()
 {
-    out.clear();
-    auto add = [&](int sy0, int sx0, int ph, int pw, int cy0, int cy1, int cx0, int cx1) {
-        PlaneDesc p;
-        std::memset(&p, 0, sizeof p);
-        p.h = ph; p.w = pw;
-        p.src_y0 = sy0; p.src_x0 = sx0;
-        p.core_y0 = cy0; p.core_y1 = cy1; p.core_x0 = cx0; p.core_x1 = cx1;
-        out.push_back(p);
-    };
-    if (tile_size <= 0) {
-        add(0, 0, h, w, 0, h, 0, w);
-    } else {
-        const int tiles_x = (w + tile_size - 1) / tile_size, tiles_y = (h + tile_size - 1) / tile_size;
-        if ((long long)tiles_x * tiles_y > MAX_PLANES) return fail("frame needs more than 64 tiles");
-        for (int ty = 0; ty < tiles_y; ++ty)
-            for (int tx = 0; tx < tiles_x; ++tx) {
-                const int y0 = ty * tile_size, x0 = tx * tile_size;
-                const int y1 = std::min(y0 + tile_size, h), x1 = std::min(x0 + tile_size, w);
-                const int by0 = y0 >= border ? border : 0, by1 = y1 <= h - border ? border : 0;
-                const int bx0 = x0 >= border ? border : 0, bx1 = x1 <= w - border ? border : 0;
-                add(y0 - by0, x0 - bx0, (y1 + by1) - (y0 - by0), (x1 + bx1) - (x0 - bx0), by0, by0 + (y1 - y0),
-                    bx0, bx0 + (x1 - x0));
-            }
+    PlanOpts o;
+    if (const char* e = uva::debug_env("UVA_TW_SIX")) o.tw.six_mode = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = uva::debug_env("UVA_TW_FOLD")) {
+        o.tw.fold = std::atoi(e) != 0;
+        if (std::atoi(e) == 14) o.tw.fold_maxw = 14;
     }
-    return 0;
+    if (const char* e = uva::debug_env("UVA_T2_NARROW")) o.narrow_ok = std::atoi(e) != 0;
+    return o;
 }
 
-// Work-tile counts, activation pitch and array offset of every plane (see PlaneDesc).
-void layout_planes(std::vector<PlaneDesc>& planes, size_t* pixels, int* ntiles, int* ntiles4)
-{
-    size_t pix = 0;
-    int tiles = 0, tiles4 = 0;
-    for (auto& p : planes) {
-        p.nty = (p.h + TH - 1) / TH;
-        p.ntx = (p.w + TW - 1) / TW;
-        p.pitch = p.ntx * TW + 2;
-        p.tile_begin = tiles;
-        p.nty4 = (p.h + 3) / 4;
-        p.tile_begin4 = tiles4;
-        p.act_off = (long long)pix;
-        tiles += p.nty * p.ntx;
-        tiles4 += p.nty4 * p.ntx;
-        pix += (size_t)(p.nty * TH + 2) * p.pitch;
-    }
-    if (pixels) *pixels = pix;
-    if (ntiles) *ntiles = tiles;
-    if (ntiles4) *ntiles4 = tiles4;
-}
+static_assert(Geo<64, 4>::PIXB == PLAN_PIXB, "the planner's byte offsets are those of the 64-feature activations");
 
 int get_workspace(uva_net* n, int h, int w, int tile_size, int border, Workspace** out)
 {
-    if (tile_size <= 0) { tile_size = 0; border = 0; }
+    normalize_tiling(tile_size, border);
     for (auto it = n->wss.begin(); it != n->wss.end(); ++it)
         if (it->h == h && it->w == w && it->tile_size == tile_size && it->border == border) {
             n->wss.splice(n->wss.begin(), n->wss, it);
@@ -1226,42 +808,15 @@ int get_workspace(uva_net* n, int h, int w, int tile_size, int border, Workspace
         }
     Workspace ws;
     ws.h = h; ws.w = w; ws.tile_size = tile_size; ws.border = border;
-    if (build_planes(h, w, tile_size, border, ws.planes)) return 1;
-    size_t pix = 0;
-    int tiles = 0, tiles4 = 0;
-    layout_planes(ws.planes, &pix, &tiles, &tiles4);
-    ws.ntiles = tiles;
-    ws.ntiles4 = tiles4;
-    ws.act_pixels = pix;
     // everything that can be refused is checked BEFORE anything is allocated
-    std::vector<uint4> sched4;
-    std::vector<Trunk2Step> steps2, stepsw;
-    std::vector<int> nsteps2, nstepsw;
-    int max_pitch = 0;
-    for (auto& p : ws.planes) max_pitch = std::max(max_pitch, p.pitch);
-    ws.guard_bytes = (size_t)8 * max_pitch * n->g.nf * 2;
-    if (n->g.nf == 64) {
-        using G4 = Geo<64, 4>;
-        sched4.reserve((size_t)tiles4);
-        for (size_t pi = 0; pi < ws.planes.size(); ++pi) {
-            const PlaneDesc& p = ws.planes[pi];
-            if (p.nty4 >= 4096 || p.ntx >= 256) return fail("frame too large for the tile schedule encoding");
-            for (int ty = 0; ty < p.nty4; ++ty)
-                for (int tx = 0; tx < p.ntx; ++tx) {
-                    const unsigned long long off =
-                        ((unsigned long long)p.act_off + (unsigned long long)(ty * 4) * p.pitch + (unsigned long long)tx * TW) * G4::PIXB;
-                    if (off >> 40) return fail("activation buffer too large for the tile schedule encoding");
-                    const int vy = std::min(4, p.h - ty * 4), vx = std::min(TW, p.w - tx * TW);
-                    sched4.push_back(make_uint4((unsigned)off, (unsigned)(off >> 32) | ((unsigned)pi << 8), (unsigned)(p.pitch * G4::PIXB),
-                                                (unsigned)(vx | (vy << 6) | (tx << 9) | (ty << 17))));
-                }
-        }
-        ws.grid2 = std::max(8, (n->ncu / 8) * 8);
-        const char* const nv = uva::debug_env("UVA_T2_NARROW");      // (A/B switch: 0 = every strip computes both fragment columns)
-        if (build_trunk2_schedule(ws.planes, ws.grid2, ws.guard_bytes, steps2, nsteps2, &ws.max_steps2, !(nv && std::atoi(nv) == 0))) return 1;
-        if (build_trunkw_schedule(ws.planes, ws.grid2, ws.guard_bytes, stepsw, nstepsw, &ws.max_stepsw)) return 1;
-    }
-    const size_t bytes = pix * (size_t)n->g.nf * 2 + 2 * ws.guard_bytes;
+    FramePlan plan;
+    std::string err;
+    if (n->g.nf == 64) ws.grid2 = std::max(8, (n->ncu / 8) * 8);
+    if (plan_frame(h, w, tile_size, border, n->g.nf, ws.grid2, plan_switches(), plan, err)) return fail(err);
+    static_cast<PlaneLayout&>(ws) = plan;
+    ws.max_steps2 = plan.max_steps2;
+    ws.max_stepsw = plan.max_stepsw;
+    const size_t bytes = ws.act_pixels * (size_t)n->g.nf * 2 + 2 * ws.guard_bytes;
     // LRU over the cached geometries, by bytes (the fused route keeps one workspace per frame size, the
     // float / Extractor route one per distinct tile shape -- 9 for a 4000x2200 frame): plenty fit 288 GB
     constexpr size_t CACHE_BYTES = (size_t)96 << 30;
@@ -1288,20 +843,13 @@ int get_workspace(uva_net* n, int h, int w, int tile_size, int border, Workspace
         ws.act[i] = (_Float16*)(ws.act_base[i] + ws.guard_bytes);
     }
     ws.alloc_bytes = 2 * bytes;
-    HIP_TRY(hipMalloc((void**)&ws.d_planes, ws.planes.size() * sizeof(PlaneDesc)));
-    HIP_TRY(hipMemcpyAsync(ws.d_planes, ws.planes.data(), ws.planes.size() * sizeof(PlaneDesc),
-                           hipMemcpyHostToDevice, n->stream));
+    if (upload(&ws.d_planes, ws.planes.data(), ws.planes.size() * sizeof(PlaneDesc), n->stream)) return 1;
     if (n->g.nf == 64) {
-        HIP_TRY(hipMalloc((void**)&ws.d_sched4, sched4.size() * sizeof(uint4)));
-        HIP_TRY(hipMemcpyAsync(ws.d_sched4, sched4.data(), sched4.size() * sizeof(uint4), hipMemcpyHostToDevice, n->stream));
-        HIP_TRY(hipMalloc((void**)&ws.d_steps2, steps2.size() * sizeof(Trunk2Step)));
-        HIP_TRY(hipMalloc((void**)&ws.d_nsteps2, nsteps2.size() * sizeof(int)));
-        HIP_TRY(hipMemcpyAsync(ws.d_steps2, steps2.data(), steps2.size() * sizeof(Trunk2Step), hipMemcpyHostToDevice, n->stream));
-        HIP_TRY(hipMemcpyAsync(ws.d_nsteps2, nsteps2.data(), nsteps2.size() * sizeof(int), hipMemcpyHostToDevice, n->stream));
-        HIP_TRY(hipMalloc((void**)&ws.d_stepsw, stepsw.size() * sizeof(Trunk2Step)));
-        HIP_TRY(hipMalloc((void**)&ws.d_nstepsw, nstepsw.size() * sizeof(int)));
-        HIP_TRY(hipMemcpyAsync(ws.d_stepsw, stepsw.data(), stepsw.size() * sizeof(Trunk2Step), hipMemcpyHostToDevice, n->stream));
-        HIP_TRY(hipMemcpyAsync(ws.d_nstepsw, nstepsw.data(), nstepsw.size() * sizeof(int), hipMemcpyHostToDevice, n->stream));
+        if (upload(&ws.d_sched4, plan.sched4.data(), plan.sched4.size() * sizeof(uint4), n->stream)) return 1;
+        if (upload(&ws.d_steps2, plan.steps2.data(), plan.steps2.size() * sizeof(Trunk2Step), n->stream)) return 1;
+        if (upload(&ws.d_nsteps2, plan.nsteps2.data(), plan.nsteps2.size() * sizeof(int), n->stream)) return 1;
+        if (upload(&ws.d_stepsw, plan.stepsw.data(), plan.stepsw.size() * sizeof(Trunk2Step), n->stream)) return 1;
+        if (upload(&ws.d_nstepsw, plan.nstepsw.data(), plan.nstepsw.size() * sizeof(int), n->stream)) return 1;
     }
     HIP_TRY(hipStreamSynchronize(n->stream));
     guard.w = nullptr;
@@ -2194,8 +1742,9 @@ int generic_process_u8_device(uva_net* n, const void* d_in, int h, int w, size_t
                               int tile_size, int border)
 {
     std::vector<PlaneDesc> planes;
-    if (tile_size <= 0) { tile_size = 0; border = 0; }
-    if (build_planes(h, w, tile_size, border, planes)) return 1;
+    normalize_tiling(tile_size, border);
+    std::string err;
+    if (build_planes(h, w, tile_size, border, planes, err)) return fail(err);
     std::vector<int> batch_of;
     generic_plan_batches(planes, generic_batch_on(), generic_batch_pixels(), batch_of);
     std::vector<std::vector<PlaneJob>> batches;
@@ -3867,27 +3416,22 @@ int uva_net_debug_packed_weights(uva_net* n, int conv_idx, uint16_t* out, size_t
     return 0;
 }
 
-int uva_debug_trunk2_schedule(int h, int w, int tile_size, int border, int grid, uint32_t* steps_words,
-                              size_t capacity_words, size_t* needed_words, int* nsteps, int* stride,
-                              long long* plane_info, int max_planes, int* nplanes, long long* guard_bytes)
+// the two trunk step-list hooks: the frame's plan as get_workspace gets it, one of its step lists copied out
+static int debug_trunk_schedule(bool wino, int h, int w, int tile_size, int border, int grid, uint32_t* steps_words,
+                                size_t capacity_words, size_t* needed_words, int* nsteps, int* stride,
+                                long long* plane_info, int max_planes, int* nplanes, long long* guard_bytes)
 {
     if (h <= 0 || w <= 0 || grid < 8 || grid % 8) return fail("bad argument");
-    std::vector<PlaneDesc> planes;
-    if (tile_size <= 0) { tile_size = 0; border = 0; }
-    if (build_planes(h, w, tile_size, border, planes)) return 1;
-    size_t pix = 0;
-    int max_pitch = 0;
-    layout_planes(planes, &pix, nullptr, nullptr);
-    for (auto& p : planes) max_pitch = std::max(max_pitch, p.pitch);
-    const size_t guard = (size_t)8 * max_pitch * 128;
-    std::vector<Trunk2Step> steps;
-    std::vector<int> ns;
-    int max_steps = 0;
-    if (build_trunk2_schedule(planes, grid, guard, steps, ns, &max_steps)) return 1;
+    FramePlan plan;
+    std::string err;
+    if (plan_frame(h, w, tile_size, border, 64, grid, plan_switches(), plan, err)) return fail(err);
+    const std::vector<PlaneDesc>& planes = plan.planes;
+    const std::vector<Trunk2Step>& steps = wino ? plan.stepsw : plan.steps2;
+    const std::vector<int>& ns = wino ? plan.nstepsw : plan.nsteps2;
     if (needed_words) *needed_words = steps.size() * 8;
-    if (stride) *stride = max_steps + T2_PAD_STEPS;
+    if (stride) *stride = wino ? plan.max_stepsw + TW_PAD_STEPS : plan.max_steps2 + T2_PAD_STEPS;
     if (nplanes) *nplanes = (int)planes.size();
-    if (guard_bytes) *guard_bytes = (long long)guard;
+    if (guard_bytes) *guard_bytes = (long long)plan.guard_bytes;
     if (plane_info)
         for (int i = 0; i < (int)planes.size() && i < max_planes; ++i) {
             plane_info[4 * i + 0] = planes[i].h; plane_info[4 * i + 1] = planes[i].w;
@@ -3897,79 +3441,60 @@ int uva_debug_trunk2_schedule(int h, int w, int tile_size, int border, int grid,
     std::memcpy(steps_words, steps.data(), steps.size() * sizeof(Trunk2Step));
     if (nsteps) std::copy(ns.begin(), ns.end(), nsteps);
     return 0;
+}
+
+int uva_debug_trunk2_schedule(int h, int w, int tile_size, int border, int grid, uint32_t* steps_words,
+                              size_t capacity_words, size_t* needed_words, int* nsteps, int* stride,
+                              long long* plane_info, int max_planes, int* nplanes, long long* guard_bytes)
+{
+    return debug_trunk_schedule(false, h, w, tile_size, border, grid, steps_words, capacity_words, needed_words, nsteps, stride,
+                                plane_info, max_planes, nplanes, guard_bytes);
 }
 
 int uva_debug_trunkw_schedule(int h, int w, int tile_size, int border, int grid, uint32_t* steps_words,
                               size_t capacity_words, size_t* needed_words, int* nsteps, int* stride,
                               long long* plane_info, int max_planes, int* nplanes, long long* guard_bytes)
 {
+    return debug_trunk_schedule(true, h, w, tile_size, border, grid, steps_words, capacity_words, needed_words, nsteps, stride,
+                                plane_info, max_planes, nplanes, guard_bytes);
+}
+
+// the row-list hooks (frames > 0: sub10_kernel's list for that many frames; 0: sub5_kernel's): the one builder, the copy-out
+static int debug_strip_rows(int h, int w, int frames, int grid, uint32_t* rows_words, size_t capacity_words, size_t* needed_words,
+                            int* nrows, int* stride)
+{
     if (h <= 0 || w <= 0 || grid < 8 || grid % 8) return fail("bad argument");
-    std::vector<PlaneDesc> planes;
-    if (tile_size <= 0) { tile_size = 0; border = 0; }
-    if (build_planes(h, w, tile_size, border, planes)) return 1;
-    size_t pix = 0;
-    int max_pitch = 0;
-    layout_planes(planes, &pix, nullptr, nullptr);
-    for (auto& p : planes) max_pitch = std::max(max_pitch, p.pitch);
-    const size_t guard = (size_t)8 * max_pitch * 128;
-    std::vector<Trunk2Step> steps;
-    std::vector<int> ns;
-    int max_steps = 0;
-    if (build_trunkw_schedule(planes, grid, guard, steps, ns, &max_steps)) return 1;
-    if (needed_words) *needed_words = steps.size() * 8;
-    if (stride) *stride = max_steps + TW_PAD_STEPS;
-    if (nplanes) *nplanes = (int)planes.size();
-    if (guard_bytes) *guard_bytes = (long long)guard;
-    if (plane_info)
-        for (int i = 0; i < (int)planes.size() && i < max_planes; ++i) {
-            plane_info[4 * i + 0] = planes[i].h; plane_info[4 * i + 1] = planes[i].w;
-            plane_info[4 * i + 2] = planes[i].pitch; plane_info[4 * i + 3] = planes[i].act_off;
-        }
-    if (!steps_words || capacity_words < steps.size() * 8) return fail("steps buffer too small");
-    std::memcpy(steps_words, steps.data(), steps.size() * sizeof(Trunk2Step));
-    if (nsteps) std::copy(ns.begin(), ns.end(), nsteps);
+    std::vector<uint4> rows;
+    std::vector<int> nr;
+    int max_rows = 0;
+    std::string err;
+    const int rc = frames ? build_sub10_rows(h, w, frames, grid, rows, nr, &max_rows, err) : build_sub5_rows(h, w, grid, rows, nr, &max_rows, err);
+    if (rc == 2) return fail(frames ? "frame too large for the fused 1x kernel's row table" : "frame too large for sub5_kernel's row table");
+    if (rc) return fail(err);
+    if (needed_words) *needed_words = rows.size() * 4;
+    if (stride) *stride = max_rows;
+    if (!rows_words || capacity_words < rows.size() * 4) return fail("rows buffer too small");
+    std::memcpy(rows_words, rows.data(), rows.size() * sizeof(uint4));
+    if (nrows) std::copy(nr.begin(), nr.end(), nrows);
     return 0;
 }
 
 int uva_debug_sub10_rows(int h, int w, int grid, uint32_t* rows_words, size_t capacity_words, size_t* needed_words,
                          int* nrows, int* stride)
 {
-    return uva_debug_sub10_rows_batch(h, w, 1, grid, rows_words, capacity_words, needed_words, nrows, stride);
+    return debug_strip_rows(h, w, 1, grid, rows_words, capacity_words, needed_words, nrows, stride);
 }
 
 int uva_debug_sub10_rows_batch(int h, int w, int frames, int grid, uint32_t* rows_words, size_t capacity_words, size_t* needed_words,
                                int* nrows, int* stride)
 {
-    if (h <= 0 || w <= 0 || grid < 8 || grid % 8 || frames < 1 || frames > S10_MAXB) return fail("bad argument");
-    std::vector<uint4> rows;
-    std::vector<int> nr;
-    int max_rows = 0;
-    const int rc = build_sub10_rows(h, w, frames, grid, rows, nr, &max_rows);
-    if (rc == 2) return fail("frame too large for the fused 1x kernel's row table");
-    if (rc) return 1;
-    if (needed_words) *needed_words = rows.size() * 4;
-    if (stride) *stride = max_rows;
-    if (!rows_words || capacity_words < rows.size() * 4) return fail("rows buffer too small");
-    std::memcpy(rows_words, rows.data(), rows.size() * sizeof(uint4));
-    if (nrows) std::copy(nr.begin(), nr.end(), nrows);
-    return 0;
+    if (frames < 1 || frames > S10_MAXB) return fail("bad argument");
+    return debug_strip_rows(h, w, frames, grid, rows_words, capacity_words, needed_words, nrows, stride);
 }
 
 int uva_debug_sub5_rows(int h, int w, int grid, uint32_t* rows_words, size_t capacity_words, size_t* needed_words, int* nrows, int* stride)
 {
-    if (h <= 0 || w <= 0 || grid <= 0 || grid % 8) return fail("bad argument");
-    std::vector<uint4> rows;
-    std::vector<int> nr;
-    int max_rows = 0;
-    const int rc = build_sub5_rows(h, w, grid, rows, nr, &max_rows);
-    if (rc == 2) return fail("frame too large for sub5_kernel's row table");
-    if (rc) return 1;
-    if (needed_words) *needed_words = rows.size() * 4;
-    if (stride) *stride = max_rows;
-    if (!rows_words || capacity_words < rows.size() * 4) return fail("rows buffer too small");
-    std::memcpy(rows_words, rows.data(), rows.size() * sizeof(uint4));
-    if (nrows) std::copy(nr.begin(), nr.end(), nrows);
-    return 0;
+    return debug_strip_rows(h, w, 0, grid, rows_words, capacity_words, needed_words, nrows, stride);
 }
 
 int uva_debug_generic_segments_planes(int kind, const int* dims, int nplanes, int grid, int32_t* out, size_t capacity_words,
@@ -4005,8 +3530,9 @@ int uva_debug_generic_batches(int h, int w, int tile_size, int border, long long
 {
     if (h <= 0 || w <= 0) return fail("bad argument");
     std::vector<PlaneDesc> planes;
-    if (tile_size <= 0) { tile_size = 0; border = 0; }
-    if (build_planes(h, w, tile_size, border, planes)) return 1;
+    normalize_tiling(tile_size, border);
+    std::string err;
+    if (build_planes(h, w, tile_size, border, planes, err)) return fail(err);
     std::vector<int> batch_of;
     generic_plan_batches(planes, true, batch_pixels > 0 ? batch_pixels : generic_batch_pixels(), batch_of);
     if (needed_words) *needed_words = planes.size() * 4;

@@ -12,6 +12,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "uva_plan.h"       // Trunk2Step
+
 namespace uva {
 
 // Host side.  The library's A/B and debug switches (kernel choice, schedule variants, several of
@@ -170,16 +172,5 @@ __device__ __forceinline__ void dma_barrier()
 {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(KEEP) : "memory");
 }
-
-struct Trunk2Step {                             // 32 bytes
-    // A half: x = input halo origin byte offset (low 32), y = offset bits 32..39 | row mask << 8 (bit r:
-    // intermediate row r of the block is inside the plane) | c_lo << 12 | c_hi << 18 (intermediate columns
-    // [c_lo, c_hi) of the block are inside the plane) | active << 24, z = row pitch in bytes
-    uint4 a;
-    // B half: x = output origin byte offset (low 32), y = offset bits 32..39 | valid rows << 8 |
-    // valid columns << 11 | active << 24, z = row pitch in bytes
-    uint4 b;
-};
-static_assert(sizeof(Trunk2Step) == 32, "Trunk2Step layout");
 
 }  // namespace uva

@@ -50,32 +50,13 @@
 #endif
 
 #include "uva_devutil.hip.h"
+#include "uva_plan.h"       // TH, TW, MAX_PLANES, PlaneDesc; T2_SW, T2_SLOTS, T2_PAD_STEPS
 
 namespace uva {
 
-constexpr int TH = 8;           // work-tile rows
-constexpr int TW = 32;          // work-tile columns (= one MFMA N fragment)
 constexpr int PH = TH + 2;      // halo tile rows
 constexpr int PW = TW + 2;      // halo tile columns
 constexpr int NPIX = PH * PW;   // 340 pixels per halo tile
-constexpr int MAX_PLANES = 64;
-
-// One independent sub-image.  The reference cuts a frame into <=980x980 tiles
-// (upscale_processing.py:395-434) and feeds each through the net on its own; each such tile is a
-// "plane" here, and all planes of a frame go through every layer in one launch.
-struct PlaneDesc {
-    int h, w;               // plane size in input pixels
-    int nty, ntx;           // work tiles
-    int tile_begin;         // first global work-tile index of this plane
-    int pitch;              // activation row pitch in pixels (ntx*TW + 2)
-    long long act_off;      // pixel offset of the plane's padded array inside the activation buffer
-    int src_y0, src_x0;     // plane origin inside the source frame
-    int core_y0, core_y1;   // plane-local rows whose output is written (border cropped, :464-477)
-    int core_x0, core_x1;   // plane-local columns whose output is written
-    int nty4;               // work tiles of the trunk kernel (4-row tiles)
-    int tile_begin4;        // first global 4-row work-tile index of this plane
-};
-static_assert(sizeof(PlaneDesc) == 64, "PlaneDesc layout");
 
 template <int NF, int THT = TH>
 struct Geo {
@@ -1329,11 +1310,7 @@ __global__ __launch_bounds__(512, 2) void trunk_kernel(ConvArgs a)
 //   B: output rows yA+1 .. yA+4 (= the rows whose 3x3 windows are complete once block g+1 exists),
 //      columns x0 .. x0+29, from ring blocks g % 3 and (g+1) % 3; executed in iteration g+2.
 // ----------------------------------------------------------------------------------------------
-constexpr int T2_SW = 30;                       // output columns per strip
-constexpr int T2_SLOTS = 4;                     // input halo-tile ring (A only: one tile per period; tile it+1 is complete
-                                                // one barrier before its k-loop, so its first fragments are read early)
-constexpr int T2_RING_ROWS = 12;                // intermediate ring: 3 blocks of 4 rows
-constexpr int T2_PAD_STEPS = T2_SLOTS;          // dummy entries behind a workgroup's last step (DMA look-ahead)
+constexpr int T2_RING_ROWS = 12;                // intermediate ring: 3 blocks of 4 rows (T2_SW, T2_SLOTS, T2_PAD_STEPS: uva_plan.h)
 
 
 struct Trunk2Args {

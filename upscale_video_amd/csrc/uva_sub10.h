@@ -14,16 +14,9 @@
 
 namespace uva {
 
-constexpr int S10_WC = 80;                       // computed columns per strip (five 16-pixel fragments)
-constexpr int S10_NL = 10;                       // layers = pipeline stages
+// (the row lists' constants S10_WC, S10_NL, S10_VALID, S10_MAX_ROWS, S10_MAXB, S10_YBIAS, S10_FSHIFT, S10_MAX_H: uva_plan.h, through uva_devutil.hip.h)
 constexpr int S10_NW = 12;                       // waves: 8 trunk layers, the first and the last layer on two waves each
-constexpr int S10_VALID = S10_WC - 2 * S10_NL;   // columns of the strip the last layer gets right
-constexpr int S10_MAX_ROWS = 640;                // row descriptors of a workgroup, copied to LDS (8 B each)
 constexpr int S10_DRAIN = 2 * S10_NL;            // steps after the last row went in until it has come out
-constexpr int S10_MAXB = 8;                      // frames per launch (uva_net_process_u8_device_batch)
-constexpr int S10_YBIAS = 16;                    // a descriptor's row travels as y + S10_YBIAS (rows -10.. are warm-up rows) ...
-constexpr int S10_FSHIFT = 16;                   // ... below the frame's index: ((frame << S10_FSHIFT) | (y + S10_YBIAS))
-constexpr int S10_MAX_H = (1 << S10_FSHIFT) - 2 * S10_YBIAS;
 
 struct Sub10Args {
     const uint8_t* src[S10_MAXB]; // u8 HWC BGR frames (one plane = a whole frame: apply_model, :263-288), one geometry

@@ -9,13 +9,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "uva_plan.h"       // the row lists' constants: S5_WC, S5_NL, S5_VALID, S5_PAIRW, S5_MAX_ROWS
+
 namespace uva {
 
-constexpr int S5_WC = 64;                        // computed columns per strip: four 16-pixel MFMA fragments
-constexpr int S5_NL = 5;                         // layers per launch = stages of a pipeline
-constexpr int S5_VALID = S5_WC - 2 * S5_NL;      // 54: the columns of a strip the fifth layer gets right
-constexpr int S5_PAIRW = 2 * S5_VALID;           // 108: a workgroup's two pipelines cover neighbouring strips
-constexpr int S5_MAX_ROWS = 1024;                // row descriptors of a workgroup, copied to LDS (8 B each)
 constexpr int S5_MIDB = 48;                      // bytes per pixel of the 24-channel image between the two launches (fp16, ring order)
 
 struct Sub5Args {

@@ -4,13 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "uva_plan.h"       // Trunk2Step (trunkw's meaning of the fields: uva_wino.hip.h); TW_SW, TW_PAD_STEPS, TW_FOLD_MAXW
+
 namespace uva {
-
-struct Trunk2Step;                                // uva_devutil.hip.h (32 bytes; trunkw's meaning of the fields: uva_wino.hip.h)
-
-constexpr int TW_SW = 30;                         // output columns per strip
-constexpr int TW_PAD_STEPS = 2;                   // dummy entries behind a workgroup's last step (DMA look-ahead)
-constexpr int TW_FOLD_MAXW = 12;                  // widest last strip two planes can share (folded steps: pairs 0..6 per plane)
 
 struct TrunkwArgs {
     const char* in_act;           // activation buffer INCLUDING its leading guard
