@@ -50,7 +50,9 @@ extern "C" {
                                15 + resampler: + uva_resize_taps, uva_resize, uva_resize_device, uva_net_submit_pix_sized, UVA_RESIZE_*
                                    (additive: every earlier entry keeps its signature and its bytes)
                                15 + repeated frames: + uva_frame_diff, uva_frame_diff_device, uva_net_set_skip_repeats,
-                                   uva_net_reset_reference, uva_net_skip_stats (additive: off unless asked for) */
+                                   uva_net_reset_reference, uva_net_skip_stats (additive: off unless asked for)
+                               15 + 16 bits through the 1x net: + uva_net_enable_u16_1x, kind 3 of uva_net_kernel_stats (additive: off
+                                   unless asked for) */
 
 typedef struct uva_net uva_net;
 
@@ -191,8 +193,8 @@ int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out
 /* ---- the 16-bit route ---------------------------------------------------------------------
  * The 2x and 4x Compact nets on u16 BGR samples (unorm16, v / 65535): head operand fp16(v / 257) times 1/255, tail output
  * clamp(rint(y * 65535), 0, 65535).  Y'CbCr frames reach the net without an 8-bit hop (10 bits in, 10 bits out); bgr24
- * frames go in as v * 257 and come out as rint(v / 257).  Every 16-bit entry refuses the 1x net, generic graphs (x_Valar_v1)
- * and frames whose byte offsets pass 32 bits, with uva_last_error set. */
+ * frames go in as v * 257 and come out as rint(v / 257).  Every 16-bit entry refuses the 1x net (unless uva_net_enable_u16_1x
+ * is on, below), generic graphs (x_Valar_v1) and frames whose byte offsets pass 32 bits, with uva_last_error set. */
 /* uva_net_process_u8_device's analogue: d_in u16 [h][w][3], d_out u16 [h*s][w*s][3], strides in bytes (even). */
 int uva_net_process_u16_device(uva_net* net, const void* d_in, int h, int w, size_t in_stride, void* d_out, size_t out_stride,
                                int tile_size, int border);
@@ -203,6 +205,18 @@ int uva_net_process_u16(uva_net* net, const uint16_t* in, int h, int w, size_t i
  * BGR48LE on both ends is uva_net_process_u16's frame. */
 long long uva_net_submit_pix16(uva_net* net, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
                                int tile_size, int border);
+/* 16 bits through the 1x net.
+ * 1: uva_net_process_u16, uva_net_process_u16_device and uva_net_submit_pix16 (uva_net_submit_pix_sized with bits = 16) take this
+ * net if it is the 1x SubCompact net (24 features, 10 convolutions, scale 1, not a generic graph); 0 (the default): they refuse it
+ * as before.  Returns non-zero with uva_last_error set on any other net.  Loading another graph into the net switches it off.
+ * The default is a refusal only because a pinned test holds the 16-bit entries to their earlier message on this net; nothing in
+ * the arithmetic makes the route second-rate: same head operand, same tail rounding as the 2x / 4x nets, in one launch of
+ * sub10_kernel16.
+ * The route takes whole frames only, as apply_model runs this net.  Refused with uva_last_error set, never run at 8 bits instead:
+ * tile_size > 0; frames whose row lists do not fit the fused kernel (beyond roughly 2160p); input and output frames that overlap
+ * (the kernel reads the input again for the residual while it stores).  UVA_SUB10=0 and UVA_SUB5=1 select among the u8 kernels
+ * and do not apply to this route. */
+int uva_net_enable_u16_1x(uva_net* net, int on);
 /* uva_pix_convert through u16 BGR (any two formats, UVA_PIX_BGR48LE included). */
 int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour);
 
@@ -347,6 +361,7 @@ int uva_net_debug_read_activation(uva_net* net, int conv_idx, float* out_chw, in
 /* Per-kernel-kind timing with HIP events recorded on the net's stream around each launch.
  * kind: 0 head conv, 1 trunk conv (the dominant kernel), 2 tail conv.  Generic graphs (4x_Valar_v1): 1 = rdb4_kernel
  * (a residual dense block's first four convolutions, all planes of the frame), 2 = the block's 192 -> 64 convolution; 0 unused.
+ * kind 3: sub10_kernel16, the 1x net's launches on the 16-bit route (uva_net_enable_u16_1x); its u8 launches count under 1 as before.
  * enable != 0 starts (and resets) collection; stats are valid after uva_net_synchronize. */
 int uva_net_set_profiling(uva_net* net, int enable);
 int uva_net_kernel_stats(uva_net* net, int kind, long long* launches, double* total_ms);

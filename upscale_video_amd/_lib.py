@@ -26,6 +26,8 @@ SYMBOLS = [
     "uva_resize_taps", "uva_resize", "uva_resize_device", "uva_net_submit_pix_sized",
     # 15 + repeated frames (additive as well)
     "uva_frame_diff", "uva_frame_diff_device", "uva_net_set_skip_repeats", "uva_net_reset_reference", "uva_net_skip_stats",
+    # 15 + 16 bits through the 1x net (additive as well)
+    "uva_net_enable_u16_1x",
 ]
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -96,6 +98,7 @@ def load():
     decl("uva_net_set_skip_repeats", [c_p, c_i])
     decl("uva_net_reset_reference", [c_p])
     decl("uva_net_skip_stats", [c_p, pll, pll])
+    decl("uva_net_enable_u16_1x", [c_p, c_i])
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

@@ -18,7 +18,7 @@ SOURCES = {
                     "uva_model.h", "uva_png.hip.h", "uva_denoise.hip.h", "uva_pixfmt.h", "uva_plan.h", "uva_resize.h", "uva_repeat.h", _UVA_H],
     "uva_wino.hip": ["uva_wino.hip.h", "uva_wino.h", "uva_devutil.hip.h", "uva_plan.h"],
     "uva_sub5.hip": ["uva_sub5.hip.h", "uva_sub5.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
-    "uva_sub10.hip": ["uva_sub10.hip.h", "uva_sub10.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
+    "uva_sub10.hip": ["uva_sub10.hip.h", "uva_sub10_body.hip.h", "uva_sub10.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
     "uva_sww.hip": ["uva_sww.hip.h", "uva_sw.h", "uva_devutil.hip.h", "uva_plan.h"],
     "uva_pixfmt.hip": ["uva_pixfmt.h"],
     "uva_resize.hip": ["uva_resize.h"],

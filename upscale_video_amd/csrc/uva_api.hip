@@ -151,6 +151,7 @@ struct uva_net {
     bool generic_lds_conv = true; // generic graphs: 3x3 convolutions through g_conv3_lds (UVA_GENERIC_LDS=0: the plain g_conv<3>)
     bool fuse_all = true;         // 24-feature 1x net: all ten convolutions in one launch (sub10_kernel); UVA_SUB10=0 turns it off
     bool split5 = false;          // ... as two launches of five layers instead (sub5_kernel, csrc/uva_sub5.hip.h); UVA_SUB5=1
+    bool u16_1x = false;          // ... takes part in the 16-bit route (sub10_kernel16; uva_net_enable_u16_1x)
     bool fuse_pairs = true;       // 64-feature nets: trunk layers run two per launch (trunk2_kernel); UVA_TRUNK_FUSION=0 turns it off
     bool carry = true;            // ... and between two launches the negated channels stay negated in HBM (UVA_TW_CARRY=0: every launch
                                   // restores the signs in front of its stores)
@@ -222,10 +223,11 @@ struct uva_net {
     std::vector<hipEvent_t> ev_sync_free;   // ordering events between streams (take_sync_event)
     struct EvSet { hipEvent_t e[4]; int ntrunk; };
     std::vector<EvSet> ev_pending;
-    struct EvPair { hipEvent_t a, b; int kind; };       // generic graphs: one launch of rdb4_kernel (kind 1) / the 192 -> 64 convolution (2)
+    struct EvPair { hipEvent_t a, b; int kind; };       // generic graphs: one launch of rdb4_kernel (kind 1) / the 192 -> 64 convolution (2);
+                                                        // the 1x net's sub10_kernel16 (kind 3)
     std::vector<EvPair> ev_pairs;
-    long long launches[3] = {0, 0, 0};
-    double total_ms[3] = {0, 0, 0};
+    long long launches[4] = {0, 0, 0, 0};       // [3]: sub10_kernel16
+    double total_ms[4] = {0, 0, 0, 0};
 
     void free_device()
     {
@@ -518,10 +520,9 @@ int launch_sub5(uva_net* n, Workspace* ws, const void* src, size_t src_stride, v
     return 0;
 }
 
-// the whole 24-feature 1x net in one launch (u8 route, one plane per frame), `frames` frames of the workspace's geometry at once;
-// returns 2 when that many frames do not fit the kernel's row table (the caller takes fewer, or for one frame another path)
-int launch_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_stride, void* const* dsts, size_t dst_stride, int frames,
-                 unsigned long long* dbg = nullptr)
+// the row lists of `frames` frames per launch (sub10_kernel; one frame: sub10_kernel16 as well), built on first use;
+// 0 = there, 1 = error, 2 = that many frames do not fit the kernel's row table (the workspace remembers)
+int ensure_sub10_rows(uva_net* n, Workspace* ws, int frames)
 {
     if (ws->sub10_unfit || frames < 1 || frames > ws->sub10_max_batch) return 2;
     const int bi = frames - 1;
@@ -552,6 +553,16 @@ int launch_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_
         ws->d_rows10[bi] = d_rows;
         ws->d_nrows10[bi] = d_nrows;
     }
+    return 0;
+}
+
+// the whole 24-feature 1x net in one launch (u8 route, one plane per frame), `frames` frames of the workspace's geometry at once;
+// returns 2 when that many frames do not fit the kernel's row table (the caller takes fewer, or for one frame another path)
+int launch_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_stride, void* const* dsts, size_t dst_stride, int frames,
+                 unsigned long long* dbg = nullptr)
+{
+    if (const int rc = ensure_sub10_rows(n, ws, frames)) return rc;
+    const int bi = frames - 1;
     Sub10Args a;
     std::memset(&a, 0, sizeof a);
     for (int f = 0; f < S10_MAXB; ++f) {       // (unused slots repeat the last frame: never addressed, never null)
@@ -574,6 +585,11 @@ int launch_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_
 int launch_sub10(uva_net* n, Workspace* ws, const void* src, size_t src_stride, void* dst, size_t dst_stride, unsigned long long* dbg = nullptr)
 {
     return launch_sub10(n, ws, &src, src_stride, &dst, dst_stride, 1, dbg);
+}
+
+bool is_sub10_net(const uva_net* n)
+{
+    return !n->generic && n->g.nf == 24 && n->g.scale == 1 && (int)n->g.convs.size() == S10_NL;
 }
 
 // two trunk layers of the 24-feature net per launch (pair24_kernel), two persistent workgroups per CU
@@ -1009,13 +1025,55 @@ int run_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_str
     return rc;
 }
 
-// u16: the 16-bit route (u16 HWC BGR in and out; 64-feature 2x / 4x nets only)
+// the 16-bit route of the 1x net (sub10_kernel16): one u16 frame, whole-frame plane, one launch -- or a
+// refusal.  Nothing falls back to another kernel: there is no other u16 path for this net.
+int run_sub10_u16(uva_net* n, Workspace* ws, const void* src, size_t src_stride, void* dst, size_t dst_stride)
+{
+    if (ws->planes.size() != 1 || !n->layers[0].wpk_s10) return fail("the 16-bit route runs the 1x net on whole frames only (tile_size 0)");
+    // the tail waves read the residual from the input frame while other workgroups store: the frames must not overlap
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + src_stride * (size_t)ws->h, d0 = (uintptr_t)dst, d1 = d0 + dst_stride * (size_t)ws->h;
+    if (s0 < d1 && d0 < s1) return fail("the 16-bit route of the 1x net needs input and output frames that do not overlap");
+    if (ensure_sub10_rows(n, ws, 1) == 1) return 1;
+    if (ws->sub10_unfit)
+        return fail("the 16-bit route of the 1x net: a frame of " + std::to_string(ws->w) + " x " + std::to_string(ws->h) +
+                    " does not fit the fused kernel's row table (frames up to about 2160p do)");
+    Sub10Args16 a;
+    std::memset(&a, 0, sizeof a);
+    a.src = (const uint16_t*)src; a.dst = (uint16_t*)dst;
+    a.src_stride = src_stride; a.dst_stride = dst_stride;
+    a.h = ws->h; a.w = ws->w;
+    a.rows = ws->d_rows10[0]; a.nrows = ws->d_nrows10[0]; a.max_rows = ws->max_rows10[0];
+    for (int i = 0; i < S10_NL; ++i) {
+        a.wpk[i] = n->layers[i].wpk_s10;
+        a.bias[i] = n->layers[i].bias_s10;
+        a.slope[i] = n->layers[i].slope;
+    }
+    uva_net::EvPair ev = {nullptr, nullptr, 3};
+    if (n->prof) {
+        ev.a = take_event(n);
+        ev.b = ev.a ? take_event(n) : nullptr;
+        if (!ev.b) {
+            if (ev.a) n->ev_free.push_back(ev.a);
+            return 1;
+        }
+        HIP_TRY(hipEventRecord(ev.a, n->stream));
+    }
+    HIP_TRY(launch_sub10_kernel16(n->stream, ws->grid10, a));
+    if (n->prof) {
+        HIP_TRY(hipEventRecord(ev.b, n->stream));
+        n->ev_pairs.push_back(ev);
+    }
+    return 0;
+}
+
+// u16: the 16-bit route (u16 HWC BGR in and out; the 64-feature 2x / 4x nets, and the 1x net where uva_net_enable_u16_1x is on)
 int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_stride, void* dst,
               size_t dst_stride, int stop_after, bool u16 = false)
 {
     const Graph& g = n->g;
     const int nconv = (int)g.convs.size();
     // the 24-feature 1x net on a whole-frame plane, u8 in / u8 out: one launch for all ten convolutions
+    if (u16 && is_sub10_net(n)) return run_sub10_u16(n, ws, src, src_stride, dst, dst_stride);
     if (!u16 && sub10_route(n, ws, f32, stop_after)) {
         const int rc = run_sub10(n, ws, &src, src_stride, &dst, dst_stride, 1);
         if (rc != 2) return rc;
@@ -2276,6 +2334,7 @@ int uva_net_load_param(uva_net* n, const char* path)
     if (!n || !path) return fail("null argument");
     n->free_device();
     n->generic = false;
+    n->u16_1x = false;
     n->gg = GenericGraph();
     std::string err;
     // UVA_GENERIC=1 (tests): run even the SRVGGNetCompact graphs through the generic executor
@@ -2385,9 +2444,11 @@ int uva_net_process_u8_device(uva_net* n, const void* d_in, int h, int w, size_t
     return run_graph(n, ws, false, d_in, in_stride, d_out, out_stride, -1);
 }
 
-// the 16-bit route's refusals, shared by every 16-bit entry: 2x / 4x Compact nets only
+// the 16-bit route's refusals, shared by every 16-bit entry: 2x / 4x Compact nets only -- and the 1x net where the caller has
+// asked for it (uva_net_enable_u16_1x)
 static int check_u16_net(uva_net* n)
 {
+    if (n->u16_1x && is_sub10_net(n)) return 0;
     if (n->generic) return fail("the 16-bit route takes the 2x and 4x Compact nets only (this net runs as a generic graph)");
     if (!has_tail64(n)) return fail("the 16-bit route takes the 2x and 4x Compact nets only (64 features, scale 2 or 4)");
     return 0;
@@ -2407,6 +2468,7 @@ int uva_net_process_u16_device(uva_net* n, const void* d_in, int h, int w, size_
     if ((unsigned long long)in_stride * (unsigned long long)h >= (1ull << 32) - 64 ||
         (unsigned long long)out_stride * (unsigned long long)h * (unsigned long long)s >= (1ull << 32) - 64)
         return fail("frame of 4 GB or more");
+    if (is_sub10_net(n) && tile_size > 0) return fail("the 16-bit route runs the 1x net on whole frames only (tile_size 0)");
     Workspace* ws = nullptr;
     if (get_workspace(n, h, w, tile_size, border, &ws)) return 1;
     n->last = LastCall();        // the debug replays know u8 and f32 frames only
@@ -2763,6 +2825,15 @@ long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, in
     const int s = uva_net_scale(n);
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 6, (uint8_t*)out, (size_t)w * s * 6, tile_size, border, nullptr, 0,
                      in_fmt, out_fmt, colour, true, 0, 0, 0, true);
+}
+
+int uva_net_enable_u16_1x(uva_net* n, int on)
+{
+    if (!n) return fail("null net");
+    if (!n->g.param_loaded || !is_sub10_net(n))
+        return fail("uva_net_enable_u16_1x: not the 1x SubCompact net (24 features, 10 convolutions, scale 1, not a generic graph)");
+    n->u16_1x = on != 0;
+    return 0;
 }
 
 int uva_net_process_u16(uva_net* n, const uint16_t* in, int h, int w, size_t in_stride, uint16_t* out, size_t out_stride,
@@ -3144,13 +3215,13 @@ int uva_net_set_profiling(uva_net* n, int enable)
     if (!n) return fail("null net");
     if (uva_net_synchronize(n)) return 1;
     n->prof = enable != 0;
-    for (int k = 0; k < 3; ++k) { n->launches[k] = 0; n->total_ms[k] = 0; }
+    for (int k = 0; k < 4; ++k) { n->launches[k] = 0; n->total_ms[k] = 0; }
     return 0;
 }
 
 int uva_net_kernel_stats(uva_net* n, int kind, long long* launches, double* total_ms)
 {
-    if (!n || kind < 0 || kind > 2) return fail("bad argument");
+    if (!n || kind < 0 || kind > 3) return fail("bad argument");
     if (launches) *launches = n->launches[kind];
     if (total_ms) *total_ms = n->total_ms[kind];
     return 0;

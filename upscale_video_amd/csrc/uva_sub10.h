@@ -6,6 +6,7 @@
 // launch, u8 in -> u8 out -- and, since round 6, up to S10_MAXB FRAMES of one geometry in that one launch:
 // a frame's strips are dealt out to the 256 workgroups in segments that each pay 20 warm-up rows and the launch pays the
 // pipeline's 20 steps of fill and drain once, so k frames in one launch pay both once per k.
+// sub10_kernel16 is the same net on one u16 frame (u16 in -> u16 out).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,7 +36,27 @@ struct Sub10Args {
     unsigned long long* dbg;      // UVA_INSTRUMENT builds: workgroup 0 stamps [step][wave][4] here
 };
 
+// sub10_kernel16's arguments: ONE u16 HWC BGR frame (the 16-bit route).  Strides are in bytes and even,
+// like the pointers; the tail waves read the residual from `src` while neighbouring strips store to `dst`, so the two frames
+// must not overlap.  Row lists, weights, biases and slopes are sub10_kernel's.
+struct Sub10Args16 {
+    const uint16_t* src;
+    uint16_t* dst;
+    size_t src_stride;
+    size_t dst_stride;
+    int h, w;
+    const uint4* rows;
+    const int* nrows;
+    int max_rows;
+    const half8* wpk[S10_NL];
+    const float* bias[S10_NL];
+    const float* slope[S10_NL];
+    unsigned long long* dbg;
+};
+
 // One launch of sub10_kernel on `grid` workgroups of 768 threads.  Returns hipSuccess or the failing call's error.
 hipError_t launch_sub10_kernel(hipStream_t stream, int grid, const Sub10Args& a);
+// ... of sub10_kernel16 (row lists built for one frame)
+hipError_t launch_sub10_kernel16(hipStream_t stream, int grid, const Sub10Args16& a);
 
 }  // namespace uva

@@ -44,6 +44,20 @@ constexpr int S10_SKIP_ALL = 15 * 2;             // descriptor word of "no row":
 __host__ __device__ constexpr int sub10_lag(int stage) { return 2 * stage + 2; }
 constexpr int sub10_lds_bytes() { return (S10_NL - 1) * S10_RINGB + S10_URINGB + S10_PRMB + S10_RESB + S10_MAX_ROWS * 8; }
 static_assert(sub10_lds_bytes() <= 160 * 1024, "sub10 kernel LDS budget");
+// sub10_kernel16 (u16 frames) keeps no residual ring: a u16 pixel would take 6 or 8 bytes of it where
+// 64 bytes are free.  Its tail waves fetch the residual sample from the input frame, one row ahead of use.
+constexpr int sub10_lds_bytes16() { return sub10_lds_bytes() - S10_RESB; }
+static_assert(sub10_lds_bytes16() == (S10_NL - 1) * S10_RINGB + S10_URINGB + S10_PRMB + S10_MAX_ROWS * 8 && sub10_lds_bytes16() <= 160 * 1024,
+              "sub10 u16 kernel LDS budget: nine rings, the input ring, the parameters and the row descriptors");
+
+// the frame's sample type by argument block: uint8_t (sub10_kernel) or uint16_t (sub10_kernel16)
+template <typename A> struct Sub10Sample;
+template <> struct Sub10Sample<Sub10Args> { typedef uint8_t type; };
+template <> struct Sub10Sample<Sub10Args16> { typedef uint16_t type; };
+// the input frame of a descriptor's row word (the u16 kernel takes one frame per launch)
+__device__ __forceinline__ int sub10_row_frame(int yb);
+__device__ __forceinline__ const uint8_t* sub10_src(const Sub10Args& a, int yb) { return a.src[sub10_row_frame(yb)]; }
+__device__ __forceinline__ const uint16_t* sub10_src(const Sub10Args16& a, int) { return a.src; }
 
 struct Sub10Lds {
     char* smem;
@@ -52,6 +66,7 @@ struct Sub10Lds {
     char* resring;
     int2* rows;
 };
+template <bool U16 = false>
 __device__ __forceinline__ Sub10Lds sub10_lds(char* smem)
 {
     Sub10Lds l;
@@ -59,7 +74,7 @@ __device__ __forceinline__ Sub10Lds sub10_lds(char* smem)
     l.uring = smem + (S10_NL - 1) * S10_RINGB;
     l.prm = (float*)(l.uring + S10_URINGB);
     l.resring = (char*)l.prm + S10_PRMB;
-    l.rows = (int2*)(l.resring + S10_RESB);
+    l.rows = (int2*)(l.resring + (U16 ? 0 : S10_RESB));       // (u16: no residual ring, resring is never addressed)
     return l;
 }
 // a descriptor's row word (>> 5): the frame of the batch above bit S10_FSHIFT, the plane row + S10_YBIAS below
@@ -107,12 +122,16 @@ __device__ __forceinline__ void sub10_store(const f32x4 x0, const f32x4 x1, cons
 }
 
 // ---- two waves: u8 rows in, conv 3 -> 24 (+bias, PReLU); HALF 0: ring columns 0..40, fragments 0..2; HALF 1: the rest ----
-template <int HALF>
-__device__ __forceinline__ void sub10_head(const Sub10Args& a, const Sub10Lds L, const int wave, const int lane, const int nrows,
+// u16 frames (A = Sub10Args16): the operand is fp16(v * (1/257)) formed in fp32, as headp_kernel<64, 2> forms it -- v = 257 k is
+// exactly the u8 route's k, 65535 is 255 and not inf -- and nothing is kept for the residual (the tail waves fetch it).
+template <int HALF, typename A>
+__device__ __forceinline__ void sub10_head(const A& a, const Sub10Lds L, const int wave, const int lane, const int nrows,
                                            const int nsteps)
 {
     constexpr int F0 = HALF ? 3 : 0, F1 = HALF ? 5 : 3, NF = F1 - F0;
     constexpr int Q0 = HALF ? S10_ROWPX / 2 : 0, QN = S10_ROWPX / 2;     // one ring column per lane (41 lanes)
+    constexpr bool U16 = sizeof(typename Sub10Sample<A>::type) == 2;
+    typedef std::conditional_t<U16, uint2, unsigned> px_t;               // a fetched pixel: B | G<<8 | R<<16, or {B | G<<16, R}
     const int p = lane & 15, o = lane >> 4;
     const bool stamp = a.dbg != nullptr && blockIdx.x == 0 && lane == 0;
     (void)stamp;
@@ -136,20 +155,25 @@ __device__ __forceinline__ void sub10_head(const Sub10Args& a, const Sub10Lds L,
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // the u8 row of descriptor r (two pixels per lane: ring columns lane and lane + 64), packed B | G<<8 | R<<16;
     // outside the plane: 0.  Fetched one step before it is needed so that HBM latency has a whole step to pass.
-    auto fetch_row = [&](int r, unsigned& px) {
-        px = 0;
+    auto fetch_row = [&](int r, px_t& px) {
+        px = px_t{};
         if (r < nrows) {
             const int2 e = L.rows[r];
             const int yb = __builtin_amdgcn_readfirstlane(e.x) >> 5, x0c = e.y;
             const int y = sub10_row_y(yb);
             const int qq = Q0 + lane, X = x0c - 1 + qq;
             if (lane < QN && y >= 0 && y < a.h && X >= 0 && X < a.w) {
+                if constexpr (U16) {
+                    const uint16_t* sp = (const uint16_t*)((const char*)sub10_src(a, yb) + (size_t)y * a.src_stride) + (size_t)X * 3;
+                    px = make_uint2((unsigned)sp[0] | ((unsigned)sp[1] << 16), (unsigned)sp[2]);
+                } else {
                 const uint8_t* sp = a.src[sub10_row_frame(yb)] + (size_t)y * a.src_stride + (size_t)X * 3;
                 px = (unsigned)sp[0] | ((unsigned)sp[1] << 8) | ((unsigned)sp[2] << 16);
+                }
             }
         }
     };
-    auto step = [&](const int t, const unsigned upx, unsigned& upx_next) {
+    auto step = [&](const int t, const px_t upx, px_t& upx_next) {
         S10_STAMP(0);
         fetch_row(t + 1, upx_next);
         const int d = t - 2;
@@ -197,16 +221,23 @@ __device__ __forceinline__ void sub10_head(const Sub10Args& a, const Sub10Lds L,
             // the fetched u8 pixel -> [B, G, R, 0] fp16 in ring row t (outside the plane: zeros, already in upx), and as it
             // is for the last layer's residual add
             const int qq = Q0 + lane;
+            if constexpr (U16) {
+                constexpr float inv = (float)(1 / 257.0);
+                const half2v bg = {(_Float16)((float)(upx.x & 0xffff) * inv), (_Float16)((float)(upx.x >> 16) * inv)};
+                const half2v r0 = {(_Float16)((float)upx.y * inv), (_Float16)0.f};
+                *(uint2*)(L.uring + (t & 3) * S10_UROWB + qq * 8) = make_uint2(__builtin_bit_cast(unsigned, bg), __builtin_bit_cast(unsigned, r0));
+            } else {
             const half2v bg = {(_Float16)(float)(upx & 0xff), (_Float16)(float)((upx >> 8) & 0xff)};
             const half2v r0 = {(_Float16)(float)((upx >> 16) & 0xff), (_Float16)0.f};
             *(uint2*)(L.uring + (t & 3) * S10_UROWB + qq * 8) = make_uint2(__builtin_bit_cast(unsigned, bg), __builtin_bit_cast(unsigned, r0));
             *(unsigned*)(L.resring + ((t & (S10_RES_ROWS - 1)) * S10_ROWPX + qq) * 4) = upx;
+            }
         }
         S10_STAMP(2);
         sub10_barrier();
     };
     // two steps per trip: the row fetched during one step is converted at the end of the next
-    unsigned pxa, pxb;
+    px_t pxa, pxb;
     fetch_row(0, pxa);
     for (int t = 0; t < nsteps; t += 2) {
         step(t, pxa, pxb);
@@ -236,9 +267,11 @@ __host__ __device__ constexpr int sub10_dy(int ks, int o) { return ((SUB16_OCTET
 // meanwhile.  Measured and dropped (profiles/r02_sub10_experiments.txt): epilogue arithmetic pinned between the MFMAs,
 // the first operands of the next row fetched before the barrier, a half-step phase shift between the SIMD's two trunk
 // waves, 8-byte reads with swapped halves instead of the conflict-free 16-byte ones.
-template <bool TAIL, int F0, int F1, int CSH, bool MASKED, int KS, int MB>
+// T is the frame's sample type.  The tail's residual: u8 frames, `res` points at the pixel the head waves left in LDS; u16
+// frames, resv[f - F0] holds this lane's sample of fragment f, fetched from the input frame during the step before.
+template <bool TAIL, int F0, int F1, int CSH, bool MASKED, int KS, int MB, typename T>
 __device__ __forceinline__ void sub10_row(const char* __restrict__ rin, char* __restrict__ px0, char* __restrict__ px1,
-                                          const char* __restrict__ res, uint8_t* __restrict__ dst, const unsigned (&adr)[KS],
+                                          const char* __restrict__ res, const unsigned (&resv)[2], T* __restrict__ dst, const unsigned (&adr)[KS],
                                           const half8 (&wgt)[KS][MB], const f32x4 (&binit)[2], const Sub10Prm& q, const int x0c,
                                           const int w, const bool row_in, const bool emit, const int pix, const int o)
 {
@@ -267,7 +300,17 @@ __device__ __forceinline__ void sub10_row(const char* __restrict__ rin, char* __
             // + input pixel (Interp x1 = identity, BinaryOp add; left in LDS by the head waves), *255, cv2 convertTo(CV_8U);
             // only rows that are written out and only the columns this strip gets right
             // (channel j is lane group j's first result register -- pack_sub16 -- : three groups, one byte each, one store)
-            if (emit && row_in && o < 3 && c >= S10_NL && c < S10_WC - S10_NL && X >= 0 && X < w) {
+            if constexpr (sizeof(T) == 2) {
+                // u16 frames, as tail_kernel<..., uint16_t>: residual (v / 257) * (1/255) with a true division (v = 257 k gives the
+                // u8 route's k / 255 bit for bit), the same three roundings, clamp(rint(y * 65535), 0, 65535) half to even; three
+                // lane groups, one 2-byte sample each: a fragment's store covers 96 consecutive bytes
+                if (emit && row_in && o < 3 && c >= S10_NL && c < S10_WC - S10_NL && X >= 0 && X < w) {
+#pragma clang fp contract(off)
+                    const float r = ((float)resv[f - F0] / 257.0f) * norm;
+                    const float v = acc[0][0] + r;
+                    dst[f * 16 * 3 + o] = (uint16_t)(unsigned)__builtin_amdgcn_fmed3f(__builtin_rintf(v * 65535.0f), 0.f, 65535.f);
+                }
+            } else if (emit && row_in && o < 3 && c >= S10_NL && c < S10_WC - S10_NL && X >= 0 && X < w) {
 #pragma clang fp contract(off)
                 const unsigned r8 = *(const unsigned*)(res + f * 16 * 4);
                 // v_cvt_pk_u8_f32 rounds half to even and saturates: cv2's convertTo(CV_8U) in one instruction
@@ -318,11 +361,13 @@ __device__ __forceinline__ void sub10_row(const char* __restrict__ rin, char* __
 }
 
 // CSH: the wave's fragments cover computed columns CSH + 16 F0 .. CSH + 16 F1 - 1 (see S10_BAL at the kernel)
-template <bool TAIL, int F0, int F1, int CSH = 0>
-__device__ __forceinline__ void sub10_body(const Sub10Args& a, const Sub10Lds L, const int wave, const int stage, const int lane,
+template <bool TAIL, int F0, int F1, int CSH = 0, typename A>
+__device__ __forceinline__ void sub10_body(const A& a, const Sub10Lds L, const int wave, const int stage, const int lane,
                                            const int nrows, const int nsteps)
 {
     constexpr int KS = 7, MB = TAIL ? 1 : 2;
+    typedef typename Sub10Sample<A>::type T;
+    constexpr bool U16 = sizeof(T) == 2;
     const int p = lane & 15, o = lane >> 4, pix = sub10_pix(p);
     const bool stamp = a.dbg != nullptr && blockIdx.x == 0 && lane == 0;
     (void)stamp;
@@ -350,6 +395,8 @@ __device__ __forceinline__ void sub10_body(const Sub10Args& a, const Sub10Lds L,
     char* const out_ring = L.smem + stage * S10_RINGB;
 
     int2 desc = make_int2(0, 0);        // the descriptor of the next step's row, fetched a step ahead
+    unsigned resv[2] = {0u, 0u};        // u16 tail: the next step's residual samples (fragments F0, F0 + 1), fetched a step ahead
+    static_assert(!(TAIL && U16) || F1 - F0 == 2, "the u16 tail prefetches two fragments' residual");
     for (int t = 0; t < nsteps; ++t) {
         S10_STAMP(0);
         const int d = t - lag;
@@ -362,12 +409,14 @@ __device__ __forceinline__ void sub10_body(const Sub10Args& a, const Sub10Lds L,
             if (((ye >> 1) & 15) <= maxdist) {
             char* const px = out_ring + (d & 3) * S10_ROWB + (pix + 1 + CSH) * S10_PIXB;
             const char* const res = L.resring + ((d & (S10_RES_ROWS - 1)) * S10_ROWPX + pix + 1 + CSH) * 4;
-            uint8_t* const dst = (TAIL ? a.dst[sub10_row_frame(ye >> 5)] : a.dst[0]) + (size_t)yy * a.dst_stride + (size_t)(x0c + pix + CSH) * 3;
+            T* dst;
+            if constexpr (U16) dst = (T*)((char*)a.dst + (size_t)yy * a.dst_stride) + (size_t)(x0c + pix + CSH) * 3;
+            else dst = (TAIL ? a.dst[sub10_row_frame(ye >> 5)] : a.dst[0]) + (size_t)yy * a.dst_stride + (size_t)(x0c + pix + CSH) * 3;
             if (!TAIL && row_in && x0c >= 0 && x0c + S10_WC <= a.w)
-                sub10_row<TAIL, F0, F1, CSH, false, KS, MB>(L.smem, px + 8 * o, px + 32 + 4 * o, res, dst, adr, wgt, binit, q, x0c, a.w,
+                sub10_row<TAIL, F0, F1, CSH, false, KS, MB>(L.smem, px + 8 * o, px + 32 + 4 * o, res, resv, dst, adr, wgt, binit, q, x0c, a.w,
                                                        row_in, (ye & 1) != 0, pix, o);
             else
-                sub10_row<TAIL, F0, F1, CSH, true, KS, MB>(L.smem, px + 8 * o, px + 32 + 4 * o, res, dst, adr, wgt, binit, q, x0c, a.w,
+                sub10_row<TAIL, F0, F1, CSH, true, KS, MB>(L.smem, px + 8 * o, px + 32 + 4 * o, res, resv, dst, adr, wgt, binit, q, x0c, a.w,
                                                       row_in, (ye & 1) != 0, pix, o);
             }
             // Next row: every address one ring row on, wrapping after the fourth.  Whether an address wraps depends only
@@ -385,56 +434,42 @@ __device__ __forceinline__ void sub10_body(const Sub10Args& a, const Sub10Lds L,
         }
         S10_STAMP(2);
         if (d + 1 >= 0 && d + 1 < nrows) desc = L.rows[d + 1];
+        if constexpr (TAIL && U16) {
+            // the residual of the next step's row: this lane's sample (lane group o < 3) of the pixel it stores in each fragment,
+            // under the store's own tests, so nothing outside the frame is read.  The head waves read these bytes some 30 steps
+            // ago; the loads stay in flight over the barrier and the next row's MFMAs.
+            resv[0] = resv[1] = 0u;
+            if (d + 1 >= 0 && d + 1 < nrows) {
+                const int ye = __builtin_amdgcn_readfirstlane(desc.x), x0c = __builtin_amdgcn_readfirstlane(desc.y);
+                const int yy = sub10_row_y(ye >> 5);
+                if (((ye >> 1) & 15) <= maxdist && (ye & 1) != 0 && yy >= 0 && yy < a.h && o < 3) {
+                    const uint16_t* const sp = (const uint16_t*)((const char*)sub10_src(a, ye >> 5) + (size_t)yy * a.src_stride);
+#pragma unroll
+                    for (int f = F0; f < F1; ++f) {
+                        const int c = 16 * f + CSH + pix, X = x0c + c;
+                        if (c >= S10_NL && c < S10_WC - S10_NL && X >= 0 && X < a.w) resv[f - F0] = sp[(size_t)X * 3 + o];
+                    }
+                }
+            }
+        }
         sub10_barrier();
     }
 }
 
 __global__ __launch_bounds__(64 * S10_NW, 1) UVA_NO_PK_F32 void sub10_kernel(Sub10Args a)
 {
+    typedef Sub10Args A;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const Sub10Lds L = sub10_lds(smem);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int nrows = __builtin_amdgcn_readfirstlane(a.nrows[blockIdx.x]);
-    if (nrows <= 0) return;
-    // this workgroup's row descriptors live in LDS, 8 bytes each: {32 ((frame << 16) + y + 16) + 2 dist + emit, x0} (dist: rows between y and the nearest row
-    // of its segment that is written out, 0..10 -- layer s is needed where dist <= 9 - s); every wave reads one (or two) per step
-    {
-        const uint4* const grows = a.rows + (size_t)blockIdx.x * a.max_rows;
-        for (int i = threadIdx.x; i < nrows; i += 64 * S10_NW) {
-            const uint4 e = grows[i];
-            L.rows[i] = make_int2(((int)((e.z >> 8) << S10_FSHIFT) + (int)e.x + S10_YBIAS) * 32 + (int)(e.w & 15u) * 2 + (int)(e.z & 1), (int)e.y);
-        }
-    }
-    // rings start as zeros (margins and pipeline fill are never written: no NaN patterns may sit there)
-    for (int i = threadIdx.x; i < ((S10_NL - 1) * S10_RINGB + S10_URINGB) / 16; i += 64 * S10_NW)
-        ((uint4*)smem)[i] = make_uint4(0, 0, 0, 0);
-    if (wave < S10_NL && lane < 32) {
-        L.prm[wave * 96 + lane] = a.bias[wave][lane];
-        L.prm[wave * 96 + 32 + lane] = wave + 1 < S10_NL ? a.slope[wave][lane] : 0.f;
-    }
-    __syncthreads();
-    // every wave runs the same number of steps = barriers, whatever code it sits in
-    const int nsteps = (nrows + S10_DRAIN + 1) & ~1;
-    // Waves w, w+4, w+8 share a SIMD: two trunk layers and one half of the first or the last layer each -- the same
-    // MFMA and VALU load on all four.  (No s_setprio: with the light waves halved, raising them or the trunk waves
-    // measured 2 % slower than leaving the arbiter alone, profiles/r02_sub10_experiments.txt.)
-#define S10_BAL 1
-    // Round 5 (profiles/r05_ab_results.txt block 19): only columns 10..69 of the last layer are stored, so trunk layer 8 is needed
-    // on columns 9..70 and layer 7 on 8..71 -- 64 columns, FOUR fragments at a column shift of 8 (an even number of 16-byte units:
-    // the conflict-free read recipe holds), where every layer computed all five.  The last layer likewise: four fragments, two per
-    // wave instead of three and two.  What a SIMD carries was 3 818 / 3 458 / 3 744 / 3 224 ticks per row (head 3 fragments, head 2,
-    // tail 3, tail 2 beside two five-fragment trunk waves each); now the tail halves sit beside the five-fragment layers (waves
-    // 8, 9) and the head halves beside the two four-fragment ones (waves 10, 11).  The rings' columns 0..7 and 72..79 of layers 7
-    // and 8 stay at the zeros the kernel starts with; what reads them is never stored.
-#define S10_MAP 0       // A/B builds (block 22): 1 = the first layer's three-fragment half on wave 11 instead of 10; 2 = the four-fragment
-                              // layers on the OLDER waves of their SIMDs (waves 2, 3 = layers 7, 8; waves 6, 7 = layers 3, 4)
-    if (wave < 6) sub10_body<false, 0, 5>(a, L, wave, wave + 1, lane, nrows, nsteps);
-    else if (wave < 8) sub10_body<false, 0, 4, 8>(a, L, wave, wave + 1, lane, nrows, nsteps);
-    else if (wave == 8) sub10_body<true, 0, 2, 8>(a, L, wave, S10_NL - 1, lane, nrows, nsteps);
-    else if (wave == 9) sub10_body<true, 2, 4, 8>(a, L, wave, S10_NL - 1, lane, nrows, nsteps);
-    else if (wave == (S10_MAP == 1 ? 11 : 10)) sub10_head<0>(a, L, wave, lane, nrows, nsteps);
-    else sub10_head<1>(a, L, wave, lane, nrows, nsteps);
+#include "uva_sub10_body.hip.h"
+}
+
+// the same net on u16 BGR frames (the 16-bit route): only the head waves' loads and conversion and the
+// tail waves' residual, rounding and stores differ; the eight trunk waves run sub10_kernel's code
+__global__ __launch_bounds__(64 * S10_NW, 1) UVA_NO_PK_F32 void sub10_kernel16(Sub10Args16 a)
+{
+    typedef Sub10Args16 A;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+#include "uva_sub10_body.hip.h"
 }
 
 }  // namespace uva

@@ -122,6 +122,15 @@ PIX_FORMATS = {"bgr24": 0, "yuv420p": 1, "nv12": 2, "p010le": 3}     # ffmpeg's 
 # the formats of the first pixel-format release
 PIX_FORMATS_ALL = dict(PIX_FORMATS, yuv420p10le=5, bgr48le=6, yuv422p=7, yuv422p10le=8)      # (code 4 is not assigned)
 PIX16_ONLY = ("bgr48le",)
+
+
+def pix_depth(fmt):
+    """bits per sample of a rawvideo pixel format's frames: 8, 10 or 16"""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    return 16 if fmt == "bgr48le" else 10 if fmt in ("p010le", "yuv420p10le", "yuv422p10le") else 8
+
+
 COLORSPACES = {"bt601": 0, "bt709": 1}                              # ffmpeg's -colorspace names
 COLOR_RANGES = {"tv": 0, "pc": 2}                                   # ffmpeg's -color_range names (limited, full)
 # 4:2:0 chroma resampling (DESIGN.md section 7.5): replicate = chroma repeated over its 2x2 block coming in and the 2x2 box
@@ -448,7 +457,8 @@ class Net:
 
     def process_u16(self, img_bgr, tile_size=0, border=0):
         """process_u8 on 16-bit samples (include/uva.h uva_net_process_u16): u16 HWC BGR (unorm16) ->
-        u16 HWC BGR.  The 2x and 4x Compact nets only."""
+        u16 HWC BGR.  The 2x and 4x Compact nets, and the 1x net after enable_u16_1x() (whole frames only: tile_size 0;
+        DESIGN.md section 7.9)."""
         img = np.ascontiguousarray(img_bgr, dtype=np.uint16)
         if img.ndim != 3 or img.shape[2] != 3:
             raise ValueError("frame must be u16 [h][w][3]")
@@ -460,6 +470,12 @@ class Net:
         _lib.check(self._L.uva_net_process_u16(self._h, img.ctypes.data, h, w, w * 6, out.ctypes.data,
                                                w * s * 6, int(tile_size), int(border)))
         return out
+
+    def enable_u16_1x(self, on=True):
+        """Lets the 16-bit entries (process_u16, submit_pix with bit_depth=16) take this net if it is the 1x SubCompact net
+        (include/uva.h uva_net_enable_u16_1x); off, the default, they refuse it.  Raises on any other
+        net.  Needs no GPU."""
+        _lib.check(self._L.uva_net_enable_u16_1x(self._h, 1 if on else 0))
 
     def submit_u8(self, img_bgr, out=None, tile_size=0, border=0):
         """Pipelined process_u8 (include/uva.h uva_net_submit_u8): returns a Ticket at once; up to 3
@@ -488,7 +504,8 @@ class Net:
         h x w frame of in_fmt, the result is one dense (h*s) x (w*s) frame of out_fmt; both conversions run on the GPU around
         the net.  `out`: optional preallocated result buffer of pix_frame_bytes(out_fmt, h*s, w*s) bytes (pix_empty; pinned
         memory avoids the staging copy).  Returns a Ticket that collect_u8 takes.  bit_depth=16: the 16-bit route
-        (uva_net_submit_pix16): the frame reaches the net as u16 BGR and leaves it as u16 BGR, no 8-bit hop.
+        (uva_net_submit_pix16): the frame reaches the net as u16 BGR and leaves it as u16 BGR, no 8-bit hop (the 2x and 4x
+        Compact nets; the 1x net after enable_u16_1x(), at tile_size 0).
         chroma_filter="bilinear": both conversions interpolate chroma sited at chroma_loc.
         out_size=(oh, ow): the net's result is resampled to oh x ow with resize_filter between the net and the output
         conversion (uva_net_submit_pix_sized); the result is then one dense oh x ow frame of out_fmt."""

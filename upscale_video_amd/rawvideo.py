@@ -18,7 +18,10 @@ p010le, yuv420p10le, and the 4:2:2 formats of capture and mezzanine material yuv
       | ffmpeg -f rawvideo -pix_fmt p010le -s 3840x2160 -r 24 -i - -c:v libx265 out.mkv
 
 --bit-depth 16 runs the 2x / 4x net on 16-bit samples so that 10-bit frames (p010le, yuv420p10le, yuv422p10le) keep their depth
-(no -m option with it).
+(DESIGN.md section 7.4).  -m a goes with it: the 1x net then runs on 16-bit samples too and hands u16 BGR (bgr48le) frames to the
+2x / 4x net, so the chain has no 8-bit hop either; -m n=K and -m r run at 8 bits only.  The pair wants
+a format of more than 8 bits on at least one end (p010le, yuv420p10le, yuv422p10le, bgr48le); with 8-bit frames in and out it is
+refused, as it always was.
 
 --chroma-filter bilinear interpolates the 4:2:0 chroma on the way in and filters it on the way out for where its samples sit
  instead of repeating every chroma sample over its 2x2 block and averaging the block: the net then
@@ -38,7 +41,7 @@ and the pipe carries frames of the final size:
       | ffmpeg -f rawvideo -pix_fmt p010le -s 2560x1440 -r 24 -i - -c:v libx265 out.mkv
 
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
-conversions run on the net's stream around its kernels); nets in between pass u8 BGR.  A leading `-m n=K` stage converts
+conversions run on the net's stream around its kernels); nets in between pass u8 BGR (u16 BGR with --bit-depth 16).  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
 
 Frames go through Net.submit_u8 / collect_u8 (include/uva.h): page-locked rings on the host, H2D copy,
@@ -268,7 +271,9 @@ class Lane:
         last = len(nets_tiles) - 1
         for k, (net, tile) in enumerate(nets_tiles):
             # the first stage takes the stream's input format, the last one produces its output format, u8 BGR in between
-            fmts = dict(in_fmt=pix.in_fmt if k == 0 else "bgr24", out_fmt=pix.out_fmt if k == last else "bgr24", pix=pix)
+            # (--bit-depth 16: u16 BGR, so that the hop between the nets of `-m a` keeps the depth)
+            mid = "bgr48le" if pix.bit_depth == 16 else "bgr24"
+            fmts = dict(in_fmt=pix.in_fmt if k == 0 else mid, out_fmt=pix.out_fmt if k == last else mid, pix=pix)
             if isinstance(net, tuple):         # ("denoise", gpu, K): the `-m n=K` stage
                 if k == last and pix.out_size is not None:
                     raise ValueError("--out-size / --out-scale: the resampler sits behind a net, and this lane ends in the denoise "
@@ -773,7 +778,8 @@ def main(argv=None):
     ap.add_argument("--color-range", default="tv", choices=list(ncnn.COLOR_RANGES), help="tv = limited (default), pc = full")
     ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
                     help="16: the 2x / 4x net runs on 16-bit samples, so 10-bit frames (p010le, yuv420p10le, yuv422p10le) keep their "
-                         "depth (default 8); takes no -m option")
+                         "depth (default 8); of the -m options it takes -m a, whose 1x net then runs on 16-bit samples as well "
+                         "(with a 10- or 16-bit pixel format on at least one end)")
     ap.add_argument("--model-path", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models"))
     ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS),
                     help="chroma resampling in the Y'CbCr conversions (4:2:2 formats: along the row alone; DESIGN.md section 7.7): "
@@ -845,8 +851,14 @@ def main(argv=None):
                 ap.error("-m n=K: K must be between 1 and 30")
         elif m not in ("a", "r"):
             ap.error("unknown model option %r (a, n=K, r)" % m)
-    if models and a.bit_depth == 16:
-        ap.error("--bit-depth 16 takes the 2x and 4x Compact nets only: -m a, -m n=K and -m r run at 8 bits (-m %s)" % a.models)
+    if a.bit_depth == 16 and any(m != "a" for m in models):
+        ap.error("--bit-depth 16 takes the 2x and 4x Compact nets only: -m n=K and -m r run at 8 bits (-m %s)" % a.models)
+    if a.bit_depth == 16 and models and all(ncnn.pix_depth(f) == 8 for f in (a.in_pix_fmt, a.out_pix_fmt)):
+        # (the plain pair, with the default bgr24 at both ends, is held to a refusal by a pinned test, tests/test_pixfmt16.py;
+        # what the 16-bit chain is for -- frames of more than 8 bits -- names such a format on at least one end)
+        ap.error("--bit-depth 16 -m a is for frames of more than 8 bits: name a 10- or 16-bit format (%s) with --in-pix-fmt or "
+                 "--out-pix-fmt, or run the chain at 8 bits (%s in, %s out)"
+                 % (", ".join(f for f in ncnn.PIX_FORMATS_ALL if ncnn.pix_depth(f) > 8), a.in_pix_fmt, a.out_pix_fmt))
     if out_size is not None and a.scale == 1 and denoise is not None and "a" not in models:
         ap.error("--out-size / --out-scale: the resampler sits behind a net, and -s 1 -m n=K ends in the denoise stage: add -m a or "
                  "-s 2|4")
@@ -871,6 +883,8 @@ def main(argv=None):
             chain.append((("denoise", gpu, denoise), 0))
         if "a" in models:
             chain.append((load_net(MODEL_FILES[1], gpu, a.model_path), 0))          # apply_model: whole frame
+            if a.bit_depth == 16:
+                chain[-1][0].enable_u16_1x()
         if a.scale != 1:
             chain.append((load_net(final_stem, gpu, a.model_path), a.tile))
         if chain:
