@@ -52,7 +52,8 @@ extern "C" {
                                15 + repeated frames: + uva_frame_diff, uva_frame_diff_device, uva_net_set_skip_repeats,
                                    uva_net_reset_reference, uva_net_skip_stats (additive: off unless asked for)
                                15 + 16 bits through the 1x net: + uva_net_enable_u16_1x, kind 3 of uva_net_kernel_stats (additive: off
-                                   unless asked for) */
+                                   unless asked for)
+                               15 + launch census: + uva_net_debug_generic_launches (additive: a host-side test hook) */
 
 typedef struct uva_net uva_net;
 
@@ -406,6 +407,16 @@ int uva_debug_trunkw_schedule(int h, int w, int tile_size, int border, int grid,
  * their first input only, [4] 3x3 convolutions that take the LDS-tiled kernel, [5] channels of the widest shared array, [6] residual dense blocks
  * whose first four convolutions run as one launch (rdb4_kernel).  info: at least 8 ints. */
 int uva_net_debug_generic_plan(const uva_net* net, int* info);
+
+/* Test hook (host only): how often the generic executor has launched each of its kernel instantiations on this net since
+ * uva_net_create -- counted on the host next to the launch, nothing on the GPU.  *n = the number of counters (also with
+ * counts == NULL); capacity < *n is an error.  Index: 11-14 g_conv3_lds<1..4> (3x3, weights through LDS), 15 / 23
+ * g_conv3_lds<4 / 2, 3, true, 8> (16-row tiles), 16-19 g_conv3_lds<1..4, 1> (1x1), 21 / 22 g_conv3_lds<2 / 4, 3, true> (weights in
+ * registers); g_conv3_sw: 24 <6,1,false,2,0>, 25 <6,1,false,2,2>, 26 <2,2,false,1,0>, 27 <2,2,true,0,0>, 29 <6,1,false,0,0>,
+ * 30 <2,2,false,0,0>, 31 <2,2,true,0,0,true> (the 2x Interp folded in); 28 rdb4_kernel; g_conv3_sk: 32 <2,0>, 33 <2,2>, 34 <0,0>;
+ * 40 g_conv<1>, 41 g_conv<3>, g_conv3_sww: 42 no sum, 43 one sum, 44 two sums; 45 g_axpby, 46 g_axpby_strided, 47 g_concat_part,
+ * 48 g_interp_nearest, 49 g_prelu, 50 g_pixelshuffle, 51 g_input_f32, 52 g_input_u8, 53 g_output_f32, 54 g_output_u8. */
+int uva_net_debug_generic_launches(const uva_net* net, long long* counts, int capacity, int* n);
 
 /* Test hook (host only): the work lists of the generic executor's persistent kernels for an h x w plane on `grid`
  * workgroups -- kind 0: rdb4_kernel (a residual dense block's first four convolutions, models/4x_Valar_v1.param:6-19),

@@ -28,6 +28,8 @@ SYMBOLS = [
     "uva_frame_diff", "uva_frame_diff_device", "uva_net_set_skip_repeats", "uva_net_reset_reference", "uva_net_skip_stats",
     # 15 + 16 bits through the 1x net (additive as well)
     "uva_net_enable_u16_1x",
+    # 15 + the generic executor's launch census (additive as well)
+    "uva_net_debug_generic_launches",
 ]
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -107,6 +109,7 @@ def load():
     decl("uva_png_deflate_u8", [c_i, c_p, c_i, c_i, c_sz, c_p, c_sz])
     decl("uva_debug_png_deflate_host", [c_p, c_i, c_i, c_sz, c_p, c_sz])
     decl("uva_net_debug_generic_plan", [c_p, pi])
+    decl("uva_net_debug_generic_launches", [c_p, pll, c_i, pi])
     decl("uva_debug_generic_segments", [c_i, c_i, c_i, c_i, c_p, c_sz, psz, c_p])
     decl("uva_debug_generic_segments_planes", [c_i, c_p, c_i, c_i, c_p, c_sz, psz, c_p])
     decl("uva_debug_generic_batches", [c_i, c_i, c_i, c_i, ctypes.c_longlong, c_p, c_sz, psz])

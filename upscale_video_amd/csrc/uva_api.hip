@@ -128,6 +128,11 @@ std::set<uva_net*> g_nets;
 
 }  // namespace
 
+
+// uva_net::glaunch slots (include/uva.h uva_net_debug_generic_launches): 0..39 are the attr_set slots of the kernels that have
+// one (11-23 g_conv3_lds, 24-27 / 29-31 g_conv3_sw, 28 rdb4_kernel, 32-34 g_conv3_sk), the rest have none
+enum { GL_CONV1 = 40, GL_CONV3, GL_SWW, GL_SWW_SUM, GL_SWW_SUM2, GL_AXPBY, GL_AXPBY_STRIDED, GL_CONCAT_PART, GL_INTERP, GL_PRELU,
+       GL_PIXELSHUFFLE, GL_INPUT_F32, GL_INPUT_U8, GL_OUTPUT_F32, GL_OUTPUT_U8, GL_COUNT };
 struct uva_net {
     int device = 0;
     Graph g;
@@ -146,6 +151,7 @@ struct uva_net {
     size_t d_fin_cap = 0, d_fout_cap = 0;
     _Float16* d_sink = nullptr;   // where out-of-image lanes of the trunk kernel store to
     bool attr_set[40] = {false};  // hipFuncAttributeMaxDynamicSharedMemorySize done for kernel slot k on this net's device
+    long long glaunch[GL_COUNT] = {0};   // generic executor: launches per kernel instantiation since the net was created (uva_net_debug_generic_launches)
     int last_act_buf = 0;         // which ping-pong buffer the last run_graph() left its last trunk activation in
     bool generic_fuse_add = true; // generic graphs: sums that follow a convolution are done in its epilogue (UVA_GENERIC_FUSE_ADD=0: own launch)
     bool generic_lds_conv = true; // generic graphs: 3x3 convolutions through g_conv3_lds (UVA_GENERIC_LDS=0: the plain g_conv<3>)
@@ -1532,6 +1538,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
             EvPairScope evp(n, 1, n->prof);
             HIP_TRY(evp.begin());
             hipLaunchKernelGGL(rdb4_kernel, dim3(plan.grid), dim3(256), rdb4_lds_bytes(), n->stream, ra);
+            ++n->glaunch[28];
             HIP_TRY(hipGetLastError());
             HIP_TRY(evp.end());
             for (PlaneState& ps : P) finish_layer(ps);
@@ -1585,6 +1592,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                     EvPairScope evp(n, 2, n->prof && cd.cin_pad == 192);
                     HIP_TRY(evp.begin());
                     hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), lds, n->stream, sa);
+                    ++n->glaunch[slot];
                     HIP_TRY(evp.end());
                     return 0;
                 };
@@ -1600,6 +1608,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                     EvPairScope evp(n, 2, n->prof);
                     HIP_TRY(evp.begin());
                     HIP_TRY(launch_conv3_sww(n->stream, plan.grid, sa, variant == 4 ? 0 : 2, variant == 1 ? 2 : 0));
+                    ++n->glaunch[variant == 4 ? GL_SWW : variant == 0 ? GL_SWW_SUM : GL_SWW_SUM2];
                     HIP_TRY(evp.end());
                 }
                 else if (variant == 0 && sk_on) { if (launch_sw(g_conv3_sk<2, 0>, 32, sk_lds_bytes())) return 1; }
@@ -1626,6 +1635,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
         auto in = [&](int k) -> const GBuf& { return buf[root(gl.in[k])]; };
         switch (gl.kind) {
         case GLayer::INPUT:
+            ++n->glaunch[f32 ? GL_INPUT_F32 : GL_INPUT_U8];
             if (f32) hipLaunchKernelGGL(g_input_f32, dim3((w + T - 1) / T, h), dim3(T), 0, n->stream, (const float*)ps.j.src, h, w, o.p, o.cpad);
             else hipLaunchKernelGGL(g_input_u8, dim3((w + T - 1) / T, h), dim3(T), 0, n->stream, (const uint8_t*)ps.j.src, ps.j.src_stride, ps.j.sy0, ps.j.sx0, h, w, o.p, o.cpad);
             break;
@@ -1668,6 +1678,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                         n->attr_set[slot] = true;
                     }
                     hipLaunchKernelGGL(kern, g3, dim3(64 * nw), lds, n->stream, ga);
+                    ++n->glaunch[slot];
                     return 0;
                 };
                 if (gl.ksize == 1) {
@@ -1687,6 +1698,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                 break;
             }
             const dim3 grid((a.w + 63) / 64, (a.h + 3) / 4, (cd.cout_pad + 63) / 64);
+            ++n->glaunch[gl.ksize == 3 ? GL_CONV3 : GL_CONV1];
             if (gl.ksize == 3)
                 hipLaunchKernelGGL(g_conv<3>, grid, dim3(256), 0, n->stream, a.p, a.cpad, cd.wpk, cd.bias, o.p, o.c, cd.cout_pad, o.cpad, a.h, a.w, gl.has_act ? 1 : 0, gl.act_slope);
             else
@@ -1699,11 +1711,13 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                 // an operand or the result is a channel range of a wider array (dense chain): per-pixel strides
                 if (o.c % 8) return fail("generic executor: strided add needs a multiple of 8 channels");
                 const size_t npix = (size_t)(o.h + 3) * (o.w + 2), work = npix * (o.c / 8);
+                ++n->glaunch[GL_AXPBY_STRIDED];
                 hipLaunchKernelGGL(g_axpby_strided, dim3((unsigned)((work + T - 1) / T)), dim3(T), 0, n->stream, in(0).p, in(0).cpad,
                                    gl.coeffs[0], in(1).p, in(1).cpad, gl.coeffs[1], o.p, o.cpad, o.c / 8, npix);
                 break;
             }
             const size_t n8 = o.elems() / 8;
+            ++n->glaunch[GL_AXPBY];
             hipLaunchKernelGGL(g_axpby, dim3((unsigned)((n8 + T - 1) / T)), dim3(T), 0, n->stream, (const half8*)in(0).p, gl.coeffs[0],
                                (const half8*)in(1).p, gl.coeffs[1], (half8*)o.p, n8);
             break;
@@ -1716,6 +1730,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
             for (size_t k = 0; k < (mode == 1 ? 1 : gl.in.size()); ++k) {
                 const GBuf& a = in((int)k);
                 const size_t work = npix * (a.c / 8);
+                ++n->glaunch[GL_CONCAT_PART];
                 hipLaunchKernelGGL(g_concat_part, dim3((unsigned)((work + T - 1) / T)), dim3(T), 0, n->stream, a.p, a.cpad, a.c, o.p, o.cpad, c_off, npix);
                 c_off += a.c;
             }
@@ -1724,17 +1739,20 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
         case GLayer::INTERP_NEAREST: {
             const GBuf& a = in(0);
             const size_t work = (size_t)o.h * o.w * (o.cpad / 8);
+            ++n->glaunch[GL_INTERP];
             hipLaunchKernelGGL(g_interp_nearest, dim3((unsigned)((work + T - 1) / T)), dim3(T), 0, n->stream, a.p, a.h, a.w, a.cpad, o.p, gl.factor);
             break;
         }
         case GLayer::PRELU: {
             const size_t npix = (size_t)(o.h + 3) * (o.w + 2), work = npix * o.c;
+            ++n->glaunch[GL_PRELU];
             hipLaunchKernelGGL(g_prelu, dim3((unsigned)((work + T - 1) / T)), dim3(T), 0, n->stream, in(0).p, n->gd.prelu[gl.slopes], o.p, o.c, o.cpad, npix);
             break;
         }
         case GLayer::PIXELSHUFFLE: {
             const GBuf& a = in(0);
             const size_t work = (size_t)o.h * o.w * o.c;
+            ++n->glaunch[GL_PIXELSHUFFLE];
             hipLaunchKernelGGL(g_pixelshuffle, dim3((unsigned)((work + T - 1) / T)), dim3(T), 0, n->stream, a.p, a.h, a.w, a.cpad, o.p, o.c, o.cpad, gl.factor);
             break;
         }
@@ -1749,11 +1767,14 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
         const PlaneJob& j = ps.j;
         const GBuf& res = ps.buf[root(g.out_blob)];
         const int s = g.scale;
+        if (f32) ++n->glaunch[GL_OUTPUT_F32];
         if (f32) hipLaunchKernelGGL(g_output_f32, dim3((j.w * s + T2 - 1) / T2, j.h * s), dim3(T2), 0, n->stream, res.p, j.h * s, j.w * s, res.cpad, (float*)j.dst);
         else if (out_conv >= 0) { /* written by the last convolution */ }
-        else if (j.cx1 > j.cx0 && j.cy1 > j.cy0)
+        else if (j.cx1 > j.cx0 && j.cy1 > j.cy0) {
+            ++n->glaunch[GL_OUTPUT_U8];
             hipLaunchKernelGGL(g_output_u8, dim3(((j.cx1 - j.cx0) * s + T2 - 1) / T2, (j.cy1 - j.cy0) * s), dim3(T2), 0, n->stream, res.p, j.h * s, j.w * s, res.cpad,
                                (uint8_t*)j.dst, j.dst_stride, j.sy0 * s, j.sx0 * s, j.cy0 * s, j.cy1 * s, j.cx0 * s, j.cx1 * s);
+        }
         HIP_TRY(hipGetLastError());
         done_with(ps, g.out_blob);
     }
@@ -2398,6 +2419,16 @@ int uva_net_debug_generic_plan(const uva_net* n, int* info)
     info[5] = 0;
     for (int c : g.group_channels) info[5] = std::max(info[5], c);
     info[6] = (int)find_rdbs(g).size();
+    return 0;
+}
+
+int uva_net_debug_generic_launches(const uva_net* n, long long* counts, int capacity, int* count)
+{
+    if (!n || !count) return fail("null argument");
+    if (!n->generic) return fail("not a generic graph");
+    *count = GL_COUNT;
+    if (!counts || capacity < GL_COUNT) return counts ? fail("uva_net_debug_generic_launches: capacity too small") : 0;
+    std::memcpy(counts, n->glaunch, sizeof n->glaunch);
     return 0;
 }
 

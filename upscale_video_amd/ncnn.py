@@ -641,6 +641,15 @@ class Net:
         _lib.check(self._L.uva_net_kernel_stats(self._h, kind, n, ms))
         return n.value, ms.value
 
+    def debug_generic_launches(self):
+        """launches per kernel instantiation of the generic executor since this net was made (include/uva.h
+        uva_net_debug_generic_launches lists the indices): a test's proof that the kernel it is about ran"""
+        n = ctypes.c_int(0)
+        _lib.check(self._L.uva_net_debug_generic_launches(self._h, None, 0, ctypes.byref(n)))
+        counts = (ctypes.c_longlong * n.value)()
+        _lib.check(self._L.uva_net_debug_generic_launches(self._h, counts, n.value, ctypes.byref(n)))
+        return list(counts)
+
     def debug_read_activation(self, conv_idx, h, w):
         out = np.empty((self.num_features, h, w), np.float32)
         _lib.check(self._L.uva_net_debug_read_activation(self._h, conv_idx, out.ctypes.data, h, w))
