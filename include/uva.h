@@ -53,7 +53,10 @@ extern "C" {
                                    uva_net_reset_reference, uva_net_skip_stats (additive: off unless asked for)
                                15 + 16 bits through the 1x net: + uva_net_enable_u16_1x, kind 3 of uva_net_kernel_stats (additive: off
                                    unless asked for)
-                               15 + launch census: + uva_net_debug_generic_launches (additive: a host-side test hook) */
+                               15 + launch census: + uva_net_debug_generic_launches (additive: a host-side test hook)
+                               15 + 16-bit PNGs: + uva_png_workspace_bytes16, uva_png_assemble16, uva_png_deflate_u16,
+                                   uva_debug_png_deflate_host16, uva_png_decode_bgr16, uva_net_submit_u16_png (additive: every 8-bit PNG
+                                   entry keeps its signature and its bytes) */
 
 typedef struct uva_net uva_net;
 
@@ -306,6 +309,42 @@ int uva_debug_zlib_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t 
 /* Test hook (host only): the kernel's arithmetic restated on the host, block for block and bit for bit, into an
  * ordinary buffer of uva_png_workspace_bytes(h, w) bytes. */
 int uva_debug_png_deflate_host(const uint8_t* bgr, int h, int w, size_t stride, void* png_ws, size_t png_ws_bytes);
+
+/* ---- the PNG route at 16 bits (csrc/uva_png.hip.h png_deflate_kernel16) -------------------
+ * The reference extracts its frames as rgb24 PNGs (upscale/upscale_processing.py:223-232) and merges the result frames with
+ * -pix_fmt p010le by default (upscale_video.py:28-30, upscale/upscale_processing.py:632-633): 10-bit video out of 256 levels.
+ * With the frames extracted as rgb48be instead, these entries keep 16 bits from file to file: u16 HWC BGR frames (unorm16,
+ * little-endian samples, addresses and strides even) and 16-bit RGB PNGs -- colour type 2, depth 16, Sub on every scanline
+ * (bpp 6), one deflate block per group of rows with one of eight fixed literal codes. */
+/* uva_png_workspace_bytes for the 16-bit encoder (cv2.imwrite of a CV_16U frame, :288, :519): the workspaces of the two
+ * encoders differ in size and layout.  0 for frames it does not take (wider than 8 191 pixels). */
+size_t uva_png_workspace_bytes16(int h, int w);
+/* uva_png_assemble for a workspace the 16-bit encoder filled (cv2.imwrite's framing, :288, :519): IHDR with depth 16, the same
+ * checksum combination.  A workspace remembers which encoder filled it: this call refuses an 8-bit one, uva_png_assemble a
+ * 16-bit one, each with uva_last_error saying so -- never a file framed with the wrong depth. */
+int uva_png_assemble16(const void* png_ws, int h, int w, uint8_t* out, size_t cap, size_t* len);
+/* uva_png_deflate_u8 for a u16 BGR frame in host memory (cv2.imwrite(frame.png) of a CV_16U frame, :288, :519); stride in
+ * bytes.  png_ws: page-locked, uva_png_workspace_bytes16(h, w) bytes. */
+int uva_png_deflate_u16(int gpu, const uint16_t* bgr, int h, int w, size_t stride, void* png_ws, size_t png_ws_bytes);
+/* Test hook (host only): png_deflate_kernel16's arithmetic restated on the host, block for block and bit for bit, into an
+ * ordinary buffer of uva_png_workspace_bytes16(h, w) bytes (the kernel's reference; what cv2.imwrite's encoder is to the
+ * reference, :288). */
+int uva_debug_png_deflate_host16(const uint16_t* bgr, int h, int w, size_t stride, void* png_ws, size_t png_ws_bytes);
+/* cv2.imread(path, cv2.IMREAD_UNCHANGED) of a 16-bit frame (the reference reads its frames at :263, :487) for a file image in
+ * memory, host only, any thread: 16-bit RGB, RGBA (alpha dropped) or grey (replicated), all five filter types, into u16 HWC BGR;
+ * cap counts BYTES (h*w*6 are needed).  An 8-bit file of a kind uva_png_decode_bgr takes comes back widened v * 257, the 16-bit
+ * route's convention for 8-bit samples (above).  out == NULL: only *h, *w are set.  Returns 0, 1 for a corrupt file (chunk CRC,
+ * Adler-32 and stream length are checked; a header that promises more pixels than its data can hold is refused before anything
+ * is allocated, on the size query too), 2 for palette, interlaced and 1/2/4-bit files. */
+int uva_png_decode_bgr16(const uint8_t* file, size_t len, uint16_t* out, size_t cap, int* h, int* w);
+/* uva_net_submit_u8_png on 16-bit samples (the imread -> net -> imwrite hop of :263-288 and :487-519 without its 8-bit files):
+ * `in` is a u16 BGR frame (in_stride in bytes), the u16 result stays in HBM, png_deflate_kernel16 follows the net on its stream
+ * and the blocks reach `png_ws` (page-locked, uva_png_workspace_bytes16(h*scale, w*scale) bytes) as in the 8-bit call: the same
+ * guess of the download's size, the rest fetched by uva_net_collect_u8(ticket); then uva_png_assemble16.  Tiling arguments as in
+ * uva_net_submit_u8.  Nets: the 16-bit route's -- the 1x net only after uva_net_enable_u16_1x and with tile_size 0; refused
+ * with uva_last_error set otherwise.  Takes no part in uva_net_set_skip_repeats, like the 8-bit PNG entry. */
+long long uva_net_submit_u16_png(uva_net* net, const uint16_t* in, int h, int w, size_t in_stride, void* png_ws,
+                                 size_t png_ws_bytes, int tile_size, int border);
 
 /* Same, with in/out already resident in this device's HBM (dense rows: in_stride = 3*w,
  * out_stride = 3*w*s unless stated).  Asynchronous on the net's stream; follow with

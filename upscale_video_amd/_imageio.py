@@ -40,8 +40,45 @@ def _fast_png(path):
     return out if rc == 0 else None
 
 
-def imread(path):
-    """-> u8 [h][w][3] BGR, or None if unreadable (cv2.imread's convention)."""
+def _imread16(path):
+    """-> u16 [h][w][3] BGR or None.  cv2.IMREAD_UNCHANGED where cv2 is present (8-bit files widened v * 257, the 16-bit route's
+    convention for 8-bit samples); otherwise the library's reader (include/uva.h uva_png_decode_bgr16).  Never Pillow: it
+    opens a 16-bit RGB PNG as 8-bit RGB and drops the low bytes without a word."""
+    if _cv2 is not None:
+        img = _cv2.imread(path, _cv2.IMREAD_UNCHANGED)
+        if img is None:
+            return None
+        if img.ndim == 2:
+            img = np.repeat(img[:, :, None], 3, 2)
+        img = img[:, :, :3]
+        if img.dtype == np.uint8:
+            return img.astype(np.uint16) * 257
+        return np.ascontiguousarray(img) if img.dtype == np.uint16 else None
+    import ctypes
+    from . import _lib
+    L = _lib.load()          # no library: an error (there is no other reader that keeps 16 bits)
+    if not hasattr(L, "uva_png_decode_bgr16"):
+        raise _lib.UvaError("this libuva build has no 16-bit PNG reader: rebuild it")
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+    except OSError:
+        return None
+    h, w = ctypes.c_int(0), ctypes.c_int(0)
+    if L.uva_png_decode_bgr16(data, len(data), None, 0, h, w):
+        return None
+    out = np.empty((h.value, w.value, 3), np.uint16)
+    rc = L.uva_png_decode_bgr16(data, len(data), out.ctypes.data, out.nbytes, h, w)
+    return out if rc == 0 else None
+
+
+def imread(path, bit_depth=8):
+    """-> u8 [h][w][3] BGR, or None if unreadable (cv2.imread's convention).  bit_depth=16: u16 BGR instead (16-bit files as
+    they are, 8-bit files widened v * 257)."""
+    if bit_depth == 16:
+        return _imread16(path)
+    if bit_depth != 8:
+        raise ValueError("bit_depth must be 8 or 16")
     if _cv2 is not None:
         return _cv2.imread(path)
     img = _fast_png(path)
@@ -83,6 +120,26 @@ def png_bytes(bgr, level=1):
             chunk(b"IDAT", deflate.compress(rows.tobytes()) + deflate.flush()) + chunk(b"IEND", b""))
 
 
+def png_bytes16(bgr, level=1):
+    """png_bytes for a u16 BGR frame: a 16-bit RGB PNG (samples big-endian, Sub over 6 bytes), what cv2.imwrite writes for a
+    CV_16U frame.  The host route of the 16-bit PNG path: no GPU, and UVA_GPU_PNG=0."""
+    import struct
+    import zlib
+    h, w, _ = bgr.shape
+    flat = np.ascontiguousarray(bgr[:, :, ::-1]).astype(">u2").view(np.uint8).reshape(h, 6 * w)
+    rows = np.empty((h, 1 + 6 * w), np.uint8)
+    rows[:, 0] = 1
+    rows[:, 1:7] = flat[:, :6]
+    np.subtract(flat[:, 6:], flat[:, :-6], out=rows[:, 7:])
+    deflate = zlib.compressobj(level, zlib.DEFLATED, 15, 9, zlib.Z_RLE)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 2, 0, 0, 0)) +
+            chunk(b"IDAT", deflate.compress(rows.tobytes()) + deflate.flush()) + chunk(b"IEND", b""))
+
+
 def to_u8(arr):
     """cv2's Mat::convertTo(CV_8U): round half to even, saturate to [0, 255]."""
     a = np.asarray(arr)
@@ -92,9 +149,17 @@ def to_u8(arr):
 
 
 def imwrite(path, arr):
-    """arr: [h][w][3] BGR, u8 or float (floats are converted like cv2.imwrite does)."""
+    """arr: [h][w][3] BGR, u8 or float (floats are converted like cv2.imwrite does); a u16 array is written as a 16-bit PNG,
+    as cv2.imwrite writes a CV_16U frame."""
     if _cv2 is not None:
         return bool(_cv2.imwrite(path, arr))
+    if np.asarray(arr).dtype == np.uint16:
+        bgr = np.asarray(arr)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("frame must be [h][w][3]")
+        with open(path, "wb") as f:
+            f.write(png_bytes16(bgr))
+        return True
     bgr = to_u8(arr)
     if bgr.ndim != 3 or bgr.shape[2] != 3:
         raise ValueError("frame must be [h][w][3]")

@@ -31,6 +31,12 @@ SYMBOLS = [
     # 15 + the generic executor's launch census (additive as well)
     "uva_net_debug_generic_launches",
 ]
+# 15 + 16-bit PNGs (additive as well).  Optional at load time: an ABI-15 library or stand-in without them (an older build,
+# tests/standin_libuva.py) still loads and serves every 8-bit call; what needs them (ncnn.PngWorkspace(bit_depth=16),
+# Net.submit_u16_png, _imageio.imread(bit_depth=16)) asks with hasattr and says what is missing.
+OPTIONAL_SYMBOLS = ["uva_png_workspace_bytes16", "uva_png_assemble16", "uva_png_deflate_u16", "uva_debug_png_deflate_host16",
+                    "uva_png_decode_bgr16", "uva_net_submit_u16_png"]
+SYMBOLS += OPTIONAL_SYMBOLS
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
 _lib = None
@@ -64,7 +70,8 @@ def load():
                        "A/B build through)" % (L.uva_abi_version(), ABI_VERSION))
     if not old_ok:
         for n in SYMBOLS:   # AttributeError here means the .so is stale: rebuild it
-            getattr(L, n)
+            if n not in OPTIONAL_SYMBOLS:
+                getattr(L, n)
 
     def decl(name, argtypes=None, restype=None, keep_restype=False):
         if not hasattr(L, name):
@@ -83,6 +90,12 @@ def load():
     decl("uva_net_submit_u8", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i], ctypes.c_longlong)
     decl("uva_net_submit_u8_png", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i], ctypes.c_longlong)
     decl("uva_png_workspace_bytes", [c_i, c_i], c_sz)
+    decl("uva_png_workspace_bytes16", [c_i, c_i], c_sz)
+    decl("uva_net_submit_u16_png", [c_p, c_p, c_i, c_i, c_sz, c_p, c_sz, c_i, c_i], ctypes.c_longlong)
+    decl("uva_png_assemble16", [c_p, c_i, c_i, c_p, c_sz, psz])
+    decl("uva_png_deflate_u16", [c_i, c_p, c_i, c_i, c_sz, c_p, c_sz])
+    decl("uva_debug_png_deflate_host16", [c_p, c_i, c_i, c_sz, c_p, c_sz])
+    decl("uva_png_decode_bgr16", [c_p, c_sz, c_p, c_sz, pi, pi])
     decl("uva_pix_frame_bytes", [c_i, c_i, c_i], c_sz)
     decl("uva_net_submit_pix", [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i], ctypes.c_longlong)
     decl("uva_pix_convert", [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i])

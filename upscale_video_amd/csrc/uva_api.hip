@@ -21,6 +21,7 @@
 
 namespace uva {   // uva_pngread.cpp
 int png_read_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int* h_out, int* w_out, std::string& err);
+int png_read_bgr16(const uint8_t* file, size_t len, uint16_t* out, size_t cap, int* h_out, int* w_out, std::string& err);
 int zlib_decompress_exact(const uint8_t* in, size_t n, uint8_t* out, size_t out_len, std::string& err);
 }
 
@@ -177,7 +178,7 @@ struct uva_net {
         size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0, d_png_cap = 0, d_pin_cap = 0, d_pout_cap = 0, d_rs_cap = 0;
         uint8_t* png_ws = nullptr;       // PNG submit: the caller's workspace, how many packed bytes went there with the
         size_t png_sent = 0;             // frame's download, and the frame size (collect fetches the rest, if any)
-        int png_h = 0, png_w = 0;
+        int png_h = 0, png_w = 0, png_bits = 8;   // (png_bits 16: the 16-bit encoder's workspace layout)
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
         static constexpr int BANDS = 4;  // a staged (pageable) result comes down in row bands: collect copies band k to the
         hipEvent_t ev_band[BANDS] = {nullptr, nullptr, nullptr, nullptr};   // caller while band k + 1 is still on PCIe
@@ -187,6 +188,7 @@ struct uva_net {
     };
     PipeSlot pipe[PIPE_SLOTS];
     size_t png_guess = 0;                // packed bytes of the last PNG frame collected: the next download's size
+    size_t png_guess16 = 0;              // ... of the last 16-bit PNG frame (about twice the size: a guess of its own)
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     long long next_ticket = 0;
     // uva_net_set_skip_repeats: the kept frame -- the last frame the net ran on -- with its packed input
@@ -1949,6 +1951,8 @@ struct PngDev {
     uint32_t* d_code = nullptr;
     uint8_t* d_hdr = nullptr;
     uint32_t* d_crcmul = nullptr;
+    uint32_t* d_code16 = nullptr;     // the 16-bit encoder's tables (png_tables16)
+    uint8_t* d_hdr16 = nullptr;
     bool attr_set = false;
     // the synchronous utility's own buffers
     hipStream_t stream = nullptr;
@@ -1971,6 +1975,8 @@ void png_release_all()
         if (c.d_code) (void)hipFree(c.d_code);
         if (c.d_hdr) (void)hipFree(c.d_hdr);
         if (c.d_crcmul) (void)hipFree(c.d_crcmul);
+        if (c.d_code16) (void)hipFree(c.d_code16);
+        if (c.d_hdr16) (void)hipFree(c.d_hdr16);
         if (c.d_frame) (void)hipFree(c.d_frame);
         if (c.d_blocks) (void)hipFree(c.d_blocks);
         c = PngDev();
@@ -1993,6 +1999,12 @@ int png_dev(int device, PngDev** out)
         HIP_TRY(hipMalloc((void**)&c.d_crcmul, sizeof T.crcmul));
         HIP_TRY(hipMemcpy(c.d_crcmul, T.crcmul, sizeof T.crcmul, hipMemcpyHostToDevice));
         HIP_TRY(hipFuncSetAttribute((const void*)png_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, png_lds_bytes()));
+        const PngTables16& T16 = png_tables16();
+        HIP_TRY(hipMalloc((void**)&c.d_code16, sizeof T16.code));
+        HIP_TRY(hipMalloc((void**)&c.d_hdr16, sizeof T16.hdr));
+        HIP_TRY(hipMemcpy(c.d_code16, T16.code, sizeof T16.code, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.d_hdr16, T16.hdr, sizeof T16.hdr, hipMemcpyHostToDevice));
+        HIP_TRY(hipFuncSetAttribute((const void*)png_deflate_kernel16, hipFuncAttributeMaxDynamicSharedMemorySize, png_lds_bytes()));
         c.attr_set = true;
     }
     *out = &c;
@@ -2019,39 +2031,60 @@ int png_launch(int device, hipStream_t stream, const uint8_t* d_frame, size_t st
     return 0;
 }
 
+// the same for an h x w u16 BGR frame (stride in bytes): png_deflate_kernel16 into png_workspace_bytes(h, w, 16)
+int png_launch16(int device, hipStream_t stream, const uint8_t* d_frame, size_t stride, int h, int w, uint8_t* d_blocks)
+{
+    if (!png_takes(h, w, 16)) return fail("PNG encoder: frame width out of range");
+    if ((((uintptr_t)d_frame | stride) & 1) != 0) return fail("PNG encoder: odd address or stride of a 16-bit frame");
+    PngDev* c = nullptr;
+    if (png_dev(device, &c)) return 1;
+    PngArgs16 a;
+    std::memset(&a, 0, sizeof a);
+    a.src = d_frame; a.stride = stride; a.h = h; a.w = w;
+    a.rows_per_block = png_rows_per_block(w, 16);
+    a.nblocks = png_num_blocks(h, w, 16);
+    a.code = c->d_code16; a.hdr = c->d_hdr16; a.crcmul = c->d_crcmul;
+    for (int t = 0; t < PNG_TABLES16; ++t) a.hdr_bits[t] = png_tables16().hdr_bits[t];
+    a.meta = (uint32_t*)d_blocks;
+    a.slots = d_blocks + png_meta_bytes(h, w, 16);
+    hipLaunchKernelGGL(png_deflate_kernel16, dim3(a.nblocks), dim3(PNG_THREADS), png_lds_bytes(), stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // device layout of a frame's encoder output: [png_workspace_bytes(h, w): meta + slots][the same bound again: the packed bytes]
-size_t png_device_bytes(int h, int w) { return 2 * png_workspace_bytes(h, w); }
-uint8_t* png_packed(uint8_t* d_blocks, int h, int w) { return d_blocks + png_workspace_bytes(h, w); }
+size_t png_device_bytes(int h, int w, int bits = 8) { return 2 * png_workspace_bytes(h, w, bits); }
+uint8_t* png_packed(uint8_t* d_blocks, int h, int w, int bits = 8) { return d_blocks + png_workspace_bytes(h, w, bits); }
 
 // the blocks at d_blocks, concatenated behind them (a device-to-device copy: microseconds), on `stream`
-int png_pack_launch(hipStream_t stream, uint8_t* d_blocks, int h, int w)
+int png_pack_launch(hipStream_t stream, uint8_t* d_blocks, int h, int w, int bits = 8)
 {
     PngPackArgs a;
     a.meta = (const uint32_t*)d_blocks;
-    a.slots = d_blocks + png_meta_bytes(h, w);
-    a.nblocks = png_num_blocks(h, w);
+    a.slots = d_blocks + png_meta_bytes(h, w, bits);
+    a.nblocks = png_num_blocks(h, w, bits);
     a.out_meta = nullptr;
-    a.out_data = png_packed(d_blocks, h, w);
+    a.out_data = png_packed(d_blocks, h, w, bits);
     hipLaunchKernelGGL(png_pack_kernel, dim3(a.nblocks), dim3(PNG_PACK_THREADS), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 // meta + the first `bytes` packed bytes -> the page-locked workspace, by the copy engine, on `stream`
-int png_download(hipStream_t stream, const uint8_t* d_blocks, int h, int w, void* ws, size_t bytes)
+int png_download(hipStream_t stream, const uint8_t* d_blocks, int h, int w, void* ws, size_t bytes, int bits = 8)
 {
-    const size_t mb = png_meta_bytes(h, w);
+    const size_t mb = png_meta_bytes(h, w, bits);
     HIP_TRY(hipMemcpyAsync(ws, d_blocks, mb, hipMemcpyDeviceToHost, stream));
-    if (bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)ws + mb, d_blocks + png_workspace_bytes(h, w), bytes, hipMemcpyDeviceToHost, stream));
+    if (bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)ws + mb, d_blocks + png_workspace_bytes(h, w, bits), bytes, hipMemcpyDeviceToHost, stream));
     return 0;
 }
 
 // packed bytes of the frame whose meta is in the workspace
-size_t png_total_bytes(const void* ws, int h, int w)
+size_t png_total_bytes(const void* ws, int h, int w, int bits = 8)
 {
     const uint32_t* m = (const uint32_t*)ws;
     size_t t = 0;
-    for (int b = 0, nb = png_num_blocks(h, w); b < nb; ++b) t += m[(size_t)b * PNG_META_WORDS];
+    for (int b = 0, nb = png_num_blocks(h, w, bits); b < nb; ++b) t += m[(size_t)b * PNG_META_WORDS];
     return t;
 }
 
@@ -2589,6 +2622,7 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
                     int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
                     int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0, bool may_skip = false)
 {
+    const int png_bits = u16 ? 16 : 8;     // (png_ws: the encoder that matches the net's frames)
     if (check_dims(n, h, w)) return -1;
     if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
     if (png_ws && !is_pinned_host(png_ws)) { fail("PNG workspace must be page-locked host memory (uva_host_alloc)"); return -1; }
@@ -2627,9 +2661,9 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     const uint8_t* d_res = rs ? ps.d_rs : ps.d_out;                        // the BGR frame that leaves
     std::string rs_err;
     if (png_ws) {
-        if (uva_png_workspace_bytes(h * s, w * s) == 0) { fail("PNG encoder: frame width out of range"); return -1; }
-        if (png_ws_bytes < png_workspace_bytes(h * s, w * s)) { fail("PNG workspace too small"); return -1; }
-        if (grow_dev(&ps.d_png, &ps.d_png_cap, png_device_bytes(h * s, w * s))) return -1;
+        if (!png_takes(h * s, w * s, png_bits)) { fail("PNG encoder: frame width out of range"); return -1; }
+        if (png_ws_bytes < png_workspace_bytes(h * s, w * s, png_bits)) { fail("PNG workspace too small"); return -1; }
+        if (grow_dev(&ps.d_png, &ps.d_png_cap, png_device_bytes(h * s, w * s, png_bits))) return -1;
     }
     // H2D: straight from the caller's buffer when it is pinned (uva_host_alloc / hipHostMalloc /
     // hipHostRegister), through this slot's pinned staging buffer otherwise
@@ -2710,8 +2744,9 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     }
     // png: the deflate kernel follows the net on its stream and leaves the blocks in HBM, packed end to end by a second
     // (device-to-device) kernel: 0.15 ms per 4K frame together
-    if (png_ws && (png_launch(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png) ||
-                   png_pack_launch(n->stream, ps.d_png, h * s, w * s))) return -1;
+    if (png_ws && ((u16 ? png_launch16(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png)
+                        : png_launch(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png)) ||
+                   png_pack_launch(n->stream, ps.d_png, h * s, w * s, png_bits))) return -1;
     if (!repeat && (tryhip(hipEventRecord(ps.ev_done, n->stream), "hipEventRecord") ||
                     tryhip(hipStreamWaitEvent(n->s_d2h, ps.ev_done, 0), "hipStreamWaitEvent"))) return -1;
     if (rp_on && !repeat) {
@@ -2728,11 +2763,12 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
         // many bytes there are is only known on the device: as many as the previous frame had (+ 6 %) go now, collect
         // fetches the rest should this frame be larger.  (A kernel writing to host memory instead keeps CUs busy for
         // the PCIe transfer: 0.24 ms per 4K frame that the next frame's net then waits for.)
-        const size_t cap = png_workspace_bytes(h * s, w * s) - png_meta_bytes(h * s, w * s);
-        const size_t guess = n->png_guess ? std::min(cap, n->png_guess + n->png_guess / 16 + 65536) : std::min(cap, out_bytes * 5 / 8);
-        if (png_download(n->s_d2h, ps.d_png, h * s, w * s, png_ws, guess)) return -1;
+        const size_t cap = png_workspace_bytes(h * s, w * s, png_bits) - png_meta_bytes(h * s, w * s, png_bits);
+        const size_t last = u16 ? n->png_guess16 : n->png_guess;
+        const size_t guess = last ? std::min(cap, last + last / 16 + 65536) : std::min(cap, out_bytes * 5 / 8);
+        if (png_download(n->s_d2h, ps.d_png, h * s, w * s, png_ws, guess, png_bits)) return -1;
         if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return -1;
-        ps.png_ws = (uint8_t*)png_ws; ps.png_sent = guess; ps.png_h = h * s; ps.png_w = w * s;
+        ps.png_ws = (uint8_t*)png_ws; ps.png_sent = guess; ps.png_h = h * s; ps.png_w = w * s; ps.png_bits = png_bits;
         ps.user_out = nullptr;
         ps.busy = true;
         ps.ticket = n->next_ticket;
@@ -2786,6 +2822,18 @@ long long uva_net_submit_u8_png(uva_net* n, const uint8_t* in, int h, int w, siz
 {
     if (!png_ws) { fail("null PNG workspace"); return -1; }
     return submit_u8(n, in, h, w, in_stride, nullptr, 0, tile_size, border, png_ws, png_ws_bytes);
+}
+
+long long uva_net_submit_u16_png(uva_net* n, const uint16_t* in, int h, int w, size_t in_stride, void* png_ws, size_t png_ws_bytes,
+                                 int tile_size, int border)
+{
+    if (!png_ws) { fail("null PNG workspace"); return -1; }
+    if (check_dims(n, h, w)) return -1;
+    if (ensure_device(n) || check_u16_net(n)) return -1;
+    if (is_sub10_net(n) && tile_size > 0) { fail("the 16-bit route runs the 1x net on whole frames only (tile_size 0)"); return -1; }
+    if ((((uintptr_t)in | in_stride) & 1) != 0) { fail("odd address or stride of a 16-bit frame"); return -1; }
+    return submit_u8(n, (const uint8_t*)in, h, w, in_stride, nullptr, 0, tile_size, border, png_ws, png_ws_bytes, PIX_BGR48LE, PIX_BGR48LE,
+                     0, true);
 }
 
 size_t uva_pix_frame_bytes(int fmt, int h, int w) { return pix_frame_bytes(fmt, h, w); }
@@ -3112,6 +3160,68 @@ int uva_png_deflate_u8(int device, const uint8_t* bgr, int h, int w, size_t stri
     return 0;
 }
 
+size_t uva_png_workspace_bytes16(int h, int w)
+{
+    if (!png_takes(h, w, 16)) return 0;
+    return png_workspace_bytes(h, w, 16);
+}
+
+int uva_png_assemble16(const void* png_ws, int h, int w, uint8_t* out, size_t cap, size_t* len)
+{
+    if (!png_ws || uva_png_workspace_bytes16(h, w) == 0) return fail("bad argument");
+    std::string err;
+    if (png_assemble((const uint8_t*)png_ws, h, w, out, cap, len, err, 16)) return fail(err);
+    return 0;
+}
+
+int uva_png_deflate_u16(int device, const uint16_t* bgr, int h, int w, size_t stride, void* png_ws, size_t png_ws_bytes)
+{
+    if (!bgr || stride < (size_t)w * 6 || (((uintptr_t)bgr | stride) & 1) != 0) return fail("bad frame");
+    if (uva_png_workspace_bytes16(h, w) == 0) return fail("PNG encoder: frame width out of range");
+    if (!is_pinned_host(png_ws)) return fail("PNG workspace must be page-locked host memory (uva_host_alloc)");
+    PngDev* c = nullptr;
+    if (png_dev(device, &c)) return 1;
+    std::lock_guard<std::mutex> lk(g_png_util_mu);
+    HIP_TRY(hipSetDevice(device));
+    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    // (rows a multiple of 4 bytes apart on the device: the kernel then stages every width with dword loads)
+    const size_t row = (size_t)w * 6, pitch = (row + 3) & ~(size_t)3;
+    if (png_ws_bytes < png_workspace_bytes(h, w, 16)) return fail("PNG workspace too small");
+    if (grow_dev(&c->d_frame, &c->d_frame_cap, pitch * h) || grow_dev(&c->d_blocks, &c->d_blocks_cap, png_device_bytes(h, w, 16))) return 1;
+    HIP_TRY(hipMemcpy2DAsync(c->d_frame, pitch, bgr, stride, row, h, hipMemcpyHostToDevice, c->stream));
+    if (png_launch16(device, c->stream, c->d_frame, pitch, h, w, c->d_blocks) || png_pack_launch(c->stream, c->d_blocks, h, w, 16)) return 1;
+    if (png_download(c->stream, c->d_blocks, h, w, png_ws, 0, 16)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t total = png_total_bytes(png_ws, h, w, 16);
+    if (total > png_workspace_bytes(h, w, 16) - png_meta_bytes(h, w, 16)) return fail("PNG encoder: block sizes out of range");
+    HIP_TRY(hipMemcpy((uint8_t*)png_ws + png_meta_bytes(h, w, 16), png_packed(c->d_blocks, h, w, 16), total, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int uva_debug_png_deflate_host16(const uint16_t* bgr, int h, int w, size_t stride, void* png_ws, size_t png_ws_bytes)
+{
+    if (!bgr || !png_ws || stride < (size_t)w * 6 || uva_png_workspace_bytes16(h, w) == 0 || png_ws_bytes < png_workspace_bytes(h, w, 16))
+        return fail("bad argument");
+    png_deflate_host16((const uint8_t*)bgr, stride, h, w, (uint8_t*)png_ws);
+    return 0;
+}
+
+int uva_png_decode_bgr16(const uint8_t* file, size_t len, uint16_t* out, size_t cap, int* h, int* w)
+{
+    if (!file) return fail("null file image");
+    if (((uintptr_t)out & 1) != 0) return fail("odd address of a 16-bit frame");
+    std::string err;
+    int rc;
+    try {
+        rc = png_read_bgr16(file, len, out, cap, h, w, err);
+    } catch (const std::exception& e) {              // out of memory: an error, not a crash across the C ABI
+        return fail(std::string("PNG reader: ") + e.what());
+    }
+    if (rc == 1) return fail(err);
+    if (rc == 2) { fail("PNG of a kind the reader does not take (palette, interlaced or below 8 bits)"); return 2; }
+    return 0;
+}
+
 int uva_png_decode_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int* h, int* w)
 {
     if (!file) return fail("null file image");
@@ -3170,13 +3280,14 @@ int uva_net_collect_u8(uva_net* n, long long ticket)
     HIP_TRY(hipEventSynchronize(ps.ev_d2h));
     if (ps.png_ws) {
         // the meta is here: fetch what the download did not cover (a frame that compressed worse than the one before)
-        const size_t mb = png_meta_bytes(ps.png_h, ps.png_w), cap = png_workspace_bytes(ps.png_h, ps.png_w) - mb;
-        const size_t total = png_total_bytes(ps.png_ws, ps.png_h, ps.png_w);
+        const int pb = ps.png_bits;
+        const size_t mb = png_meta_bytes(ps.png_h, ps.png_w, pb), cap = png_workspace_bytes(ps.png_h, ps.png_w, pb) - mb;
+        const size_t total = png_total_bytes(ps.png_ws, ps.png_h, ps.png_w, pb);
         if (total > cap) { ps.busy = false; ps.png_ws = nullptr; return fail("PNG encoder: block sizes out of range"); }
         if (total > ps.png_sent)
-            HIP_TRY(hipMemcpy(ps.png_ws + mb + ps.png_sent, png_packed(ps.d_png, ps.png_h, ps.png_w) + ps.png_sent, total - ps.png_sent,
+            HIP_TRY(hipMemcpy(ps.png_ws + mb + ps.png_sent, png_packed(ps.d_png, ps.png_h, ps.png_w, pb) + ps.png_sent, total - ps.png_sent,
                               hipMemcpyDeviceToHost));
-        n->png_guess = total;
+        (pb == 16 ? n->png_guess16 : n->png_guess) = total;
         ps.png_ws = nullptr;
     }
     ps.busy = false;

@@ -8,7 +8,8 @@
 // per-symbol bounds checks while both buffers have slack, word-wise match copies), plus PNG un-filtering straight into
 // cv2's BGR layout.  RFC 1950 / 1951 / PNG 1.2; every check a careful reader makes is made (chunk CRCs, Adler-32, stream
 // length), a corrupt file is an error, never a crash.  8-bit RGB / RGBA / grey (+alpha), non-interlaced -- what ffmpeg's
-// `%d.extract.png` and cv2.imwrite produce; anything else returns 2 and the caller uses a general reader.
+// `%d.extract.png` and cv2.imwrite produce; anything else returns 2 and the caller uses a general reader.  png_read_bgr16 reads
+// the same kinds at 8 or 16 bits into u16 BGR (the PNG route at 16 bits).
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -509,15 +510,16 @@ bool unfilter(uint8_t* raw, int h, int w, int bpp, uint8_t* bgr, std::string& er
 
 }  // namespace
 
-// 0: decoded (out = h*w*3 bytes BGR, cv2.imread's IMREAD_COLOR), 1: corrupt / unreadable (err set), 2: a valid-looking
-// PNG of a kind this reader does not take (16-bit, palette, interlaced)
-int png_read_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int* h_out, int* w_out, std::string& err)
+namespace {
+
+// want_bits = 8: png_read_bgr; 16: png_read_bgr16 (out then holds h*w*3 little-endian u16 samples; cap in bytes)
+int png_read_any(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int* h_out, int* w_out, std::string& err, int want_bits)
 {
     crc_init();
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
     if (len < 8 + 25 + 12 || std::memcmp(file, sig, 8)) { err = "not a PNG file"; return 1; }
     size_t pos = 8;
-    int w = 0, h = 0, ctype = -1;
+    int w = 0, h = 0, ctype = -1, depth = 8;
     bool seen_ihdr = false, seen_iend = false;
     static thread_local std::vector<uint8_t> idat, raw;      // reused: a fresh 6 MB vector per frame is 1-2 ms of page faults
     idat.clear();
@@ -534,10 +536,12 @@ int png_read_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int*
             if (n != 13 || seen_ihdr) { err = "PNG: bad IHDR"; return 1; }
             seen_ihdr = true;
             w = (int)rd_be32(body); h = (int)rd_be32(body + 4);
+            depth = body[8];
             ctype = body[9];
             if (w <= 0 || h <= 0 || w > (1 << 24) || h > (1 << 24)) { err = "PNG: bad dimensions"; return 1; }
             if (body[10] || body[11]) { err = "PNG: unknown compression or filter method"; return 1; }
-            if (body[8] != 8 || body[12] != 0 || !(ctype == 0 || ctype == 2 || ctype == 4 || ctype == 6)) return 2;
+            if (!(depth == 8 || (depth == 16 && want_bits == 16)) || body[12] != 0 || !(ctype == 0 || ctype == 2 || ctype == 4 || ctype == 6))
+                return 2;
         } else if (!std::memcmp(type, "IDAT", 4)) {
             if (!seen_ihdr) { err = "PNG: IDAT before IHDR"; return 1; }
             if (++nidat == 1) { one_idat = body; one_len = n; }                       // the only chunk so far: no copy yet
@@ -556,18 +560,36 @@ int png_read_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int*
     const uint8_t* const zdata = nidat >= 2 ? idat.data() : one_idat;
     const size_t zlen = nidat >= 2 ? idat.size() : one_len;
     if (!seen_ihdr || !seen_iend || zlen == 0) { err = "PNG: missing IHDR, IDAT or IEND"; return 1; }
-    if (h_out) *h_out = h;
-    if (w_out) *w_out = w;
-    const size_t need = (size_t)h * w * 3;
-    if (!out) return 0;                                   // size query
-    if (cap < need) { err = "PNG: output buffer too small"; return 1; }
-    const int bpp = ctype == 0 ? 1 : ctype == 4 ? 2 : ctype == 2 ? 3 : 4;
+    const int chans = ctype == 0 ? 1 : ctype == 4 ? 2 : ctype == 2 ? 3 : 4, bps = depth / 8, bpp = chans * bps;
     // deflate cannot expand by more than 1032:1: a header that promises more than the IDAT data could hold is damage (or
     // an attempt to make the reader allocate terabytes)
-    if ((size_t)h * ((size_t)w * bpp + 1) > zlen * 1032 + 1024) { err = "PNG: image larger than its data can be"; return 1; }
+    const bool too_large = (size_t)h * ((size_t)w * bpp + 1) > zlen * 1032 + 1024;
+    // (the 16-bit entry says so to a size query as well: its callers allocate `out` from the answer)
+    if (want_bits == 16 && too_large) { err = "PNG: image larger than its data can be"; return 1; }
+    if (h_out) *h_out = h;
+    if (w_out) *w_out = w;
+    const size_t need = (size_t)h * w * 3 * (size_t)(want_bits / 8);
+    if (!out) return 0;                                   // size query
+    if (cap < need) { err = "PNG: output buffer too small"; return 1; }
+    if (too_large) { err = "PNG: image larger than its data can be"; return 1; }
     raw.resize((size_t)h * ((size_t)w * bpp + 1) + 8);                    // + slack for the word-wise match copy
     if (!zlib_decompress(zdata, zlen, raw.data(), raw.size() - 8, err)) return 1;
-    if (!unfilter(raw.data(), h, w, bpp, out, err)) return 1;
+    if (!unfilter(raw.data(), h, w, bpp, want_bits == 8 ? out : nullptr, err)) return 1;
+    if (want_bits == 16) {
+        // RGB(A) or grey(+alpha), 8 bits (widened v * 257: unorm8 -> unorm16 exactly) or 16 bits big-endian -> u16 B G R
+        uint16_t* const o16 = (uint16_t*)out;
+        const int step = chans >= 3 ? bps : 0;                // bytes from one colour channel to the next (grey: the same sample)
+        for (int y = 0; y < h; ++y) {
+            const uint8_t* s = raw.data() + (size_t)y * ((size_t)w * bpp + 1) + 1;
+            uint16_t* d = o16 + (size_t)y * w * 3;
+            for (int x = 0; x < w; ++x, s += bpp, d += 3)
+                for (int c = 0; c < 3; ++c) {
+                    const uint8_t* const q = s + (2 - c) * step;
+                    d[c] = bps == 2 ? (uint16_t)((q[0] << 8) | q[1]) : (uint16_t)(q[0] * 257);
+                }
+        }
+        return 0;
+    }
     if (bpp != 3)
     for (int y = 0; y < h; ++y) {
         const uint8_t* s = raw.data() + (size_t)y * ((size_t)w * bpp + 1) + 1;
@@ -578,6 +600,23 @@ int png_read_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int*
             for (int x = 0; x < w; ++x, s += bpp, d += 3) d[0] = d[1] = d[2] = s[0];                    // grey(+alpha)
     }
     return 0;
+}
+
+}  // namespace
+
+// 0: decoded (out = h*w*3 bytes BGR, cv2.imread's IMREAD_COLOR), 1: corrupt / unreadable (err set), 2: a valid-looking
+// PNG of a kind this reader does not take (16-bit, palette, interlaced)
+int png_read_bgr(const uint8_t* file, size_t len, uint8_t* out, size_t cap, int* h_out, int* w_out, std::string& err)
+{
+    return png_read_any(file, len, out, cap, h_out, w_out, err, 8);
+}
+
+// The same into u16 HWC BGR (little-endian; cap counts bytes, h*w*6 are needed): 16-bit RGB / RGBA (alpha dropped) / grey
+// (replicated) as they are, the 8-bit kinds widened v * 257 (cv2.imread(path, IMREAD_UNCHANGED) and a widening, on the 16-bit
+// PNG route).  2: palette, interlaced or 1/2/4-bit files.
+int png_read_bgr16(const uint8_t* file, size_t len, uint16_t* out, size_t cap, int* h_out, int* w_out, std::string& err)
+{
+    return png_read_any(file, len, (uint8_t*)out, cap, h_out, w_out, err, 16);
 }
 
 // test hook: the inflate alone (zlib-wrapped stream -> exactly out_len bytes)

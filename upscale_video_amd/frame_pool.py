@@ -17,6 +17,8 @@ output has been written, :295-296/:521-522), but
     and only the compressed blocks cross PCIe; a pool of encode threads frames them as a PNG file
     (zlib header, Adler-32, chunk CRC) and writes it.  UVA_GPU_PNG=0 keeps the frame route instead
     (`submit_u8`, zlib on the host's cores: ~180 ms of a core per 3840x2160 frame);
+  * a task may carry "bit_depth": 16 (default 8): its file is decoded to u16 BGR, the net runs on 16-bit samples and the
+    result is written as a 16-bit PNG (`submit_u16_png`; with UVA_GPU_PNG=0 a u16 frame comes back and zlib runs on the host);
   * every finished frame is reported to the caller's thread as the reference's log-item list, so
     `logging_callback`'s "any error item ends the run" (:40-51) happens in the main thread.
 
@@ -105,6 +107,7 @@ class _Worker:
         self.task_q, self.result_q = task_q, result_q
         self.factory = _resolve(factory)
         self.nets = {}
+        self.u16_nets = set()       # nets a 16-bit task has been prepared for
         self.rings = {}
         self.decoders = ThreadPoolExecutor(decode_threads, thread_name_prefix="decode")
         self.encoders = ThreadPoolExecutor(encode_threads, thread_name_prefix="encode")
@@ -128,7 +131,10 @@ class _Worker:
 
     def decode(self, task):
         try:
-            img = imread(task["src"])
+            depth = task.get("bit_depth", 8)         # a task without the key: 8 bits, as before
+            if depth not in (8, 16):
+                raise ValueError("bit_depth must be 8 or 16, not %r" % (depth,))
+            img = imread(task["src"], bit_depth=16) if depth == 16 else imread(task["src"])
             if img is None:
                 raise RuntimeError("cannot read " + str(task["src"]))
             self.ready.put((task, img, None))
@@ -140,34 +146,44 @@ class _Worker:
         key = (task["model_path"], task["model_file"], task["scale"])
         if key not in self.nets:
             self.nets[key] = self.factory(task["model_path"], task["model_file"], task["scale"], self.gpu)
-        return key, self.nets[key]
+        net = self.nets[key]
+        if task.get("bit_depth", 8) == 16 and key not in self.u16_nets:
+            # the 1x net takes 16-bit samples only when asked to (ncnn.Net.enable_u16_1x; its 8-bit calls are not affected)
+            if getattr(net, "scale", 0) == 1 and hasattr(net, "enable_u16_1x"):
+                net.enable_u16_1x()
+            self.u16_nets.add(key)
+        return key, net
 
-    def out_buffer(self, key, shape):
-        """Result ring of one (model, frame size): page-locked when the engine offers it.  A buffer is
+    def out_buffer(self, key, shape, depth=8):
+        """Result ring of one (model, frame size, bit depth): page-locked when the engine offers it.  A buffer is
         reused only after its encode has finished; with every buffer busy the GPU thread waits here for
         the encoders (back-pressure)."""
-        ring = self.rings.get((key, shape))
+        rk = (key, shape) if depth == 8 else (key, shape, depth)
+        ring = self.rings.get(rk)
         if ring is None:
+            import numpy as np
+            dtype = np.uint16 if depth == 16 else np.uint8
             try:
-                from .ncnn import pinned_empty as alloc
-                alloc((1,))
+                from .ncnn import pinned_empty
+                pinned_empty((1,))
+                alloc = lambda s: pinned_empty(s, dtype)   # noqa: E731
             except Exception:  # noqa: BLE001 - a stand-in net without the engine
-                import numpy as np
-                alloc = lambda s: np.empty(s, np.uint8)   # noqa: E731
+                alloc = lambda s: np.empty(s, dtype)   # noqa: E731
             ring = {"bufs": [alloc(shape) for _ in range(self.nbuf)], "free": queue.Queue()}
             for i in range(self.nbuf):
                 ring["free"].put(i)
-            self.rings[(key, shape)] = ring
+            self.rings[rk] = ring
         return ring, ring["free"].get()
 
-    def png_ring(self, key, h, w):
-        """Ring of page-locked PNG workspaces for h x w result frames (ncnn.PngWorkspace), or None when the GPU encoder
-        does not take such frames."""
-        rk = (key, "png", h, w)
+    def png_ring(self, key, h, w, depth=8):
+        """Ring of page-locked PNG workspaces for h x w result frames at `depth` bits (ncnn.PngWorkspace), or None when the
+        GPU encoder does not take such frames."""
+        rk = (key, "png", h, w) if depth == 8 else (key, "png", h, w, depth)
         if rk not in self.rings:
             from .ncnn import PngWorkspace
             try:
-                ring = {"bufs": [PngWorkspace(h, w) for _ in range(self.nbuf)], "free": queue.Queue()}
+                ring = {"bufs": [PngWorkspace(h, w) if depth == 8 else PngWorkspace(h, w, bit_depth=depth) for _ in range(self.nbuf)],
+                        "free": queue.Queue()}
             except ValueError:
                 ring = None
             else:
@@ -200,14 +216,27 @@ class _Worker:
                     s = net.scale
                     tile = task["tile_size"]
                     ring = None
-                    if self.gpu_png and task["dst"] and str(task["dst"]).lower().endswith(".png") and hasattr(net, "submit_u8_png"):
-                        ring = self.png_ring(key, img.shape[0] * s, img.shape[1] * s)
+                    depth = task.get("bit_depth", 8)
+                    png_submit = "submit_u16_png" if depth == 16 else "submit_u8_png"
+                    if self.gpu_png and task["dst"] and str(task["dst"]).lower().endswith(".png") and hasattr(net, png_submit):
+                        ring = self.png_ring(key, img.shape[0] * s, img.shape[1] * s, depth)
                     if ring is not None:
                         idx = ring["free"].get()
                     else:
-                        ring, idx = self.out_buffer(key, (img.shape[0] * s, img.shape[1] * s, 3))
+                        ring, idx = self.out_buffer(key, (img.shape[0] * s, img.shape[1] * s, 3), depth)
                     try:
-                        if hasattr(ring["bufs"][idx], "file_bytes"):
+                        if depth == 16:
+                            if img.dtype.itemsize != 2:
+                                raise TypeError("a 16-bit task decoded to %s" % img.dtype)
+                            border = task["border"] if tile else 0
+                            if hasattr(ring["bufs"][idx], "file_bytes"):
+                                ticket = net.submit_u16_png(img, workspace=ring["bufs"][idx], tile_size=tile, border=border)
+                            elif hasattr(net, "submit_pix"):         # the u16 frame route (UVA_GPU_PNG=0): zlib on the host's cores
+                                ticket = net.submit_pix(img, img.shape[0], img.shape[1], "bgr48le", out=ring["bufs"][idx], out_fmt="bgr48le",
+                                                        tile_size=tile, border=border, bit_depth=16)
+                            else:                                    # a stand-in net: its submit_u8 takes the array as it is
+                                ticket = net.submit_u8(img, out=ring["bufs"][idx], tile_size=tile, border=border)
+                        elif hasattr(ring["bufs"][idx], "file_bytes"):
                             ticket = net.submit_u8_png(img, workspace=ring["bufs"][idx], tile_size=tile, border=task["border"] if tile else 0)
                         else:
                             ticket = net.submit_u8(img, out=ring["bufs"][idx], tile_size=tile, border=task["border"] if tile else 0)
@@ -234,6 +263,7 @@ class _Worker:
         except Exception:  # noqa: BLE001
             pass
         self.nets.clear()
+        self.u16_nets.clear()
         self.finish(task, e)
 
     # ---- stage 3: encode, delete-after-write, report --------------------------------------------

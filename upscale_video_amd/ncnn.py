@@ -77,14 +77,22 @@ def pinned_empty(shape, dtype=np.uint8):
 class PngWorkspace:
     """Page-locked memory the GPU's PNG encoder writes an h x w frame's deflate blocks into (include/uva.h
     uva_png_workspace_bytes); file_bytes() frames them as a PNG file on the host (zlib / PNG headers, Adler-32, chunk
-    CRC: include/uva.h uva_png_assemble -- no GPU call, the GIL is released)."""
+    CRC: include/uva.h uva_png_assemble -- no GPU call, the GIL is released).  bit_depth=16: a workspace of the 16-bit encoder
+    (uva_png_workspace_bytes16 / uva_png_assemble16: u16 frames, 16-bit RGB files) -- the two kinds differ
+    in size and layout, and the library refuses to frame one kind's blocks as the other's."""
 
-    def __init__(self, h, w):
+    def __init__(self, h, w, bit_depth=8):
         L = _lib.load()
-        n = L.uva_png_workspace_bytes(h, w)
+        if bit_depth not in (8, 16):
+            raise ValueError("bit_depth must be 8 or 16")
+        if bit_depth == 16 and not hasattr(L, "uva_png_workspace_bytes16"):
+            raise _lib.UvaError("this libuva build has no 16-bit PNG encoder: rebuild it")
+        self._size = L.uva_png_workspace_bytes16 if bit_depth == 16 else L.uva_png_workspace_bytes
+        self._assemble = L.uva_png_assemble16 if bit_depth == 16 else L.uva_png_assemble
+        n = self._size(h, w)
         if n == 0:
-            raise ValueError("the GPU PNG encoder does not take %dx%d frames" % (w, h))
-        self.h, self.w = h, w
+            raise ValueError("the GPU PNG encoder does not take %dx%d frames at %d bits" % (w, h, bit_depth))
+        self.h, self.w, self.bit_depth = h, w, bit_depth
         self.buf = pinned_empty((n,), np.uint8)
         self._out = None
 
@@ -92,13 +100,13 @@ class PngWorkspace:
         """-> memoryview of the PNG file image (valid until the next file_bytes() of this workspace)."""
         L = _lib.load()
         n = ctypes.c_size_t(0)
-        L.uva_png_assemble(self.buf.ctypes.data, self.h, self.w, None, 0, ctypes.byref(n))      # size query (fails by design)
+        self._assemble(self.buf.ctypes.data, self.h, self.w, None, 0, ctypes.byref(n))      # size query (fails by design)
         if n.value == 0:
             raise _lib.UvaError(L.uva_last_error().decode(errors="replace"))
         if self._out is None or len(self._out) < n.value:
             self._out = bytearray(n.value + n.value // 8)          # the next frame of the stream is about the same size
         dst = (ctypes.c_ubyte * len(self._out)).from_buffer(self._out)
-        _lib.check(L.uva_png_assemble(self.buf.ctypes.data, self.h, self.w, dst, len(self._out), ctypes.byref(n)))
+        _lib.check(self._assemble(self.buf.ctypes.data, self.h, self.w, dst, len(self._out), ctypes.byref(n)))
         del dst
         return memoryview(self._out)[:n.value]
 
@@ -112,6 +120,20 @@ def png_encode_u8(img_bgr, gpu=0, workspace=None):
     h, w, _ = img.shape
     ws = workspace or PngWorkspace(h, w)
     _lib.check(_lib.load().uva_png_deflate_u8(int(gpu), img.ctypes.data, h, w, w * 3, ws.buf.ctypes.data, ws.buf.nbytes))
+    return bytes(ws.file_bytes())
+
+
+def png_encode_u16(img_bgr, gpu=0, workspace=None):
+    """png_encode_u8 for a u16 BGR frame (include/uva.h uva_png_deflate_u16): -> bytes of a 16-bit RGB PNG file that every
+    reader decodes to exactly the frame."""
+    img = np.ascontiguousarray(img_bgr, dtype=np.uint16)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("frame must be u16 [h][w][3]")
+    h, w, _ = img.shape
+    ws = workspace or PngWorkspace(h, w, bit_depth=16)
+    if ws.bit_depth != 16 or (ws.h, ws.w) != (h, w):
+        raise ValueError("workspace must be a PngWorkspace(%d, %d, bit_depth=16)" % (h, w))
+    _lib.check(_lib.load().uva_png_deflate_u16(int(gpu), img.ctypes.data, h, w, w * 6, ws.buf.ctypes.data, ws.buf.nbytes))
     return bytes(ws.file_bytes())
 
 
@@ -594,8 +616,35 @@ class Net:
             workspace = PngWorkspace(h * s, w * s)
         if (workspace.h, workspace.w) != (h * s, w * s):
             raise ValueError("PNG workspace is for %dx%d frames, the result is %dx%d" % (workspace.w, workspace.h, w * s, h * s))
+        if getattr(workspace, "bit_depth", 8) != 8:
+            raise ValueError("submit_u8_png needs an 8-bit PNG workspace")
         t = self._L.uva_net_submit_u8_png(self._h, img.ctypes.data, h, w, w * 3, workspace.buf.ctypes.data, workspace.buf.nbytes,
                                           int(tile_size), int(border))
+        if t < 0:
+            raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
+        return Ticket(t, img, workspace)
+
+    def submit_u16_png(self, img_bgr, workspace=None, tile_size=0, border=0):
+        """submit_u8_png on 16-bit samples (include/uva.h uva_net_submit_u16_png): a u16 BGR frame in, the
+        u16 result deflated on the GPU as a 16-bit RGB PNG; collect_u8(ticket) returns the PngWorkspace (bit_depth=16).  The
+        16-bit route's nets: 2x / 4x Compact, and the 1x net after enable_u16_1x() at tile_size 0."""
+        img = np.ascontiguousarray(img_bgr, dtype=np.uint16)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("frame must be u16 [h][w][3]")
+        s = self.scale
+        if s <= 0:
+            raise _lib.UvaError("net has no graph: load_param/load_model failed or were not called")
+        h, w, _ = img.shape
+        if workspace is None:
+            workspace = PngWorkspace(h * s, w * s, bit_depth=16)
+        if (workspace.h, workspace.w) != (h * s, w * s):
+            raise ValueError("PNG workspace is for %dx%d frames, the result is %dx%d" % (workspace.w, workspace.h, w * s, h * s))
+        if getattr(workspace, "bit_depth", 8) != 16:
+            raise ValueError("submit_u16_png needs a PngWorkspace(..., bit_depth=16)")
+        if not hasattr(self._L, "uva_net_submit_u16_png"):
+            raise _lib.UvaError("this libuva build has no 16-bit PNG encoder: rebuild it")
+        t = self._L.uva_net_submit_u16_png(self._h, img.ctypes.data, h, w, w * 6, workspace.buf.ctypes.data, workspace.buf.nbytes,
+                                           int(tile_size), int(border))
         if t < 0:
             raise _lib.UvaError(self._L.uva_last_error().decode(errors="replace"))
         return Ticket(t, img, workspace)

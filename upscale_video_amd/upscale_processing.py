@@ -43,6 +43,27 @@ PERSISTENT_WORKERS = True
 TILE_SIZE = 960        # upscale_processing.py:489
 TILE_BORDER = 10       # upscale_processing.py:409-427
 FUSED_DEVICE_PATH = True
+# 16: the PNG route keeps 16 bits from file to file -- process_model and upscale_frames read
+# '<n>.<tag>.png' as u16 BGR (frames extracted with -pix_fmt rgb48be; 8-bit files are widened v * 257), run the nets on u16
+# samples and write 16-bit PNGs, deflated on the GPU; the `-m a` chain's hop between its two nets is then a 16-bit PNG and its
+# 1x net processes whole frames on u16 samples.  Takes the persistent workers; `-m n=K` and `-m r` are refused at 16.
+BIT_DEPTH = 8
+
+
+def _bit_depth(what, model_file=None):
+    """BIT_DEPTH as process_model / upscale_frames / process_denoise see it; raises for what the 16-bit route does not have"""
+    if BIT_DEPTH == 8:
+        return 8
+    if BIT_DEPTH != 16:
+        raise ValueError("BIT_DEPTH must be 8 or 16, not %r" % (BIT_DEPTH,))
+    if what == "denoise":
+        raise ValueError("-m n=K at BIT_DEPTH = 16: there is no 16-bit denoise stage (non-local means runs on 8-bit Lab); "
+                         "run it at BIT_DEPTH = 8")
+    if model_file is not None and "Valar" in str(model_file):
+        raise ValueError("-m r at BIT_DEPTH = 16: the generic executor (%s) does not run on u16 samples; run it at BIT_DEPTH = 8" % model_file)
+    if not PERSISTENT_WORKERS:
+        raise ValueError("BIT_DEPTH = 16 needs PERSISTENT_WORKERS: the reference-shaped route reads and writes 8-bit frames")
+    return 16
 
 
 def get_frames(x):
@@ -250,6 +271,7 @@ def process_model(frames_count, model_path, model_file, scale, model_input, mode
     '<n>.<input_tag>.png'  (reference :302-347).  No collective: frames are independent."""
     frames = range(1, frames_count + 1) if isinstance(frames_count, int) else frames_count
     _check_gpus(gpus)
+    depth = _bit_depth("model", model_file)
     if PERSISTENT_WORKERS:
         tasks = []
         for frame in frames:
@@ -260,6 +282,8 @@ def process_model(frames_count, model_path, model_file, scale, model_input, mode
                                   tile_size=0, border=0, remove=remove,
                                   log_ok=[["info", "Processed Model: " + dst]],
                                   log_error=lambda e: [["error", "Model processing failed"], ["error", e]]))
+                if depth == 16:         # (8: no key, the task is what it was)
+                    tasks[-1]["bit_depth"] = 16
         _run_persistent(gpus, tasks)
         return
     pool = _pool(gpus, workers_used, model_path, model_file, scale, model_input, model_output)
@@ -335,6 +359,7 @@ def process_denoise(frames_count, input_file_tag, denoise, remove=True, gpus=Non
     encode and wait, `workers_per_gpu` of them per GPU.  Returns the number of pool processes like the
     reference (its caller adds it to workers_used, :885)."""
     frames = range(1, frames_count + 1) if isinstance(frames_count, int) else frames_count
+    _bit_depth("denoise")
     gpus = list(gpus) if gpus else [0]
     _check_gpus(gpus)
     nproc = len(gpus) * max(1, int(workers_per_gpu))
@@ -452,6 +477,7 @@ def upscale_frames(frame_batch, start_frame, end_frame, input_file_tag, scale, g
     else:
         frames = range(start_frame, end_frame + 1)
     _check_gpus(gpus)
+    depth = _bit_depth("upscale", model_file)
     if PERSISTENT_WORKERS:
         tasks = []
         for frame in frames:
@@ -464,6 +490,8 @@ def upscale_frames(frame_batch, start_frame, end_frame, input_file_tag, scale, g
                                   tile_size=TILE_SIZE, border=TILE_BORDER, remove=remove,
                                   log_ok=lambda shape, item=_progress_item(frame_batch, frame, end_frame, dst): _tile_items(shape) + [item],
                                   log_error=lambda e: [["error", "Upscale failed"], ["error", e]]))
+                if depth == 16:
+                    tasks[-1]["bit_depth"] = 16
         _run_persistent(gpus, tasks)
         return
     pool = _pool(gpus, workers_used, model_path, model_file, scale, model_input, model_output)
