@@ -56,7 +56,9 @@ extern "C" {
                                15 + launch census: + uva_net_debug_generic_launches (additive: a host-side test hook)
                                15 + 16-bit PNGs: + uva_png_workspace_bytes16, uva_png_assemble16, uva_png_deflate_u16,
                                    uva_debug_png_deflate_host16, uva_png_decode_bgr16, uva_net_submit_u16_png (additive: every 8-bit PNG
-                                   entry keeps its signature and its bytes) */
+                                   entry keeps its signature and its bytes)
+                               15 + 16-bit denoise: + uva_denoise_u16, uva_denoise_u16_device, uva_debug_denoise16_stage (additive: the
+                                   8-bit stage keeps its kernels and its bytes) */
 
 typedef struct uva_net uva_net;
 
@@ -391,6 +393,23 @@ int uva_denoise_synchronize(int device);
 /* Test hook: one stage of the above on dense host arrays.  stage 0: BGR -> Lab [h][w][3]; 1: Lab -> BGR;
  * 2: non-local means on a 1-channel image; 3: on a 2-channel image (strength = h). */
 int uva_debug_denoise_stage(int device, int stage, const uint8_t* in, int h, int w, float strength, uint8_t* out);
+
+/* `-m n=K` at --bit-depth 16 (csrc/uva_denoise16.hip.h): the same stage on u16 samples, for frames of
+ * more than 8 bits.  in / out: host u16 HWC BGR [h][w][3] (bgr48le), strides in BYTES.  BGR16 -> Lab16 (L * 65535 / 100,
+ * (a + 128) * 257, (b + 128) * 257: the 8-bit planes' scales x 257; linear light, the CIE formulas in fixed point), non-local
+ * means on L16 with h_luma and on (a16, b16) with h_color (template 5, search 9; squared differences `>> 8` per sample, a weight
+ * table sixteen times finer than the 8-bit one holding the same function of the mean squared patch difference, so a strength
+ * means what it means at 8 bits; 64-bit accumulators), Lab16 -> BGR16.  Strengths in (0, 64].  Integer arithmetic throughout,
+ * bit-exact against its numpy definition (tests/nlm16_ref.py); BGR16 -> Lab16 -> BGR16 alone moves a sample by at most 12 codes
+ * of 65535 (the 8-bit stage's Lab hop: up to 5 levels of 255 = 1285 codes). */
+int uva_denoise_u16(int device, const uint16_t* in, int h, int w, size_t in_stride, uint16_t* out, size_t out_stride,
+                    float h_luma, float h_color);
+/* The same on a frame in HBM, asynchronous on the denoise stage's stream (the 8-bit stage's: uva_denoise_synchronize waits for
+ * both); `after` / `before` as in uva_denoise_u8_device.  Pointers and strides 2-byte aligned. */
+int uva_denoise_u16_device(int device, const void* d_in, int h, int w, size_t in_stride, void* d_out, size_t out_stride,
+                           float h_luma, float h_color, uva_net* after, uva_net* before);
+/* Test hook: uva_debug_denoise_stage's stages 0 - 3 on dense u16 arrays. */
+int uva_debug_denoise16_stage(int device, int stage, const uint16_t* in, int h, int w, float strength, uint16_t* out);
 
 /* ---- introspection used by the parity tests and bench.py ------------------------------ */
 

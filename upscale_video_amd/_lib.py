@@ -36,6 +36,8 @@ SYMBOLS = [
 # Net.submit_u16_png, _imageio.imread(bit_depth=16)) asks with hasattr and says what is missing.
 OPTIONAL_SYMBOLS = ["uva_png_workspace_bytes16", "uva_png_assemble16", "uva_png_deflate_u16", "uva_debug_png_deflate_host16",
                     "uva_png_decode_bgr16", "uva_net_submit_u16_png"]
+# 15 + 16-bit denoise (additive and optional in the same way: rawvideo's 16-bit DenoiseStage and Net.denoise_u16_device ask)
+OPTIONAL_SYMBOLS += ["uva_denoise_u16", "uva_denoise_u16_device", "uva_debug_denoise16_stage"]
 SYMBOLS += OPTIONAL_SYMBOLS
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -137,6 +139,9 @@ def load():
     decl("uva_denoise_u8_device", [c_i, c_p, c_i, c_i, c_sz, c_p, c_sz, ctypes.c_float, ctypes.c_float, c_p, c_p])
     decl("uva_denoise_synchronize", [c_i])
     decl("uva_debug_denoise_stage", [c_i, c_i, c_p, c_i, c_i, ctypes.c_float, c_p])
+    decl("uva_denoise_u16", [c_i, c_p, c_i, c_i, c_sz, c_p, c_sz, ctypes.c_float, ctypes.c_float])
+    decl("uva_denoise_u16_device", [c_i, c_p, c_i, c_i, c_sz, c_p, c_sz, ctypes.c_float, ctypes.c_float, c_p, c_p])
+    decl("uva_debug_denoise16_stage", [c_i, c_i, c_p, c_i, c_i, ctypes.c_float, c_p])
     decl("uva_destroy_gpu_instance", [], "void")
     decl("uva_net_destroy", [c_p], "void")
     decl("uva_net_set_device", [c_p, c_i])

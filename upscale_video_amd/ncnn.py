@@ -675,6 +675,15 @@ class Net:
                                                  out_stride or w * 3, float(strength), float(strength),
                                                  after._h if after is not None else None, self._h))
 
+    def denoise_u16_device(self, d_in, h, w, d_out, strength, after=None, in_stride=None, out_stride=None):
+        """`-m n=K` at 16 bits on a u16 BGR frame in HBM (include/uva.h uva_denoise_u16_device), queued
+        like denoise_u8_device: `after` (a net, or None) comes first, this net's next work waits for the frame.  Strides in bytes."""
+        if not hasattr(self._L, "uva_denoise_u16_device"):
+            raise _lib.UvaError("this libuva build has no 16-bit denoise stage: rebuild it")
+        _lib.check(self._L.uva_denoise_u16_device(self.device_index, ctypes.c_void_p(d_in), h, w, in_stride or w * 6, ctypes.c_void_p(d_out),
+                                                  out_stride or w * 6, float(strength), float(strength),
+                                                  after._h if after is not None else None, self._h))
+
     def wait_for(self, producer):
         """Device-side ordering: work queued on `producer` so far finishes before this net's next work."""
         _lib.check(self._L.uva_net_wait_for(self._h, producer._h))

@@ -19,7 +19,10 @@ p010le, yuv420p10le, and the 4:2:2 formats of capture and mezzanine material yuv
 
 --bit-depth 16 runs the 2x / 4x net on 16-bit samples so that 10-bit frames (p010le, yuv420p10le, yuv422p10le) keep their depth
 (DESIGN.md section 7.4).  -m a goes with it: the 1x net then runs on 16-bit samples too and hands u16 BGR (bgr48le) frames to the
-2x / 4x net, so the chain has no 8-bit hop either; -m n=K and -m r run at 8 bits only.  The pair wants
+2x / 4x net, so the chain has no 8-bit hop either.  -m n=K goes with it as well: the film-grain denoise
+then runs on 16-bit Lab planes (uva_denoise_u16: the 8-bit stage's non-local means with 16-bit samples, a sixteen times finer
+weight table and 64-bit sums, K meaning what it means at 8 bits) and hands bgr48le on, instead of
+sending 10-bit frames through 256 levels and an 8-bit Lab round trip; -m r runs at 8 bits only.  Either option wants
 a format of more than 8 bits on at least one end (p010le, yuv420p10le, yuv422p10le, bgr48le); with 8-bit frames in and out it is
 refused, as it always was.
 
@@ -223,7 +226,9 @@ class DenoiseStage:
     """`-m n=K` (apply_denoise, upscale/upscale_processing.py:350-354) as a stage of a lane: cv2.fastNlMeansDenoisingColored's
     arithmetic on the lane's GPU (include/uva.h uva_denoise_u8), host frame in, host frame out like the nets' stages -- the call
     takes about a millisecond per 1080p frame and releases the interpreter lock, the nets behind it keep their frames in flight.
-    Frames of another format than bgr24 on either end are converted on the same GPU (include/uva.h uva_pix_convert)."""
+    Frames of another format than bgr24 on either end are converted on the same GPU (include/uva.h uva_pix_convert).
+    pix.bit_depth 16: the stage's native format is bgr48le and the call is uva_denoise_u16 -- in_fmt ->
+    bgr48le with convert_pix(bit_depth=16), the 16-bit non-local means, bgr48le handed on mid-chain or converted to out_fmt."""
 
     class _Scale1:
         scale = 1
@@ -232,9 +237,10 @@ class DenoiseStage:
         self.gpu, self.strength = gpu, float(strength)
         self.net = self._Scale1()
         self.in_fmt, self.out_fmt, self.pix = in_fmt, out_fmt, pix
+        self.native = "bgr48le" if pix.bit_depth == 16 else "bgr24"
         self.outs = [ncnn.pix_empty(out_fmt, h, w, alloc) for _ in range(2 * PIPE_DEPTH + 2)]
-        self._bgr_in = alloc((h, w, 3)) if in_fmt != "bgr24" else None      # (used and done with inside submit)
-        self._bgr_out = alloc((h, w, 3)) if out_fmt != "bgr24" else None
+        self._bgr_in = ncnn.pix_empty(self.native, h, w, alloc) if in_fmt != self.native else None      # (used and done with inside submit)
+        self._bgr_out = ncnn.pix_empty(self.native, h, w, alloc) if out_fmt != self.native else None
         self.h, self.w = h, w
         self.n = 0
         self.inflight = []
@@ -242,20 +248,31 @@ class DenoiseStage:
     def full(self):
         return len(self.inflight) >= 1
 
-    def submit(self, frame):
+    def denoise(self, frame, dst):
+        """the stage's arithmetic on one native frame (bgr24, or bgr48le at 16 bits), host to host"""
         from . import _lib
+        L = _lib.load()
+        if self.native == "bgr48le" and not hasattr(L, "uva_denoise_u16"):
+            raise _lib.UvaError("this libuva build has no 16-bit denoise stage: rebuild it")
+        fn = L.uva_denoise_u16 if self.native == "bgr48le" else L.uva_denoise_u8
+        _lib.check(fn(self.gpu, frame.ctypes.data, self.h, self.w, frame.strides[0], dst.ctypes.data, dst.strides[0],
+                      self.strength, self.strength))
+
+    def submit(self, frame):
         out = self.outs[self.n % len(self.outs)]
         self.n += 1
         h, w = self.h, self.w
         pix = self.pix
-        if self.in_fmt != "bgr24":
-            frame = ncnn.convert_pix(frame, h, w, self.in_fmt, "bgr24", pix.colour, pix.color_range, out=self._bgr_in, gpu=self.gpu,
-                                     **pix.chroma_kw())
-        dst = out if self.out_fmt == "bgr24" else self._bgr_out
-        _lib.check(_lib.load().uva_denoise_u8(self.gpu, frame.ctypes.data, h, w, frame.strides[0], dst.ctypes.data, dst.strides[0],
-                                              self.strength, self.strength))
-        if self.out_fmt != "bgr24":
-            ncnn.convert_pix(dst, h, w, "bgr24", self.out_fmt, pix.colour, pix.color_range, out=out, gpu=self.gpu, **pix.chroma_kw())
+        if self.in_fmt != self.native:
+            frame = ncnn.convert_pix(frame, h, w, self.in_fmt, self.native, pix.colour, pix.color_range, out=self._bgr_in, gpu=self.gpu,
+                                     **pix.depth_kw(), **pix.chroma_kw())
+        elif self.native == "bgr48le":
+            frame = np.asarray(frame).reshape(-1).view(np.uint16).reshape(h, w, 3)      # (the reader's flat bytes)
+        dst = out if self.out_fmt == self.native else self._bgr_out
+        self.denoise(frame, dst)
+        if self.out_fmt != self.native:
+            ncnn.convert_pix(dst, h, w, self.native, self.out_fmt, pix.colour, pix.color_range, out=out, gpu=self.gpu,
+                             **pix.depth_kw(), **pix.chroma_kw())
         self.inflight.append(out)
 
     def collect(self):
@@ -756,7 +773,9 @@ def main(argv=None):
     ap.add_argument("-H", "--height", type=int, required=True)
     ap.add_argument("-s", "--scale", type=int, default=2, choices=[1, 2, 4])
     ap.add_argument("-m", "--models", default="", help="upscale_video.py -m: a = 1x HurrDeblur pass first, n=K = film-grain denoise "
-                                                       "(K 1..30) before everything, r = the x_Valar_v1 model (scale 4, needs its .bin)")
+                                                       "(K 1..30) before everything, on 16-bit samples with --bit-depth 16 (K means "
+                                                       "the same at both depths), r = the x_Valar_v1 model (scale 4, needs its .bin, "
+                                                       "8 bits only)")
     ap.add_argument("-g", "--gpu", default="0",
                     help="HIP ordinals, one worker per entry, e.g. 0,1,2,3 or 0,0,1 (upscale_video.py -g; default 0)")
     ap.add_argument("--tile", type=int, default=TILE_SIZE, help="reference tile size of the final pass (960); 0 = whole frame")
@@ -778,8 +797,9 @@ def main(argv=None):
     ap.add_argument("--color-range", default="tv", choices=list(ncnn.COLOR_RANGES), help="tv = limited (default), pc = full")
     ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
                     help="16: the 2x / 4x net runs on 16-bit samples, so 10-bit frames (p010le, yuv420p10le, yuv422p10le) keep their "
-                         "depth (default 8); of the -m options it takes -m a, whose 1x net then runs on 16-bit samples as well "
-                         "(with a 10- or 16-bit pixel format on at least one end)")
+                         "depth (default 8); of the -m options it takes -m a, whose 1x net then runs on 16-bit samples as well, "
+                         "and -m n=K, whose non-local means then runs on 16-bit Lab planes (both with a 10- or 16-bit pixel format "
+                         "on at least one end); -m r runs at 8 bits only")
     ap.add_argument("--model-path", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models"))
     ap.add_argument("--chroma-filter", default="replicate", choices=list(ncnn.CHROMA_FILTERS),
                     help="chroma resampling in the Y'CbCr conversions (4:2:2 formats: along the row alone; DESIGN.md section 7.7): "
@@ -851,14 +871,22 @@ def main(argv=None):
                 ap.error("-m n=K: K must be between 1 and 30")
         elif m not in ("a", "r"):
             ap.error("unknown model option %r (a, n=K, r)" % m)
-    if a.bit_depth == 16 and any(m != "a" for m in models):
-        ap.error("--bit-depth 16 takes the 2x and 4x Compact nets only: -m n=K and -m r run at 8 bits (-m %s)" % a.models)
-    if a.bit_depth == 16 and models and all(ncnn.pix_depth(f) == 8 for f in (a.in_pix_fmt, a.out_pix_fmt)):
+    deep = ", ".join(f for f in ncnn.PIX_FORMATS_ALL if ncnn.pix_depth(f) > 8)
+    shallow = all(ncnn.pix_depth(f) == 8 for f in (a.in_pix_fmt, a.out_pix_fmt))
+    if a.bit_depth == 16 and models and shallow and any(m != "a" for m in models):
+        # (8-bit frames in and out, the default bgr24 among them: refused as before the 16-bit denoise stage existed, in the words
+        # tests/test_rawvideo_bitdepth16_chain.py and tests/test_pixfmt16.py pin)
+        ap.error("--bit-depth 16 takes the 2x and 4x Compact nets only: -m n=K and -m r run at 8 bits (-m %s with 8-bit frames, %s "
+                 "in and %s out; with a 10- or 16-bit format -- %s -- on at least one end -m n=K and -m a run on 16-bit samples, "
+                 "-m r never)" % (a.models, a.in_pix_fmt, a.out_pix_fmt, deep))
+    if a.bit_depth == 16 and "r" in models:
+        ap.error("--bit-depth 16 takes the Compact nets, -m a and -m n=K: -m r has no 16-bit weights to run on and runs at 8 bits "
+                 "(-m %s)" % a.models)
+    if a.bit_depth == 16 and models and shallow:
         # (the plain pair, with the default bgr24 at both ends, is held to a refusal by a pinned test, tests/test_pixfmt16.py;
         # what the 16-bit chain is for -- frames of more than 8 bits -- names such a format on at least one end)
-        ap.error("--bit-depth 16 -m a is for frames of more than 8 bits: name a 10- or 16-bit format (%s) with --in-pix-fmt or "
-                 "--out-pix-fmt, or run the chain at 8 bits (%s in, %s out)"
-                 % (", ".join(f for f in ncnn.PIX_FORMATS_ALL if ncnn.pix_depth(f) > 8), a.in_pix_fmt, a.out_pix_fmt))
+        ap.error("--bit-depth 16 -m %s is for frames of more than 8 bits: name a 10- or 16-bit format (%s) with --in-pix-fmt or "
+                 "--out-pix-fmt, or run the chain at 8 bits (%s in, %s out)" % (a.models, deep, a.in_pix_fmt, a.out_pix_fmt))
     if out_size is not None and a.scale == 1 and denoise is not None and "a" not in models:
         ap.error("--out-size / --out-scale: the resampler sits behind a net, and -s 1 -m n=K ends in the denoise stage: add -m a or "
                  "-s 2|4")
