@@ -281,6 +281,56 @@ int uva_net_reset_reference(uva_net* net);
 /* Frames that went through the comparison's route since uva_net_set_skip_repeats, and how many of them were skipped. */
 int uva_net_skip_stats(uva_net* net, long long* submitted, long long* skipped);
 
+/* ---- crop detection and cropped input frames (csrc/uva_crop.hip, csrc/uva_crop_host.cpp) ------
+ * The reference looks for black bars first: get_crop_detect (upscale/upscale_processing.py:137-181) runs ffmpeg's cropdetect at
+ * 100 places of the film and extract_frames (:227-230) applies the most frequent crop=W:H:X:Y.  These entries are that filter's
+ * rule restated (its definition for this project: tests/cropdetect_ref.py; parity with ffmpeg itself is unpinned) and the means
+ * to apply the result in front of a net.  Samples are code values as the input conversion reads them (bytes; word >> 6 for
+ * p010le; word & 1023 for yuv420p10le / yuv422p10le; whole words for bgr48le), of depth 8, 10 or 16.  A LINE is a row or a column
+ * of the luma plane, or of all three components of a packed BGR frame (n = w or h samples; 3w or 3h for bgr24 / bgr48le). */
+/* The exact sums of every line of a dense h x w frame of fmt (upscale/upscale_processing.py:137-181: the detector's per-frame
+ * pass), computed on HIP device `device`: rows[h], cols[w].  Host to host, synchronous.  Null pointers, an unknown format and a
+ * size below 1 are refused with uva_last_error set. */
+int uva_crop_sums(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols);
+/* The same (upscale/upscale_processing.py:137-181) with the frame resident in `device`'s HBM at a 16-byte aligned address and
+ * complete; rows / cols are host memory.  Synchronous as well. */
+int uva_crop_sums_device(int device, const void* d_frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols);
+/* Test hook: uva_crop_sums (upscale/upscale_processing.py:137-181) on a grid of at most max_groups workgroups (0: the kernel's own
+ * bound), so that a small frame exercises the kernel's grid-stride walk. */
+int uva_debug_crop_sums(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols,
+                        int max_groups);
+/* Host only, no GPU needed: cropdetect's brightness test (upscale/upscale_processing.py:137-181) on a frame's line sums.  A line
+ * with sum S over n samples is bright iff floor(S / n) > limit << (depth - 8); limit is on the 8-bit scale, 0 ... 255 (ffmpeg's
+ * default: 24), anything else is refused.  bounds = {first bright row, last bright row, first bright column, last bright
+ * column}, -1 where there is none. */
+int uva_crop_bounds(const unsigned long long* rows, const unsigned long long* cols, int fmt, int h, int w, int limit, int bounds[4]);
+/* Host only: cropdetect's rectangle (upscale/upscale_processing.py:137-181, the crop=W:H:X:Y it prints) from a running state
+ * {x1, y1, x2, y2} -- initially {w - 1, h - 1, 0, 0}; every frame lowers x1 / y1 to its first bright column / row and raises
+ * x2 / y2 to its last -- and `round` (<= 1 means 16, an odd value is doubled): x = (x1 + 1) & ~1, cw = x2 - x + 1, k = cw % round,
+ * cw -= k, x += (k / 2 + 1) & ~1, and the same for y and ch.  rect = {W, H, X, Y}, all even and inside the frame.  Returns
+ * non-zero (uva_last_error set) when there is no rectangle: cw or ch not positive at some point. */
+int uva_crop_rect(const int state[4], int round, int rect[4]);
+/* Host only: is the window h x w at (x, y) of a src_h x src_w frame of fmt one that uva_pix_window and the submit entries take
+ * (upscale/upscale_processing.py:227-230 applies any crop ffmpeg printed; here the formats' chroma grids decide)?  Refused,
+ * never rounded: a window that leaves the frame, x or w odd for a Y'CbCr format, y or h odd for a 4:2:0 format.  bgr24 / bgr48le
+ * take any window. */
+int uva_pix_window_check(int fmt, int src_h, int src_w, int x, int y, int h, int w);
+/* The crop itself (extract_frames' `-vf crop=...`, upscale/upscale_processing.py:227-230): out <- the dense h x w frame of fmt cut
+ * from the dense src_h x src_w frame `in` at (x, y), every plane at its own resolution, on HIP device `device`.  Host to host,
+ * synchronous.  For lanes whose first stage is no net (`-m n=K`, `-s 1` without a net). */
+int uva_pix_window(int device, const void* in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* out);
+/* The same (upscale/upscale_processing.py:227-230) between frames in `device`'s HBM, both complete; d_out at a 16-byte aligned
+ * address.  Synchronous. */
+int uva_pix_window_device(int device, const void* d_in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* d_out);
+/* The crop in front of a net (upscale/upscale_processing.py:227-230: no net ever sees a black bar).  While a window is set, `in` of
+ * every uva_net_submit_pix, uva_net_submit_pix16 and uva_net_submit_pix_sized call is a dense src_h x src_w frame of in_fmt and
+ * the call's own h x w is the window at (x, y) of it: only the window's rows are uploaded -- one copy per plane, and for a window
+ * narrower than the frame a small kernel on the upload stream that compacts the columns -- and everything behind the upload, `out`
+ * included, is what it is for a dense h x w frame.  A window uva_pix_window_check refuses makes the submit call fail.  All zeros
+ * switch it off (the default).  Setting it forgets the kept frame of uva_net_set_skip_repeats and zeroes its counters: the
+ * comparison is between uploaded windows.  Host only: works with no GPU present. */
+int uva_net_set_input_window(uva_net* net, int src_h, int src_w, int x, int y);
+
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 
 /* cv2.imwrite(frame.png) of the result frame (upscale_processing.py:288, :519), with the deflate work done on the GPU:

@@ -38,6 +38,10 @@ OPTIONAL_SYMBOLS = ["uva_png_workspace_bytes16", "uva_png_assemble16", "uva_png_
                     "uva_png_decode_bgr16", "uva_net_submit_u16_png"]
 # 15 + 16-bit denoise (additive and optional in the same way: rawvideo's 16-bit DenoiseStage and Net.denoise_u16_device ask)
 OPTIONAL_SYMBOLS += ["uva_denoise_u16", "uva_denoise_u16_device", "uva_debug_denoise16_stage"]
+# 15 + crop detection and the input window (additive and optional in the same way: ncnn.crop_sums, ncnn.pix_window,
+# Net.set_input_window and rawvideo's --crop / --cropdetect ask)
+OPTIONAL_SYMBOLS += ["uva_crop_sums", "uva_crop_sums_device", "uva_debug_crop_sums", "uva_crop_bounds", "uva_crop_rect",
+                     "uva_pix_window_check", "uva_pix_window", "uva_pix_window_device", "uva_net_set_input_window"]
 SYMBOLS += OPTIONAL_SYMBOLS
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -116,6 +120,15 @@ def load():
     decl("uva_net_reset_reference", [c_p])
     decl("uva_net_skip_stats", [c_p, pll, pll])
     decl("uva_net_enable_u16_1x", [c_p, c_i])
+    decl("uva_crop_sums", [c_i, c_p, c_i, c_i, c_i, c_p, c_p])
+    decl("uva_crop_sums_device", [c_i, c_p, c_i, c_i, c_i, c_p, c_p])
+    decl("uva_debug_crop_sums", [c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i])
+    decl("uva_crop_bounds", [c_p, c_p, c_i, c_i, c_i, c_i, pi])
+    decl("uva_crop_rect", [pi, c_i, pi])
+    decl("uva_pix_window_check", [c_i, c_i, c_i, c_i, c_i, c_i, c_i])
+    decl("uva_pix_window", [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p])
+    decl("uva_pix_window_device", [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p])
+    decl("uva_net_set_input_window", [c_p, c_i, c_i, c_i, c_i])
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

@@ -14,6 +14,7 @@
 #include "uva_pixfmt.h"
 #include "uva_plan.h"
 #include "uva_repeat.h"
+#include "uva_crop.h"
 #include "uva_resize.h"
 #include "uva_png.hip.h"
 #include "uva_wino.h"
@@ -176,7 +177,9 @@ struct uva_net {
         uint8_t* d_png = nullptr;        // the PNG encoder's blocks: [meta][slots], then [the blocks packed end to end]
         uint8_t *d_pin = nullptr, *d_pout = nullptr;   // uva_net_submit_pix: the packed frames (d_in / d_out hold their BGR)
         uint8_t* d_rs = nullptr;         // uva_net_submit_pix_sized: the net's result resampled to the output size (BGR)
+        uint8_t* d_win = nullptr;        // uva_net_set_input_window, a window narrower than the frame: its rows at full width
         size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0, d_png_cap = 0, d_pin_cap = 0, d_pout_cap = 0, d_rs_cap = 0;
+        size_t d_win_cap = 0;
         uint8_t* png_ws = nullptr;       // PNG submit: the caller's workspace, how many packed bytes went there with the
         size_t png_sent = 0;             // frame's download, and the frame size (collect fetches the rest, if any)
         int png_h = 0, png_w = 0, png_bits = 8;   // (png_bits 16: the 16-bit encoder's workspace layout)
@@ -214,6 +217,12 @@ struct uva_net {
         long long submitted = 0, skipped = 0;
     };
     Repeat rep;
+    // uva_net_set_input_window: the frames the pixel-format submit entries are given are dense
+    // src_h x src_w frames of which the call's h x w at (x, y) is uploaded; src_h == 0: off
+    struct Window {
+        int src_h = 0, src_w = 0, x = 0, y = 0;
+    };
+    Window win;
     void release_repeat()                // the device is current, nothing of this net is running
     {
         if (rep.d_in) (void)hipFree(rep.d_in);
@@ -273,6 +282,7 @@ struct uva_net {
             if (ps.d_pin) (void)hipFree(ps.d_pin);
             if (ps.d_pout) (void)hipFree(ps.d_pout);
             if (ps.d_rs) (void)hipFree(ps.d_rs);
+            if (ps.d_win) (void)hipFree(ps.d_win);
             if (ps.h_in) (void)hipHostFree(ps.h_in);
             if (ps.h_out) (void)hipHostFree(ps.h_out);
             if (ps.ev_h2d) (void)hipEventDestroy(ps.ev_h2d);
@@ -1858,6 +1868,8 @@ struct PixCtx {                          // per device: the conversions' own str
     uint8_t *d_in = nullptr, *d_mid = nullptr, *d_out = nullptr;
     size_t in_cap = 0, mid_cap = 0, out_cap = 0;
     FrameDiffStats* d_stats = nullptr;   // uva_frame_diff's record
+    unsigned long long* d_sums = nullptr;    // uva_crop_sums' line sums: rows, then columns
+    size_t sums_cap = 0;
 };
 std::mutex g_pix_mu;
 PixCtx g_pix[16];
@@ -1873,6 +1885,7 @@ void pix_release_all()
         for (uint8_t* p : {c.d_in, c.d_mid, c.d_out})
             if (p) (void)hipFree(p);
         if (c.d_stats) (void)hipFree(c.d_stats);
+        if (c.d_sums) (void)hipFree(c.d_sums);
         (void)hipStreamDestroy(c.stream);
         c = PixCtx();
     }
@@ -2820,10 +2833,21 @@ namespace {
 // is not computed -- the kept frame's result is downloaded for it
 long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out, size_t out_stride,
                     int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
-                    int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0, bool may_skip = false)
+                    int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0, bool may_skip = false,
+                    bool windowed = false)
 {
     const int png_bits = u16 ? 16 : 8;     // (png_ws: the encoder that matches the net's frames)
     if (check_dims(n, h, w)) return -1;
+    // windowed (the pixel-format entries, uva_net_set_input_window on): `in` is a dense src_h x src_w frame of in_fmt and h x w the
+    // window at (x, y) of it.  Only the upload below knows: it leaves the dense window frame where a whole frame's upload would.
+    const bool win = windowed && n->win.src_h > 0;
+    WindowPlane wpl[3];
+    int wn = 0;
+    if (win) {
+        const uva_net::Window& wd = n->win;
+        if (const char* e = crop_window_error(in_fmt, wd.src_h, wd.src_w, wd.x, wd.y, h, w)) { fail(e); return -1; }
+        wn = crop_window_planes(in_fmt, wd.src_h, wd.src_w, wd.x, wd.y, h, w, wpl);
+    }
     if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
     if (png_ws && !is_pinned_host(png_ws)) { fail("PNG workspace must be page-locked host memory (uva_host_alloc)"); return -1; }
     if (ensure_device(n)) return -1;
@@ -2839,6 +2863,16 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     const size_t in_bytes = in_row * h, out_bytes = out_row * (size_t)h * s;
     const int native = u16 ? PIX_BGR48LE : PIX_BGR24;
     const bool pin = in_fmt != native, pout = out_fmt != native;
+    if (win && !pin) {
+        // the net's own BGR layout: the window is the frame at an offset with the source's row stride, which the upload takes as it is
+        in += (size_t)wpl[0].row0 * wpl[0].src_row + wpl[0].xbytes;
+        in_stride = wpl[0].src_row;
+    }
+    // a window over whole rows (a letterbox) is a contiguous row range of every plane; a narrower one goes up at full width and
+    // pix_window_kernel compacts its columns
+    const bool win_rows = win && pin, win_cols = win_rows && wpl[0].dst_row != wpl[0].src_row;
+    size_t wstage[3] = {0, 0, 0};
+    const size_t wstage_bytes = win_cols ? pix_window_staging(wpl, wn, wstage) : 0;
     const size_t pin_bytes = pix_frame_bytes(in_fmt, h, w), pout_bytes = pix_frame_bytes(out_fmt, res_h, res_w);
     if (pout_bytes > (size_t)INT_MAX) { fail("result frame of 2 GB or more"); return -1; }
     uva_net::PipeSlot* free_slot = nullptr;
@@ -2858,6 +2892,7 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     if (grow_dev(&ps.d_in, &ps.d_in_cap, in_bytes) || grow_dev(&ps.d_out, &ps.d_out_cap, out_bytes)) return -1;
     if ((pin && grow_dev(&ps.d_pin, &ps.d_pin_cap, pin_bytes)) || (pout && grow_dev(&ps.d_pout, &ps.d_pout_cap, pout_bytes))) return -1;
     if (rs && grow_dev(&ps.d_rs, &ps.d_rs_cap, res_bytes)) return -1;
+    if (win_cols && grow_dev(&ps.d_win, &ps.d_win_cap, wstage_bytes)) return -1;
     const uint8_t* d_res = rs ? ps.d_rs : ps.d_out;                        // the BGR frame that leaves
     std::string rs_err;
     if (png_ws) {
@@ -2872,16 +2907,33 @@ long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_strid
     size_t src_stride = in_stride;
     const size_t h2d_row = pin ? pin_bytes : in_row;
     const int h2d_rows = pin ? 1 : h;
-    if (!is_pinned_host(in)) {
-        if (grow_host(&ps.h_in, &ps.h_in_cap, pin ? pin_bytes : in_bytes)) return -1;
-        if (pin) std::memcpy(ps.h_in, in, pin_bytes);
-        else
-            for (int y = 0; y < h; ++y) std::memcpy(ps.h_in + y * in_row, in + y * in_stride, in_row);
-        src = ps.h_in; src_stride = h2d_row;
+    if (win_rows) {
+        // one copy per plane of the plane's row range: into the packed frame where the rows are whole, into the staging otherwise
+        uint8_t* d_up = win_cols ? ps.d_win : ps.d_pin;
+        const bool pinned = is_pinned_host(in);
+        if (!pinned && grow_host(&ps.h_in, &ps.h_in_cap, win_cols ? wstage_bytes : pin_bytes)) return -1;
+        for (int p = 0; p < wn; ++p) {
+            const size_t at = win_cols ? wstage[p] : wpl[p].dst_off, nb = wpl[p].src_row * (size_t)wpl[p].rows;
+            const uint8_t* from = in + wpl[p].src_off + (size_t)wpl[p].row0 * wpl[p].src_row;
+            if (!pinned) {
+                std::memcpy(ps.h_in + at, from, nb);
+                from = ps.h_in + at;
+            }
+            if (tryhip(hipMemcpyAsync(d_up + at, from, nb, hipMemcpyHostToDevice, n->s_h2d), "H2D")) return -1;
+        }
+        if (win_cols && tryhip(launch_pix_window(n->s_h2d, ps.d_win, wstage, ps.d_pin, wpl, wn, crop_sample(in_fmt).bytes), "pix_window")) return -1;
+    } else {
+        if (!is_pinned_host(in)) {
+            if (grow_host(&ps.h_in, &ps.h_in_cap, pin ? pin_bytes : in_bytes)) return -1;
+            if (pin) std::memcpy(ps.h_in, in, pin_bytes);
+            else
+                for (int y = 0; y < h; ++y) std::memcpy(ps.h_in + y * in_row, in + y * in_stride, in_row);
+            src = ps.h_in; src_stride = h2d_row;
+        }
+        if (tryhip(hipMemcpy2DAsync(pin ? ps.d_pin : ps.d_in, h2d_row, src, pin ? h2d_row : src_stride, h2d_row, h2d_rows,
+                                    hipMemcpyHostToDevice, n->s_h2d), "H2D")) return -1;
     }
-    if (tryhip(hipMemcpy2DAsync(pin ? ps.d_pin : ps.d_in, h2d_row, src, pin ? h2d_row : src_stride, h2d_row, h2d_rows,
-                                hipMemcpyHostToDevice, n->s_h2d), "H2D") ||
-        tryhip(hipEventRecord(ps.ev_h2d, n->s_h2d), "hipEventRecord") ||
+    if (tryhip(hipEventRecord(ps.ev_h2d, n->s_h2d), "hipEventRecord") ||
         tryhip(hipStreamWaitEvent(n->stream, ps.ev_h2d, 0), "hipStreamWaitEvent")) return -1;
     // what comes down: the BGR rows of d_out, or the packed frame d_pout -- as "rows" of one byte, so that a band is a byte
     // range (collect copies it with one memcpy)
@@ -3091,7 +3143,7 @@ long long uva_net_submit_pix(uva_net* n, const void* in, int in_fmt, int h, int 
     const int s = uva_net_scale(n);
     if (s <= 0) { fail("net has no graph"); return -1; }
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3, (uint8_t*)out, (size_t)w * s * 3, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, false, 0, 0, 0, true);
+                     in_fmt, out_fmt, colour, false, 0, 0, 0, true, true);
 }
 
 long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
@@ -3103,7 +3155,7 @@ long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, in
     if (ensure_device(n) || check_u16_net(n)) return -1;
     const int s = uva_net_scale(n);
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 6, (uint8_t*)out, (size_t)w * s * 6, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, true, 0, 0, 0, true);
+                     in_fmt, out_fmt, colour, true, 0, 0, 0, true, true);
 }
 
 int uva_net_enable_u16_1x(uva_net* n, int on)
@@ -3242,7 +3294,7 @@ long long uva_net_submit_pix_sized(uva_net* n, const void* in, int in_fmt, int h
     if (const char* e = resize_axis_error(w * s, ow, filter)) { fail(e); return -1; }
     const size_t bps = bits / 8;
     return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3 * bps, (uint8_t*)out, (size_t)ow * 3 * bps, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, bits == 16, oh, ow, filter, true);
+                     in_fmt, out_fmt, colour, bits == 16, oh, ow, filter, true, true);
 }
 
 // ---- repeated frames (csrc/uva_repeat.hip) ---------------------------------------------------------
@@ -3320,6 +3372,150 @@ int uva_net_skip_stats(uva_net* n, long long* submitted, long long* skipped)
     if (!n) return fail("null net");
     if (submitted) *submitted = n->rep.submitted;
     if (skipped) *skipped = n->rep.skipped;
+    return 0;
+}
+
+// ---- crop detection and the input window (csrc/uva_crop.hip, csrc/uva_crop_host.cpp) ------------------
+namespace {
+int crop_sums_check(const void* frame, int fmt, int h, int w, const unsigned long long* rows, const unsigned long long* cols)
+{
+    if (!frame || !rows || !cols) return fail("null frame pointer");
+    if (!crop_sample(fmt).bytes || !pix_frame_bytes(fmt, 1, 1)) return fail("unknown pixel format");
+    if (h < 1 || w < 1 || (long long)h * w > (1ll << 28)) return fail("bad image size");
+    return 0;
+}
+
+// the bytes of a frame that the detector reads: the luma plane, which comes first, or all of a packed BGR frame
+size_t crop_read_bytes(int fmt, int h, int w)
+{
+    const CropSample cs = crop_sample(fmt);
+    return (size_t)h * w * cs.comps * cs.bytes;
+}
+
+// the line sums of d_frame on the conversions' stream, read back and waited for (g_pix_mu held)
+int crop_sums_run(PixCtx& c, const void* d_frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
+{
+    const size_t need = sizeof(unsigned long long) * ((size_t)h + w);
+    if (c.sums_cap < need) {
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        if (grow_dev(&c.d_sums, &c.sums_cap, need)) return 1;
+    }
+    HIP_TRY(launch_crop_sums(c.stream, d_frame, fmt, h, w, c.d_sums, c.d_sums + h, max_groups));
+    HIP_TRY(hipMemcpyAsync(rows, c.d_sums, sizeof(unsigned long long) * (size_t)h, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(cols, c.d_sums + h, sizeof(unsigned long long) * (size_t)w, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int crop_sums_host(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
+{
+    if (crop_sums_check(frame, fmt, h, w, rows, cols)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = crop_read_bytes(fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, bytes)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, frame, bytes, hipMemcpyHostToDevice, c->stream));
+    return crop_sums_run(*c, c->d_in, fmt, h, w, rows, cols, max_groups);
+}
+
+int pix_window_check(const void* in, int fmt, int src_h, int src_w, int x, int y, int h, int w, const void* out)
+{
+    if (!in || !out) return fail("null frame pointer");
+    if (const char* e = crop_window_error(fmt, src_h, src_w, x, y, h, w)) return fail(e);
+    return 0;
+}
+}  // namespace
+
+int uva_crop_sums(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols)
+{
+    return crop_sums_host(device, frame, fmt, h, w, rows, cols, 0);
+}
+
+int uva_debug_crop_sums(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
+{
+    if (max_groups < 0) return fail("uva_debug_crop_sums: max_groups is 0 (the kernel's own bound) or a number of workgroups");
+    return crop_sums_host(device, frame, fmt, h, w, rows, cols, max_groups);
+}
+
+int uva_crop_sums_device(int device, const void* d_frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols)
+{
+    if (crop_sums_check(d_frame, fmt, h, w, rows, cols)) return 1;
+    if (((uintptr_t)d_frame & 15) != 0) return fail("uva_crop_sums_device: the frame must start at a 16-byte aligned address");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    return crop_sums_run(*c, d_frame, fmt, h, w, rows, cols, 0);
+}
+
+int uva_crop_bounds(const unsigned long long* rows, const unsigned long long* cols, int fmt, int h, int w, int limit, int* bounds)
+{
+    if (const char* e = crop_bounds(rows, cols, fmt, h, w, limit, bounds)) return fail(e);
+    return 0;
+}
+
+int uva_crop_rect(const int* state, int round, int* rect)
+{
+    if (!state || !rect) return fail("uva_crop_rect: null pointer");
+    if (!crop_rect(state, round, rect)) return fail("uva_crop_rect: the state holds no rectangle");
+    return 0;
+}
+
+int uva_pix_window_check(int fmt, int src_h, int src_w, int x, int y, int h, int w)
+{
+    if (const char* e = crop_window_error(fmt, src_h, src_w, x, y, h, w)) return fail(e);
+    return 0;
+}
+
+int uva_pix_window(int device, const void* in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* out)
+{
+    if (pix_window_check(in, fmt, src_h, src_w, x, y, h, w, out)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    WindowPlane pl[3];
+    const int np = crop_window_planes(fmt, src_h, src_w, x, y, h, w, pl);
+    size_t at[3] = {0, 0, 0};
+    const size_t stage = pix_window_staging(pl, np, at), nout = pix_frame_bytes(fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, stage) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    // the window's rows go up at full width, one copy per plane; the kernel compacts their columns
+    for (int p = 0; p < np; ++p)
+        HIP_TRY(hipMemcpyAsync(c->d_in + at[p], (const uint8_t*)in + pl[p].src_off + (size_t)pl[p].row0 * pl[p].src_row,
+                               pl[p].src_row * (size_t)pl[p].rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_pix_window(c->stream, c->d_in, at, c->d_out, pl, np, crop_sample(fmt).bytes));
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_pix_window_device(int device, const void* d_in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* d_out)
+{
+    if (pix_window_check(d_in, fmt, src_h, src_w, x, y, h, w, d_out)) return 1;
+    if (((uintptr_t)d_out & 15) != 0) return fail("uva_pix_window_device: the result must start at a 16-byte aligned address");
+    if (((uintptr_t)d_in & (uintptr_t)(crop_sample(fmt).bytes - 1)) != 0) return fail("uva_pix_window_device: odd address of a frame of 16-bit words");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    WindowPlane pl[3];
+    const int np = crop_window_planes(fmt, src_h, src_w, x, y, h, w, pl);
+    size_t at[3] = {0, 0, 0};
+    for (int p = 0; p < np; ++p) at[p] = pl[p].src_off + (size_t)pl[p].row0 * pl[p].src_row;
+    HIP_TRY(launch_pix_window(c->stream, d_in, at, d_out, pl, np, crop_sample(fmt).bytes));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_net_set_input_window(uva_net* n, int src_h, int src_w, int x, int y)
+{
+    if (!n) return fail("null net");
+    const bool off = !src_h && !src_w && !x && !y;
+    if (!off && (src_h < 1 || src_w < 1 || (long long)src_h * src_w > (1ll << 28)))
+        return fail("uva_net_set_input_window: bad size of the source frame (all zeros switch the window off)");
+    if (!off && (x < 0 || y < 0 || x >= src_w || y >= src_h)) return fail("input window: the window leaves the frame");
+    n->win.src_h = src_h; n->win.src_w = src_w; n->win.x = x; n->win.y = y;
+    // the kept frame of uva_net_set_skip_repeats was compared as another window's bytes: forget it
+    n->rep.valid = false;
+    n->rep.submitted = n->rep.skipped = 0;
     return 0;
 }
 

@@ -309,6 +309,114 @@ def frame_diff(a, b, fmt, h, w, threshold=0, gpu=0, device=False):
     return int(stats[0]), int(stats[1]), int(stats[2])
 
 
+# ---- crop detection and cropped frames (include/uva.h uva_crop_*, uva_pix_window) ------------------
+def _crop_lib(name):
+    L = _lib.load()
+    if not hasattr(L, name):
+        raise _lib.UvaError("this libuva build has no %s: rebuild it" % name)
+    return L
+
+
+def crop_sums(frame, fmt, h, w, gpu=0, device=False, max_groups=None):
+    """The exact sums of every row and every column of a dense h x w frame of `fmt` -- of its luma plane, or of all three
+    components of a packed BGR frame -- on HIP device `gpu` (include/uva.h uva_crop_sums) -> (rows uint64 [h], cols uint64 [w]).
+    device=True: `frame` is a raw device pointer (int) of a frame in that GPU's HBM (uva_crop_sums_device).  max_groups: the
+    test hook uva_debug_crop_sums (a grid of at most that many workgroups)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    rows, cols = np.zeros(max(1, int(h)), np.uint64), np.zeros(max(1, int(w)), np.uint64)
+    if device:
+        L = _crop_lib("uva_crop_sums_device")
+        _lib.check(L.uva_crop_sums_device(int(gpu), ctypes.c_void_p(int(frame)), PIX_FORMATS_ALL[fmt], int(h), int(w), rows.ctypes.data,
+                                          cols.ctypes.data))
+    else:
+        L = _crop_lib("uva_crop_sums")
+        f = _pix_frame(frame, fmt, h, w, "frame")
+        if max_groups is None:
+            _lib.check(L.uva_crop_sums(int(gpu), f.ctypes.data, PIX_FORMATS_ALL[fmt], int(h), int(w), rows.ctypes.data, cols.ctypes.data))
+        else:
+            _lib.check(L.uva_debug_crop_sums(int(gpu), f.ctypes.data, PIX_FORMATS_ALL[fmt], int(h), int(w), rows.ctypes.data,
+                                             cols.ctypes.data, int(max_groups)))
+    return rows[:h], cols[:w]
+
+
+def crop_bounds(rows, cols, fmt, h, w, limit=24):
+    """cropdetect's brightness test on a frame's line sums (include/uva.h uva_crop_bounds; no GPU needed) -> (first bright row,
+    last bright row, first bright column, last bright column), -1 where there is none.  limit: 0 ... 255 on the 8-bit scale."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    r, c = np.ascontiguousarray(rows, np.uint64), np.ascontiguousarray(cols, np.uint64)
+    if r.shape != (int(h),) or c.shape != (int(w),):
+        raise ValueError("rows / cols must hold h / w sums")
+    b = (ctypes.c_int * 4)()
+    _lib.check(_crop_lib("uva_crop_bounds").uva_crop_bounds(r.ctypes.data, c.ctypes.data, PIX_FORMATS_ALL[fmt], int(h), int(w), int(limit), b))
+    return tuple(int(v) for v in b)
+
+
+def crop_rect(state, round=16):
+    """cropdetect's rectangle from a running state (x1, y1, x2, y2) (include/uva.h uva_crop_rect; no GPU needed) -> (W, H, X, Y)
+    in ffmpeg's order, or None when the state holds no rectangle."""
+    st = (ctypes.c_int * 4)(*(int(v) for v in state))
+    rect = (ctypes.c_int * 4)()
+    if _crop_lib("uva_crop_rect").uva_crop_rect(st, int(round), rect):
+        return None
+    return tuple(int(v) for v in rect)
+
+
+def pix_window_check(fmt, src_h, src_w, x, y, h, w):
+    """Raises UvaError with the reason if the window h x w at (x, y) of a src_h x src_w frame of `fmt` is one the library refuses
+    (include/uva.h uva_pix_window_check; no GPU needed)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    _lib.check(_crop_lib("uva_pix_window_check").uva_pix_window_check(PIX_FORMATS_ALL[fmt], int(src_h), int(src_w), int(x), int(y), int(h), int(w)))
+
+
+def pix_window(buf, fmt, src_h, src_w, x, y, h, w, out=None, gpu=0):
+    """The dense h x w frame of `fmt` cut from the dense src_h x src_w frame `buf` at (x, y) on HIP device `gpu`, host to host
+    (include/uva.h uva_pix_window).  Returns `out` (pix_empty's array; allocated when None)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    src = _pix_frame(buf, fmt, src_h, src_w, "input")
+    if out is None:
+        out = pix_empty(fmt, h, w)
+    if not out.flags.c_contiguous or out.nbytes != pix_frame_bytes(fmt, h, w):
+        raise ValueError("out must be a C-contiguous buffer of %d bytes" % pix_frame_bytes(fmt, h, w))
+    _lib.check(_crop_lib("uva_pix_window").uva_pix_window(int(gpu), src.ctypes.data, PIX_FORMATS_ALL[fmt], int(src_h), int(src_w), int(x),
+                                                          int(y), int(h), int(w), out.ctypes.data))
+    return out
+
+
+class CropDetector:
+    """ffmpeg cropdetect's running state over the frames it is shown: update(frame) takes one dense
+    h x w frame of `fmt` -- its line sums come from the GPU (crop_sums), the rest is host arithmetic -- and rect() is the
+    rectangle (W, H, X, Y) after the frames so far, or None."""
+
+    def __init__(self, h, w, fmt, limit=24, round=16, gpu=0):
+        if fmt not in PIX_FORMATS_ALL:
+            raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+        if not 0 <= int(limit) <= 255:
+            raise ValueError("limit is 0 ... 255 on the 8-bit scale")
+        self.h, self.w, self.fmt, self.limit, self.round, self.gpu = int(h), int(w), fmt, int(limit), int(round), int(gpu)
+        self.state = (self.w - 1, self.h - 1, 0, 0)
+
+    def update_sums(self, rows, cols):
+        """the same from a frame's line sums (no GPU needed)"""
+        r0, r1, c0, c1 = crop_bounds(rows, cols, self.fmt, self.h, self.w, self.limit)
+        x1, y1, x2, y2 = self.state
+        if r0 >= 0:
+            y1, y2 = min(y1, r0), max(y2, r1)
+        if c0 >= 0:
+            x1, x2 = min(x1, c0), max(x2, c1)
+        self.state = (x1, y1, x2, y2)
+        return self.state
+
+    def update(self, frame):
+        return self.update_sums(*crop_sums(frame, self.fmt, self.h, self.w, gpu=self.gpu))
+
+    def rect(self):
+        return crop_rect(self.state, self.round)
+
+
 class Ticket:
     """One frame in flight on the pipelined host route; keeps its buffers alive."""
 
@@ -536,7 +644,8 @@ class Net:
         s = self.scale
         if s <= 0:
             raise _lib.UvaError("net has no graph: load_param/load_model failed or were not called")
-        src = _pix_frame(buf, in_fmt, h, w, "input")
+        win = getattr(self, "_window", None)
+        src = _pix_frame(buf, in_fmt, *(win[:2] if win else (h, w)), "input")     # (set_input_window: the source frame)
         rh, rw = h * s, w * s
         if out_size is not None:
             rf = _resize_filter(resize_filter)
@@ -576,6 +685,16 @@ class Net:
         _lib.check(self._L.uva_resize_device(self.device_index, ctypes.c_void_p(d_in), h, w, in_stride or w * 3 * bps, ctypes.c_void_p(d_out),
                                              oh, ow, out_stride or ow * 3 * bps, _resize_filter(filter), int(bit_depth),
                                              after._h if after is not None else None, self._h))
+
+    def set_input_window(self, src_h=0, src_w=0, x=0, y=0):
+        """Cropped input frames (include/uva.h uva_net_set_input_window): while set, `buf` of every
+        submit_pix call is a dense src_h x src_w frame of in_fmt and the call's h x w is the window at (x, y) of it -- only the
+        window is uploaded, the result is that of a dense h x w frame.  All zeros (the default) switch it off.  Forgets the
+        kept frame of set_skip_repeats and zeroes skip_stats().  Needs no GPU."""
+        if not hasattr(self._L, "uva_net_set_input_window"):
+            raise _lib.UvaError("this libuva build has no uva_net_set_input_window: rebuild it")
+        _lib.check(self._L.uva_net_set_input_window(self._h, int(src_h), int(src_w), int(x), int(y)))
+        self._window = (int(src_h), int(src_w), int(x), int(y)) if (src_h or src_w or x or y) else None
 
     def set_skip_repeats(self, threshold):
         """Repeated frames on the pipelined route (include/uva.h uva_net_set_skip_repeats): None or -1

@@ -43,6 +43,13 @@ and the pipe carries frames of the final size:
       | python -m upscale_video_amd.rawvideo -W 1280 -H 720 -s 2 --out-size 2560x1440 --in-pix-fmt yuv420p --out-pix-fmt p010le \\
       | ffmpeg -f rawvideo -pix_fmt p010le -s 2560x1440 -r 24 -i - -c:v libx265 out.mkv
 
+--crop W:H:X:Y (ffmpeg's order) cuts that window out of every input frame in front of the first stage: -W / -H
+stay the size of the frames on the input, everything behind -- the nets, --out-size / --out-scale, --tile, the size of the frames
+that leave -- works from the cropped size, and only the window's rows are uploaded.  --crop auto finds the window first, the way
+the reference does (get_crop_detect, upscale/upscale_processing.py:137-181: ffmpeg's cropdetect at 100 places of the film, the most
+frequent rectangle wins), with the per-frame pass on the GPU; it needs a regular file.  --cropdetect only analyses (pipes too) and
+prints one `crop=W:H:X:Y` line for --crop or for ffmpeg's -vf.
+
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
 conversions run on the net's stream around its kernels); nets in between pass u8 BGR (u16 BGR with --bit-depth 16).  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
@@ -91,7 +98,7 @@ class PixFormats:
     """the raw-video formats of a stream's two ends and the colour arithmetic between them (ncnn.PIX_FORMATS_ALL etc.)"""
 
     def __init__(self, in_fmt="bgr24", out_fmt="bgr24", colour="bt601", color_range="tv", bit_depth=8, chroma_filter="replicate",
-                 chroma_loc="left", out_size=None, resize_filter="lanczos"):
+                 chroma_loc="left", out_size=None, resize_filter="lanczos", crop=None):
         for f in (in_fmt, out_fmt):
             if f not in ncnn.PIX_FORMATS_ALL:
                 raise ValueError("unknown pixel format %r (%s)" % (f, ", ".join(ncnn.PIX_FORMATS_ALL)))
@@ -111,6 +118,24 @@ class PixFormats:
         # (oh, ow): a lane's last stage resamples its result to this size; None: the nets' own size
         self.out_size = None if out_size is None else (int(out_size[0]), int(out_size[1]))
         self.resize_filter = resize_filter
+        # (W, H, X, Y), ffmpeg's order: the window of every input frame that the first stage of a lane takes;
+        # None: whole frames
+        if crop is not None and (len(crop) != 4 or min(crop[:2]) < 1 or min(crop[2:]) < 0):
+            raise ValueError("crop must be (W, H, X, Y), W and H at least 1, X and Y at least 0")
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+
+    def net_size(self, h, w):
+        """the size of the frames the first stage works on, of h x w frames on the input"""
+        return (self.crop[1], self.crop[0]) if self.crop is not None else (h, w)
+
+    def window(self, h, w):
+        """Net.set_input_window's arguments for h x w frames on the input, or None"""
+        return (h, w, self.crop[2], self.crop[3]) if self.crop is not None else None
+
+    def cut(self, frame, h, w, out=None, gpu=0):
+        """the window of one h x w input frame, host to host (ncnn.pix_window): for first stages that are no net"""
+        ch, cw = self.net_size(h, w)
+        return ncnn.pix_window(frame, self.in_fmt, h, w, self.crop[2], self.crop[3], ch, cw, out=out, gpu=gpu)
 
     def depth_kw(self):
         """the keyword the 16-bit calls take (none at 8 bits: those calls are the first pixel-format release's)"""
@@ -188,8 +213,15 @@ def read_exact(f, view):
 class Stage:
     """One net with its own ring of page-locked result buffers and up to PIPE_DEPTH frames in flight."""
 
-    def __init__(self, net, h, w, tile_size, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR, resize=False):
+    def __init__(self, net, h, w, tile_size, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR, resize=False, window=None):
         self.net, self.tile = net, tile_size
+        # window (src_h, src_w, x, y): the frames submitted are src_h x src_w frames of which the net takes h x w at (x, y)
+        # (Net.set_input_window: the window's rows are all that is uploaded); a lane's first stage with --crop
+        self.window = window
+        if window is not None:
+            net.set_input_window(*window)
+        elif getattr(net, "_window", None) is not None:
+            net.set_input_window()             # (a net that an earlier, cropped stream used)
         self.h, self.w, self.in_fmt, self.out_fmt, self.pix = h, w, in_fmt, out_fmt, pix
         s = net.scale
         # resize: the lane's last stage, whose result is resampled to pix.out_size behind the net (Net.submit_pix(out_size=...))
@@ -210,7 +242,7 @@ class Stage:
         out = self.outs[self.n % len(self.outs)]
         self.n += 1
         border = TILE_BORDER if self.tile else 0
-        if self.in_fmt == self.out_fmt == "bgr24" and self.pix.bit_depth == 8 and not self.resize_kw:
+        if self.in_fmt == self.out_fmt == "bgr24" and self.pix.bit_depth == 8 and not self.resize_kw and self.window is None:
             self.inflight.append(self.net.submit_u8(frame, out=out, tile_size=self.tile, border=border))
         else:
             self.inflight.append(self.net.submit_pix(frame, self.h, self.w, self.in_fmt, out=out, out_fmt=self.out_fmt,
@@ -233,8 +265,11 @@ class DenoiseStage:
     class _Scale1:
         scale = 1
 
-    def __init__(self, gpu, strength, h, w, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR):
+    def __init__(self, gpu, strength, h, w, alloc, in_fmt="bgr24", out_fmt="bgr24", pix=BGR, window=None):
         self.gpu, self.strength = gpu, float(strength)
+        # window (src_h, src_w, x, y): the frames submitted are src_h x src_w frames, cut to h x w first (ncnn.pix_window)
+        self.window = window
+        self._cut = ncnn.pix_empty(in_fmt, h, w, alloc) if window is not None else None
         self.net = self._Scale1()
         self.in_fmt, self.out_fmt, self.pix = in_fmt, out_fmt, pix
         self.native = "bgr48le" if pix.bit_depth == 16 else "bgr24"
@@ -263,6 +298,8 @@ class DenoiseStage:
         self.n += 1
         h, w = self.h, self.w
         pix = self.pix
+        if self.window is not None:
+            frame = pix.cut(frame, self.window[0], self.window[1], out=self._cut, gpu=self.gpu)
         if self.in_fmt != self.native:
             frame = ncnn.convert_pix(frame, h, w, self.in_fmt, self.native, pix.colour, pix.color_range, out=self._bgr_in, gpu=self.gpu,
                                      **pix.depth_kw(), **pix.chroma_kw())
@@ -283,7 +320,8 @@ class Lane:
     """The chain of nets of ONE -g entry (one or two Stages on one GPU).  Frames go in with submit() and come out,
     in the order they went in, with pop()."""
 
-    def __init__(self, nets_tiles, h, w, alloc, pix=BGR):
+    def __init__(self, nets_tiles, h, w, alloc, pix=BGR, src=None):
+        """h x w: the frames the first stage works on; src (h, w): the frames submitted when pix.crop cuts them to that"""
         self.stages = []
         last = len(nets_tiles) - 1
         for k, (net, tile) in enumerate(nets_tiles):
@@ -291,6 +329,8 @@ class Lane:
             # (--bit-depth 16: u16 BGR, so that the hop between the nets of `-m a` keeps the depth)
             mid = "bgr48le" if pix.bit_depth == 16 else "bgr24"
             fmts = dict(in_fmt=pix.in_fmt if k == 0 else mid, out_fmt=pix.out_fmt if k == last else mid, pix=pix)
+            if k == 0 and src is not None and pix.crop is not None:
+                fmts["window"] = pix.window(*src)
             if isinstance(net, tuple):         # ("denoise", gpu, K): the `-m n=K` stage
                 if k == last and pix.out_size is not None:
                     raise ValueError("--out-size / --out-scale: the resampler sits behind a net, and this lane ends in the denoise "
@@ -354,11 +394,13 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
     alloc = alloc or ncnn.pinned_empty
     pix = pix or BGR
     lanes_spec = nets_tiles if nets_tiles and isinstance(nets_tiles[0], list) else [nets_tiles]
-    lanes = [Lane(spec, h, w, alloc, pix) for spec in lanes_spec]
+    src_h, src_w = h, w                    # the frames on the input; with pix.crop the lanes work on a window of them
+    h, w = pix.net_size(h, w)
+    lanes = [Lane(spec, h, w, alloc, pix, src=(src_h, src_w)) for spec in lanes_spec]
     nl = len(lanes)
     # an input buffer is free again once its frame has left its lane's first stage: at most PIPE_DEPTH per lane are
     # there, plus the one being read into
-    ins = [ncnn.pix_empty(pix.in_fmt, h, w, alloc) for _ in range(nl * PIPE_DEPTH + 2)]
+    ins = [ncnn.pix_empty(pix.in_fmt, src_h, src_w, alloc) for _ in range(nl * PIPE_DEPTH + 2)]
 
     # writer thread: the blocking write of frame i overlaps the read of frame i+k and the GPUs
     wq = queue.Queue(maxsize=2)
@@ -524,7 +566,8 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
     full-size file of zeros and holes is worse than none).  pix: PixFormats of the two ends (default bgr24).  Returns the number
     of frames written."""
     pix = pix or BGR
-    fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(*pix.result_size(h * scale_total, w * scale_total), out=True)
+    net_h, net_w = pix.net_size(h, w)      # (pix.crop: the lanes work on a window of the h x w frames in the file)
+    fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(*pix.result_size(net_h * scale_total, net_w * scale_total), out=True)
     nl = len(lanes_spec)
     ins = list(in_path) if isinstance(in_path, (list, tuple)) else None
     outs = list(out_path) if isinstance(out_path, (list, tuple)) else None
@@ -717,18 +760,24 @@ def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
     uva_pix_convert16, through u16 BGR).  With pix.out_size every frame is converted to BGR, resampled (include/uva.h uva_resize)
     and converted to the output format at the new size."""
     pix = pix or BGR
+    src_h, src_w = h, w
+    h, w = pix.net_size(h, w)              # (pix.crop: every frame is cut first, ncnn.pix_window)
     if pix.out_size is not None and pix.out_size != (h, w):
-        return _copy_through_sized(fin, fout, h, w, max_frames, pix, gpu)
-    buf = bytearray(pix.frame_bytes(h, w))
+        return _copy_through_sized(fin, fout, src_h, src_w, max_frames, pix, gpu)
+    buf = bytearray(pix.frame_bytes(src_h, src_w))
+    cut = np.empty(pix.frame_bytes(h, w), np.uint8) if pix.crop is not None else None
     res = ncnn.pix_empty(pix.out_fmt, h, w) if pix.in_fmt != pix.out_fmt else None
     n = 0
     while max_frames is None or n < max_frames:
         if not read_exact(fin, memoryview(buf)):
             break
+        frame = buf
+        if cut is not None:
+            frame = memoryview(pix.cut(np.frombuffer(buf, np.uint8), src_h, src_w, out=cut, gpu=gpu))
         if res is None:
-            fout.write(buf)
+            fout.write(frame)
         else:
-            ncnn.convert_pix(np.frombuffer(buf, np.uint8), h, w, pix.in_fmt, pix.out_fmt, pix.colour, pix.color_range, out=res, gpu=gpu,
+            ncnn.convert_pix(np.frombuffer(frame, np.uint8), h, w, pix.in_fmt, pix.out_fmt, pix.colour, pix.color_range, out=res, gpu=gpu,
                              **pix.depth_kw(), **pix.chroma_kw())
             fout.write(memoryview(res).cast("B"))
         n += 1
@@ -741,14 +790,19 @@ def _copy_through_sized(fin, fout, h, w, max_frames, pix, gpu):
     oh, ow = pix.out_size
     native = "bgr48le" if pix.bit_depth == 16 else "bgr24"
     kw = dict(colour=pix.colour, color_range=pix.color_range, gpu=gpu, **pix.depth_kw(), **pix.chroma_kw())
-    buf = ncnn.pix_empty(pix.in_fmt, h, w)
+    src_h, src_w = h, w
+    h, w = pix.net_size(h, w)
+    whole = ncnn.pix_empty(pix.in_fmt, src_h, src_w)
+    buf = ncnn.pix_empty(pix.in_fmt, h, w) if pix.crop is not None else whole
     small = ncnn.pix_empty(native, h, w)
     big = ncnn.pix_empty(native, oh, ow)
     res = ncnn.pix_empty(pix.out_fmt, oh, ow)
     n = 0
     while max_frames is None or n < max_frames:
-        if not read_exact(fin, memoryview(buf).cast("B")):
+        if not read_exact(fin, memoryview(whole).cast("B")):
             break
+        if pix.crop is not None:
+            pix.cut(whole, src_h, src_w, out=buf, gpu=gpu)
         bgr = buf if pix.in_fmt == native else ncnn.convert_pix(buf, h, w, pix.in_fmt, native, out=small, **kw)
         ncnn.resize(bgr, (oh, ow), pix.resize_filter, gpu=gpu, out=big)
         done = big if pix.out_fmt == native else ncnn.convert_pix(big, oh, ow, native, pix.out_fmt, out=res, **kw)
@@ -762,6 +816,95 @@ def out_scale_size(h, w, f):
     """--out-scale F at an h x w input: per axis 2 floor(n F / 2 + 0.5), at least 2 (even sizes: 4:2:0 formats, encoders)"""
     import math
     return tuple(max(2, 2 * int(math.floor(n * f / 2 + 0.5))) for n in (h, w))
+
+
+def parse_crop(text):
+    """'W:H:X:Y' (ffmpeg's order; a leading 'crop=' is accepted, as --cropdetect and ffmpeg print it) -> (W, H, X, Y)"""
+    import re
+    m = re.fullmatch(r"(?:crop=)?(\d+):(\d+):(\d+):(\d+)", text.strip())
+    if not m:
+        raise ValueError("--crop takes W:H:X:Y (ffmpeg's order, e.g. 1920:800:0:140) or auto, not %r" % text)
+    cw, ch, x, y = (int(g) for g in m.groups())
+    if cw < 1 or ch < 1:
+        raise ValueError("--crop: the window must be at least 1x1, not %dx%d" % (cw, ch))
+    return cw, ch, x, y
+
+
+def crop_sample_positions(n_frames):
+    """Where --crop auto and --cropdetect look at a file of n_frames frames: the reference's recipe (get_crop_detect,
+    upscale/upscale_processing.py:144-152: `-ss (i + 1) * int(duration / 120)` for i = 10 ... 109, two frames each) in frames
+    instead of seconds -- min((i + 1) * (n_frames // 120), n_frames - 2), never below 0, duplicates dropped, in order."""
+    step = n_frames // 120
+    out = []
+    for i in range(10, 110):
+        p = max(0, min((i + 1) * step, n_frames - 2))
+        if p not in out:
+            out.append(p)
+    return out if n_frames > 0 else []
+
+
+class CropVotes:
+    """One vote per frame shown: the rectangle after that frame.  The most frequent wins, ties go to the larger area, then to the
+    rectangle seen first."""
+
+    def __init__(self):
+        self.count = {}         # (W, H, X, Y) -> votes, in order of first appearance
+
+    def add(self, rect):
+        if rect is not None:
+            self.count[rect] = self.count.get(rect, 0) + 1
+
+    def winner(self):
+        best = None
+        for rect, c in self.count.items():
+            if best is None or (c, rect[0] * rect[1]) > (self.count[best], best[0] * best[1]):
+                best = rect
+        return best
+
+
+def detect_crop_file(path, h, w, fmt, limit=24, round=16, gpu=0, max_frames=None, detector=None):
+    """--crop auto / --cropdetect on a regular file of h x w frames of fmt: at every position of crop_sample_positions a fresh
+    detector (ncnn.CropDetector: the line sums on the GPU) sees two consecutive frames and casts one vote per frame.  Returns
+    (W, H, X, Y) or None."""
+    detector = detector or ncnn.CropDetector
+    fb = ncnn.pix_frame_bytes(fmt, h, w)
+    size = os.path.getsize(path)
+    if size % fb:
+        raise EOFError("%s ends inside a frame (%d bytes, frames of %d)" % (path, size, fb))
+    n = size // fb if max_frames is None else min(size // fb, max_frames)
+    votes = CropVotes()
+    buf = np.empty(fb, np.uint8)
+    with open(path, "rb") as f:
+        for p in crop_sample_positions(n):
+            det = detector(h, w, fmt, limit=limit, round=round, gpu=gpu)
+            f.seek(p * fb)
+            for _ in range(min(2, n - p)):
+                if not read_exact(f, memoryview(buf)):
+                    break
+                det.update(buf)
+                votes.add(det.rect())
+    return votes.winner()
+
+
+def detect_crop_pipe(fin, h, w, fmt, limit=24, round=16, gpu=0, stride=240, max_frames=None, detector=None):
+    """--cropdetect on a pipe: the whole input is read, and every `stride` frames a fresh detector sees a pair of frames, one vote
+    per frame.  Returns (W, H, X, Y) or None."""
+    detector = detector or ncnn.CropDetector
+    if stride < 2:
+        raise ValueError("--cropdetect-stride: at least 2 frames (a pair is looked at every so many)")
+    buf = np.empty(ncnn.pix_frame_bytes(fmt, h, w), np.uint8)
+    votes = CropVotes()
+    det, n = None, 0
+    while max_frames is None or n < max_frames:
+        if not read_exact(fin, memoryview(buf)):
+            break
+        if n % stride == 0:
+            det = detector(h, w, fmt, limit=limit, round=round, gpu=gpu)
+        if n % stride < 2:
+            det.update(buf)
+            votes.add(det.rect())
+        n += 1
+    return votes.winner()
 
 
 def main(argv=None):
@@ -825,11 +968,80 @@ def main(argv=None):
                          "(animation on twos and threes, screen captures, telecined film).  T (default 0: exact, the output is "
                          "byte for byte what it is without the option) is the largest difference in code values, 0 ... 65535, "
                          "at which a sample still counts as equal; DESIGN.md section 7.8")
+    ap.add_argument("--crop", default=None, metavar="W:H:X:Y|auto",
+                    help="cut this window (ffmpeg's order) out of every -W x -H input frame in front of the first stage; everything "
+                         "behind works from the cropped size and only the window is uploaded.  auto: find it first as the "
+                         "reference does (cropdetect's rule at 100 places of the file, the most frequent rectangle; regular files "
+                         "only).  Y'CbCr formats: X and W even, 4:2:0 formats also Y and H; DESIGN.md section 7.12")
+    ap.add_argument("--cropdetect", action="store_true",
+                    help="analysis only: read the whole input (a pipe too), write no frames, print one crop=W:H:X:Y line for --crop "
+                         "or for ffmpeg's -vf.  A file is sampled as --crop auto samples it, a pipe every --cropdetect-stride frames")
+    ap.add_argument("--cropdetect-stride", type=int, default=240, metavar="N",
+                    help="--cropdetect on a pipe: a pair of frames is looked at every N frames (default 240)")
+    ap.add_argument("--crop-limit", type=int, default=24, metavar="L",
+                    help="--crop auto / --cropdetect: a line is picture when its mean is above L on the 8-bit scale (0 ... 255; "
+                         "cropdetect's default 24)")
+    ap.add_argument("--crop-round", type=int, default=16, metavar="R",
+                    help="--crop auto / --cropdetect: width and height are rounded down to a multiple of R (cropdetect's default 16)")
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
     if a.skip_repeats is not None and not 0 <= a.skip_repeats <= 65535:
         ap.error("--skip-repeats takes a threshold T of 0 ... 65535 code values, not %d" % a.skip_repeats)
+    try:
+        gpus = [int(tok) for tok in str(a.gpu).split(",") if tok != ""] or [0]
+    except ValueError:
+        ap.error("-g takes a comma-separated list of GPU ordinals")
+    if not 0 <= a.crop_limit <= 255:
+        ap.error("--crop-limit is 0 ... 255 on the 8-bit scale, not %d" % a.crop_limit)
+    if a.cropdetect_stride < 2:
+        ap.error("--cropdetect-stride: at least 2 frames")
+    if a.in_pix_fmt in ncnn.PIX16_ONLY and a.bit_depth != 16:
+        ap.error("%s is a 16-bit format: it needs --bit-depth 16" % a.in_pix_fmt)
+    crop = None
+    if a.cropdetect or (a.crop is not None and a.crop.strip() == "auto"):
+        what = "--cropdetect" if a.cropdetect else "--crop auto"
+        is_file = a.input != "-" and os.path.isfile(a.input)
+        if not a.cropdetect and not is_file:
+            ap.error("--crop auto looks at 100 places of the input and then reads it again, so it needs a regular file, not a pipe "
+                     "(%s): run --cropdetect on the stream first and hand its crop=W:H:X:Y to --crop" % a.input)
+        kw = dict(limit=a.crop_limit, round=a.crop_round, gpu=gpus[0], max_frames=a.frames)
+        if is_file:
+            crop = detect_crop_file(a.input, a.height, a.width, a.in_pix_fmt, **kw)
+        else:
+            fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
+            grow_pipe(fin)
+            try:
+                crop = detect_crop_pipe(fin, a.height, a.width, a.in_pix_fmt, stride=a.cropdetect_stride, **kw)
+            finally:
+                if fin is not sys.stdin.buffer:
+                    fin.close()
+        if a.cropdetect:
+            if crop is None:
+                print("%s: no frame had a bright line, no rectangle" % what, file=sys.stderr)
+            else:
+                print("crop=%d:%d:%d:%d" % crop)
+            ncnn.destroy_gpu_instance()
+            return 0 if crop is not None else 1
+        if crop is None:
+            print("--crop auto: no frame had a bright line, no rectangle: the frames go uncropped", file=sys.stderr)
+        else:
+            print("--crop auto: crop=%d:%d:%d:%d" % crop, file=sys.stderr)
+    elif a.crop is not None:
+        try:
+            crop = parse_crop(a.crop)
+        except ValueError as e:
+            ap.error(str(e))
+    if crop is not None:
+        from ._lib import UvaError
+        try:
+            ncnn.pix_window_check(a.in_pix_fmt, a.height, a.width, crop[2], crop[3], crop[1], crop[0])
+        except UvaError as e:
+            ap.error("--crop %d:%d:%d:%d of %dx%d %s frames: %s" % (crop + (a.width, a.height, a.in_pix_fmt, e)))
+        if crop == (a.width, a.height, 0, 0):
+            crop = None                         # the whole frame: today's calls
+    # the size the lanes work on: everything below that used to take -W / -H takes this
+    net_h, net_w = (crop[1], crop[0]) if crop is not None else (a.height, a.width)
     out_size = None
     if a.out_size is not None and a.out_scale is not None:
         ap.error("--out-size and --out-scale exclude each other")
@@ -842,13 +1054,13 @@ def main(argv=None):
     elif a.out_scale is not None:
         if not a.out_scale > 0 or a.out_scale != a.out_scale or a.out_scale == float("inf"):
             ap.error("--out-scale takes a positive number")
-        out_size = out_scale_size(a.height, a.width, a.out_scale)
+        out_size = out_scale_size(net_h, net_w, a.out_scale)
     if out_size is not None:
         flag = "--out-size" if a.out_size is not None else "--out-scale"
-        for n_out, n_net, what in ((out_size[0], a.height * a.scale, "height"), (out_size[1], a.width * a.scale, "width")):
+        for n_out, n_net, what in ((out_size[0], net_h * a.scale, "height"), (out_size[1], net_w * a.scale, "width")):
             if n_out * 4 < n_net or n_out > n_net * 4:
                 ap.error("%s: %s %d is outside [1/4, 4] of the net's result (%d with -s %d)" % (flag, what, n_out, n_net, a.scale))
-        if out_size == (a.height * a.scale, a.width * a.scale):
+        if out_size == (net_h * a.scale, net_w * a.scale):
             out_size = None                     # the nets' own size: nothing to resample, today's calls
     for f in (a.in_pix_fmt, a.out_pix_fmt):
         if f in ncnn.PIX16_ONLY and a.bit_depth != 16:
@@ -856,7 +1068,7 @@ def main(argv=None):
     if a.chroma_loc is not None and a.chroma_filter != "bilinear":
         ap.error("--chroma-loc needs --chroma-filter bilinear: replicate knows no siting")
     pix = PixFormats(a.in_pix_fmt, a.out_pix_fmt, a.colorspace, a.color_range, a.bit_depth, a.chroma_filter, a.chroma_loc or "left",
-                     out_size, a.resize_filter)
+                     out_size, a.resize_filter, crop)
     # upscale_video.py -m: a (anime pass), n=K (film-grain denoise, K = 1..30, :782-789), r (the x_Valar_v1 model instead of
     # x_Compact_Pretrain, :913-916); the reference runs them in the order n, a, upscale (:880-920) whatever the order given
     models = [m for m in a.models.split(",") if m]
@@ -900,10 +1112,6 @@ def main(argv=None):
     # upscale_video.py: `-m a` runs the 1x HurrDeblur pass (process_model, :888-909), `-s 2|4` the Compact net
     # (upscale_frames, :930-944), and `-s 1` performs NO network pass of its own: its frames are only renamed
     # (:924-929).  So `-s 1` alone copies frames through, `-s 1 -m a` is the HurrDeblur pass alone.
-    try:
-        gpus = [int(tok) for tok in str(a.gpu).split(",") if tok != ""] or [0]
-    except ValueError:
-        ap.error("-g takes a comma-separated list of GPU ordinals")
     nets = []                     # one chain of nets per -g entry
     for gpu in gpus:
         chain = []
