@@ -163,7 +163,8 @@ struct uva_net {
     bool u16_1x = false;          // ... takes part in the 16-bit route (sub10_kernel16; uva_net_enable_u16_1x)
     bool fuse_pairs = true;       // 64-feature nets: trunk layers run two per launch (trunk2_kernel); UVA_TRUNK_FUSION=0 turns it off
     bool carry = true;            // ... and between two launches the negated channels stay negated in HBM (UVA_TW_CARRY=0: every launch
-                                  // restores the signs in front of its stores)
+                                  // restores the signs in front of its stores), and trunkw_kernel's producers carry two rows' partial sums
+                                  // from step to step (UVA_TW_CARRY=0: the k-loop that reads all six rows of a step's window)
     bool act16 = true;            // trunkw_kernel: PReLU on packed fp16 (uva_wino.h TW_ACT_F16); UVA_TW_ACT16=0: on the fp32 sums
     bool wino = true;             // ... as 1-D Winograd F(2,3) (trunkw_kernel); UVA_TRUNK_WINO=0: trunk2_kernel (direct convolution)
     LastCall last;
@@ -482,7 +483,7 @@ int launch_trunkw(uva_net* n, const Workspace* ws, TrunkwArgs& a, int i, bool in
     }
     if (in_negated) a.wpk[0] = n->layers[i].wpk_wn;
     const int act = !n->act16 ? TW_ACT_F32 : (n->layers[i + 1].flip_w && !carry_out) ? TW_ACT_F16_FLIP : TW_ACT_F16;
-    HIP_TRY(launch_trunkw_kernel(n->stream, ws->grid2, a, act));
+    HIP_TRY(launch_trunkw_kernel(n->stream, ws->grid2, a, act, n->carry));
     return 0;
 }
 

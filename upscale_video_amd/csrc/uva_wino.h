@@ -32,7 +32,9 @@ struct TrunkwArgs {
 //                  (those whose slope[1] exceeds 1) get their sign back in front of the stores to HBM.
 enum { TW_ACT_F32 = 0, TW_ACT_F16 = 1, TW_ACT_F16_FLIP = 2 };
 
-// One launch of trunkw_kernel<64, act> on `grid` workgroups.  Returns hipSuccess or the failing call's error.
-hipError_t launch_trunkw_kernel(hipStream_t stream, int grid, const TrunkwArgs& a, int act);
+// One launch of trunkw_kernel<64, act, row_carry> on `grid` workgroups.  Returns hipSuccess or the failing call's error.
+// row_carry = false is the k-loop that reads all six rows of a step's window again instead of carrying two rows' partial sums
+// between steps: the same bytes, kept for the tests to hold the product's kernel to (UVA_TW_CARRY=0).
+hipError_t launch_trunkw_kernel(hipStream_t stream, int grid, const TrunkwArgs& a, int act, bool row_carry = true);
 
 }  // namespace uva

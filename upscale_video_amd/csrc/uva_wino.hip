@@ -6,11 +6,12 @@
 
 namespace uva {
 
-template <int ACT>
+template <int ACT, bool CARRY>
 static hipError_t launch_act(hipStream_t stream, int grid, const TrunkwArgs& a)
 {
-    auto kfn = trunkw_kernel<64, ACT>;
-    static std::atomic<bool> attr_done[64];        // per device: the kernel's 158.5 KB of dynamic LDS must be allowed once
+    auto kfn = trunkw_kernel<64, ACT, CARRY>;
+    constexpr int TW_LDS_BYTES = TwLds<CARRY>::BYTES;
+    static std::atomic<bool> attr_done[64];        // per device: the kernel's 142.5 KB of dynamic LDS must be allowed once
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -23,14 +24,20 @@ static hipError_t launch_act(hipStream_t stream, int grid, const TrunkwArgs& a)
     return hipGetLastError();
 }
 
-hipError_t launch_trunkw_kernel(hipStream_t stream, int grid, const TrunkwArgs& a, int act)
+template <bool CARRY>
+static hipError_t launch_carry(hipStream_t stream, int grid, const TrunkwArgs& a, int act)
 {
     switch (act) {
-    case TW_ACT_F32: return launch_act<TW_ACT_F32>(stream, grid, a);
-    case TW_ACT_F16: return launch_act<TW_ACT_F16>(stream, grid, a);
-    case TW_ACT_F16_FLIP: return launch_act<TW_ACT_F16_FLIP>(stream, grid, a);
+    case TW_ACT_F32: return launch_act<TW_ACT_F32, CARRY>(stream, grid, a);
+    case TW_ACT_F16: return launch_act<TW_ACT_F16, CARRY>(stream, grid, a);
+    case TW_ACT_F16_FLIP: return launch_act<TW_ACT_F16_FLIP, CARRY>(stream, grid, a);
     }
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_trunkw_kernel(hipStream_t stream, int grid, const TrunkwArgs& a, int act, bool row_carry)
+{
+    return row_carry ? launch_carry<true>(stream, grid, a, act) : launch_carry<false>(stream, grid, a, act);
 }
 
 }  // namespace uva

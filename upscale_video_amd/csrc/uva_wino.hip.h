@@ -22,12 +22,15 @@
 //   group A (waves 0-3) = layer i, group B (waves 4-7) = layer i+1, ping-pong as in trunk2_kernel: A's k-loop runs
 //   beside B's epilogue (HBM stores) in phase X, B's k-loop beside A's epilogue in phase Y.  A wave owns 16 OUTPUT
 //   CHANNELS (96 weight registers: 4 transformed taps x 3 rows x 64 input channels) and all 4 rows x 16 pairs of a
-//   step: 16 accumulators [row][j], 48 fragment reads and 96 MFMAs per k-loop, every fragment used by up to three
-//   filter rows.  Both k-loops read TRANSFORMED rows:
-//     A-ring (6 rows):  filled in phase Y from the 4 new RAW input rows of the next step (LDS-DMA by A's waves into a
-//                       2-slot staging area one and a half periods ahead; B's wave w transforms row w once its k-loop
-//                       is done -- A's epilogue is the longer half of that phase); the two rows a step shares with
-//                       the previous one stay where they are;
+//   step: 16 accumulators [row][j] and 96 MFMAs per k-loop, every fragment used by up to three filter rows.  The
+//   consumers read all six rows of a step's window, 48 fragments; the PRODUCERS read only the step's four NEW rows, 32
+//   fragments of three MFMAs each, and carry the partial sums of the next step's first two rows -- the contributions of
+//   this step's last two input rows -- across the step boundary in eight more accumulators (acc[4..5] -> acc[0..1]: the
+//   first MFMA of a carried row takes the old registers as its C operand, no copy).  Per output the order of the MFMAs
+//   is the six-row k-loop's, so the sums are the same bits.  Both k-loops read TRANSFORMED rows:
+//     A-ring (4 rows):  filled in phase Y from the 4 new RAW input rows of the next step (LDS-DMA by A's waves into a
+//                       2-slot staging area one and a half periods ahead; B's wave w transforms row w inside its
+//                       k-loop); every row is read once, in the phase X that follows;
 //     B-ring (10 rows): A's epilogue turns its result pairs into V0..V3 with the neighbouring lane's pair
 //                       (v_mov_dpp row_shl:1) and writes them here; B is 1.5 steps behind.
 //   Pair p of a step's block: A computes intermediate columns x0-1+2p, x0+2p (16 pairs = 32 columns from the 34
@@ -37,7 +40,8 @@
 //   build_trunkw_schedule; the CPU test walks the lists and checks that every pixel is produced exactly once from
 //   valid rows).
 //
-// LDS (162 304 of 163 840 bytes):
+// LDS (145 920 of 163 840 bytes; the six-row A-ring of trunkw_kernel<64, ACT, false> -- the k-loop without the carry, kept
+// as the tests' byte-for-byte yardstick -- takes 16 384 more):
 //   transformed rows: [j 0..3][channel half][pair][4 x 16 B], unit o of pair p in slot o ^ ((p >> 1) & 3):
 //     fragment reads (lane (o, p)) and the 16-byte writes (8 consecutive pairs) are bank-conflict free;
 //   raw rows: 34 pixel records of 128 B, column cc = 2h + par in record h + 17 par, octet in slot octet ^ (h & 7):
@@ -52,19 +56,30 @@ namespace uva {
 
 constexpr int TW_AROWB = 4 * 2 * 16 * 64;         // 8192: one transformed row of the A-ring (16 pairs)
 constexpr int TW_BROWB = 4 * 2 * 15 * 64;         // 7680: one transformed row of the B-ring (15 pairs)
-constexpr int TW_AROWS = 6, TW_BROWS = 10;
+constexpr int TW_BROWS = 10;
 constexpr int TW_RAWROWB = 34 * 128;              // 4352
 constexpr int TW_RAWSLOTB = 4 * TW_RAWROWB;       // 17 408 = 17 LDS-DMA pieces
 constexpr int TW_RAW_PIECES = TW_RAWSLOTB / 1024;
-constexpr int TW_ARING = 0;
-constexpr int TW_BRING = TW_ARING + TW_AROWS * TW_AROWB;
-constexpr int TW_RAW = TW_BRING + TW_BROWS * TW_BROWB;
-constexpr int TW_PRM = TW_RAW + 2 * TW_RAWSLOTB;
-constexpr int TW_FLAGS_OFF = TW_PRM + 2 * PARAM_LDS + 64;       // (TW_FLAGS) two step counters: [0] producers' k-loops done, [1] consumers'
-constexpr int TW_LDS_BYTES = TW_FLAGS_OFF + 16;                 // + a spare unit per lane group (pair 15's writes) + the counters
+// The LDS map.  CARRY (the product): the producers carry two rows' partial sums between steps and the A-ring holds a step's
+// four new rows; without it the A-ring also keeps the two rows a step shares with the one above.
+template <bool CARRY>
+struct TwLds {
+    static constexpr int AROWS = CARRY ? 4 : 6;
+    static constexpr int ARING = 0;
+    static constexpr int BRING = ARING + AROWS * TW_AROWB;
+    static constexpr int RAW = BRING + TW_BROWS * TW_BROWB;
+    static constexpr int PRM = RAW + 2 * TW_RAWSLOTB;
+    static constexpr int FLAGS_OFF = PRM + 2 * PARAM_LDS + 64;      // (TW_FLAGS) two step counters: [0] producers' k-loops done, [1] consumers'
+    static constexpr int BYTES = FLAGS_OFF + 16;                    // + a spare unit per lane group (pair 15's writes) + the counters
+    // the two extra input rows of a workgroup's first step (entry bit 25), while the B-ring is still unused: raw, then transformed
+    static constexpr int SIX_RAW = BRING, SIX_RAWB = 5120, SIX_ROWS = BRING + 16384;
+    static_assert(BYTES <= 160 * 1024, "trunkw kernel LDS budget");
+    static_assert(RAW % 128 == 0 && TW_RAWROWB % 128 == 0, "raw pixel records are 128-byte aligned (the octet XOR flips address bits 4..6)");
+    static_assert(2 * SIX_RAWB <= 16384 && SIX_ROWS + 2 * TW_AROWB <= RAW, "the first step's extra rows fit the B-ring");
+    static_assert((AROWS - 1) * TW_AROWB + 3 * (TW_AROWB / 4) + TW_AROWB / 8 < 65536, "a ring row's fragments are immediate offsets of one address");
+};
 static_assert(TW_RAW_PIECES == 17 && TW_RAWSLOTB % 1024 == 0, "raw slot = whole LDS-DMA pieces");
-static_assert(TW_LDS_BYTES <= 160 * 1024, "trunkw kernel LDS budget");
-static_assert(TW_RAW % 128 == 0 && TW_RAWROWB % 128 == 0, "raw pixel records are 128-byte aligned (the octet XOR flips address bits 4..6)");
+static_assert(TwLds<true>::BYTES + 16384 == TwLds<false>::BYTES, "the carry frees two A-ring rows (left unused)");
 
 // Step g of a workgroup (host: build_trunkw_schedule).  Trunk2Step's 32 bytes, other meaning:
 //   a: x = byte offset (low 32) of input pixel (yA + 1, x0 - 2) -- the first of the step's four NEW input rows --
@@ -118,18 +133,21 @@ __device__ __forceinline__ unsigned pk_add_f16(unsigned a, unsigned b)
 #define TW_STAMP(k) do { } while (0)
 #endif
 
-template <int NF, int ACT>
+template <int NF, int ACT, bool CARRY = true>
 __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs a)
 {
     static_assert(NF == 64, "written for 64 features");
     constexpr int PIXB = 128;
+    using Lds = TwLds<CARRY>;
+    constexpr int TW_AROWS = Lds::AROWS, TW_ARING = Lds::ARING, TW_BRING = Lds::BRING, TW_RAW = Lds::RAW, TW_PRM = Lds::PRM, TW_FLAGS_OFF = Lds::FLAGS_OFF;
     // Schedule constants.  Each is the survivor of a measured A/B (profiles/r04_ab_results.txt, r05_ab_results.txt); the
     // variants that lost -- raw rows transformed by the producers (TW_XA), epilogue rows inside the k-loop (TW_INROWS), LDS step
     // counters instead of barriers (TW_FLAGS), the producers' LDS-DMA issued late (TW_DMA_LATE) or by both groups (TW_DMA_B < 5),
     // deferred producer rows (TW_DEFER_A), both groups pre-reading (TW_PRE_BAR = 3), 128-bit stores (TW_W128) and the two
     // wrong-result ceiling experiments (TW_EXP_2D, TW_ABL_*) -- left this file in round 6: tools/experiments/tw_variants_r05.patch.
-    constexpr int TW_PFF = 12;        // fragments the producers' k-loop reads ahead of its MFMAs (an LDS read takes ~280 cycles to come
-                                      // back while four waves stream fragments, an MFMA 16; 6 until round 5: +0.3-0.6 %, 254 VGPRs)
+    constexpr int TW_PFF = CARRY ? 6 : 12;    // fragments the producers' k-loop reads ahead of its MFMAs (an LDS read takes ~280 cycles to come
+                                      // back while four waves stream fragments, an MFMA 16; 12 against 6 was +0.3-0.6 %: the carried rows'
+                                      // 32 accumulator registers are paid from this queue)
     constexpr int TW_PFF_B = 6;       // ... the consumers': the in-stream raw-row transform has the registers (7: no faster; 8 spills; 4: -0.5 %).
                                       // The consumers read these first fragments (window row 0: written a period or more ago) in FRONT of the
                                       // barrier that opens their phase and pass it without waiting for them; the producers read behind theirs.
@@ -221,9 +239,9 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
     const unsigned vlane_c = vlane_of(lane);
     const unsigned t_lo = (unsigned)((lane & 15) * PIXB + (((lane >> 4) ^ (lane & 7)) << 4));
     const unsigned t_hi = (unsigned)(((lane & 15) + 1) * PIXB + (((lane >> 4) ^ (((lane & 15) + 1) & 7)) << 4));
-    auto transform_row = [&](const char* rrow, int pos) __attribute__((always_inline)) {
+    auto transform_row = [&](const char* rrow, int vbase) __attribute__((always_inline)) {      // vbase: the transformed row's place in LDS
         const unsigned a_lo = t_lo, a_hi = t_hi;
-        char* const vrow = smem + TW_ARING + pos * TW_AROWB + vlane_c;
+        char* const vrow = smem + vbase + vlane_c;
         half8 d[2][4];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {              // all eight reads first: one LDS round trip, not two
@@ -256,12 +274,13 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
     auto transform_rows = [&](int slot, int pos0) __attribute__((always_inline)) {
         int pos = pos0 + wave;
         pos = pos >= TW_AROWS ? pos - TW_AROWS : pos;
-        transform_row(smem + TW_RAW + slot * TW_RAWSLOTB + wave * TW_RAWROWB, pos);
+        transform_row(smem + TW_RAW + slot * TW_RAWSLOTB + wave * TW_RAWROWB, TW_ARING + pos * TW_AROWB);
     };
 
     // ---- prologue: weights, parameters; A: raw rows of steps 0 and 1, rows of step 0 transformed -----------------
     // The workgroup's first step gets all six input rows (flag in its entry): the two it would share with a step above are
-    // fetched by waves 0 and 1 into the (still unused) B-ring and transformed into A-ring rows 0 and 1.
+    // fetched by waves 0 and 1 into the (still unused) B-ring and transformed -- CARRY: into two rows further on in the B-ring,
+    // from which the producers make the sums a step above would have handed down (carry_in below); else into A-ring rows 0 and 1.
     const bool six = (__builtin_amdgcn_readfirstlane(e_first.y) >> 25) & 1u;
     if (grp == 0) {
         issue_rows(e_first, 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});
@@ -275,7 +294,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
                 int q = i * 64 + lane;
                 q = q < 272 ? q : 271;
                 const int rec = q >> 3, sl = q & 7, par = rec >= 17 ? 1 : 0, hh = rec - 17 * par;
-                glds16_s(base, (unsigned)((2 * hh + par) * 128 + ((sl ^ (hh & 7)) << 4)), lds0 + TW_BRING + wave * 5120 + i * 1024);
+                glds16_s(base, (unsigned)((2 * hh + par) * 128 + ((sl ^ (hh & 7)) << 4)), lds0 + Lds::SIX_RAW + wave * Lds::SIX_RAWB + i * 1024);
             }
         }
 #pragma unroll
@@ -290,8 +309,8 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
     }
     group_barrier();                   // every A wave's pieces have landed (each waited for its own)
     if (grp == 1) {
-        transform_rows(0, 2);          // (the consumer group fills the A-ring: see its loop)
-        if (six && wave < 2) transform_row(smem + TW_BRING + wave * 5120, wave);
+        transform_rows(0, CARRY ? 0 : 2);          // (the consumer group fills the A-ring: see its loop)
+        if (six && wave < 2) transform_row(smem + Lds::SIX_RAW + wave * Lds::SIX_RAWB, CARRY ? Lds::SIX_ROWS + wave * TW_AROWB : TW_ARING + wave * TW_AROWB);
     }
     group_barrier();
 
@@ -312,7 +331,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
     // rest would run after that k-loop with nothing beside it (profiles/r04_ab_results.txt).  Row 3 completes with the
     // last MFMA: its slices are the caller's, in the next phase.  The order is pinned fragment by fragment
     // (sched_barrier): the read PFF fragments ahead, this fragment's MFMAs, one slice.
-    f32x4 acc[4][4];
+    f32x4 acc[CARRY ? 6 : 4][4];        // (CARRY, producers: rows 4 and 5 are the next step's rows 0 and 1 so far)
     // the first PFF fragments of a k-loop (all of window row 0) into `pre`: TW_PRE_BAR reads them in front of the barrier
     [[maybe_unused]] auto prefetch = [&](auto ring_tag, int base_pos, auto& pre) __attribute__((always_inline)) {
         constexpr bool BR = decltype(ring_tag)::value;
@@ -369,6 +388,67 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
         });
     };
 
+    // The producers' k-loop with the carry: the 32 fragments f = (r * 2 + ch) * 4 + j of the step's four NEW rows (window rows
+    // R = r + 2, A-ring row r); fragment (R, j, ch) feeds output rows n = R - dy (dy = 0..2) of the SIX rows n = 0..5, three MFMAs
+    // each.  Rows 0 and 1 start from what the step above left in rows 4 and 5 (dy = 0 / dy = 0, 1: the first MFMA of either reads
+    // acc[n + 4] and writes acc[n]), rows 4 and 5 are left partial.  For every output: dy ascending, ch 0 then ch 1, the bias as
+    // M1's start value -- the order of kloop() above.
+    [[maybe_unused]] auto kloop_carry = [&]() __attribute__((always_inline)) {
+        if constexpr (CARRY) {
+        constexpr int JS = TW_AROWB / 4, CS = TW_AROWB / 8;
+        constexpr int PFF = PFF_A, NFRAG = 32, RQ = PFF + 1;
+        const char* const r0 = smem + TW_ARING + vlane_c;
+        auto read_f = [&](int f) __attribute__((always_inline)) -> half8 {
+            return *(const half8*)(r0 + (f >> 3) * TW_AROWB + (f & 3) * JS + ((f >> 2) & 1) * CS);
+        };
+        half8 bq[RQ];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int f = 0; f < PFF; ++f) bq[f] = read_f(f);
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<NFRAG>([&](auto fc) __attribute__((always_inline)) {
+            constexpr int f = decltype(fc)::value;
+            if constexpr (f + PFF < NFRAG) bq[(f + PFF) % RQ] = read_f(f + PFF);
+            constexpr int R = (f >> 3) + 2, ch = (f >> 2) & 1, j = f & 3;
+            const half8 b = bq[f % RQ];
+            static_for<6>([&](auto nc) __attribute__((always_inline)) {
+                constexpr int n = decltype(nc)::value, dy = R - n;
+                if constexpr (dy >= 0 && dy <= 2) {
+                    constexpr bool first = dy == 0 && ch == 0;
+                    constexpr bool handed = R == 2 && ch == 0 && n < 2;       // the step's first MFMA of a carried row
+                    acc[n][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[(j * 3 + dy) * 2 + ch], b,
+                                                                       first ? (j == 1 ? bias4 : zero4) : acc[handed ? n + 4 : n][j], 0, 0, 0);
+                }
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        }
+    };
+    // What a step above would have left in rows 4 and 5, from the two extra rows of a workgroup's first step (R = 0, 1).
+    [[maybe_unused]] auto carry_in = [&]() __attribute__((always_inline)) {
+        if constexpr (CARRY) {
+        constexpr int JS = TW_AROWB / 4, CS = TW_AROWB / 8;
+        const char* const r0 = smem + Lds::SIX_ROWS + vlane_c;
+        static_for<2>([&](auto rc) __attribute__((always_inline)) {
+            constexpr int R = decltype(rc)::value;
+            half8 b[8];
+#pragma unroll
+            for (int f = 0; f < 8; ++f) b[f] = *(const half8*)(r0 + R * TW_AROWB + (f & 3) * JS + (f >> 2) * CS);
+            static_for<8>([&](auto fc) __attribute__((always_inline)) {
+                constexpr int ch = decltype(fc)::value >> 2, j = decltype(fc)::value & 3;
+                static_for<2>([&](auto nc) __attribute__((always_inline)) {
+                    constexpr int n = decltype(nc)::value, dy = R - n;
+                    if constexpr (dy >= 0) {
+                        constexpr bool first = dy == 0 && ch == 0;
+                        acc[n + 4][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[(j * 3 + dy) * 2 + ch], b[decltype(fc)::value],
+                                                                               first ? (j == 1 ? bias4 : zero4) : acc[n + 4][j], 0, 0, 0);
+                    }
+                });
+            });
+        });
+        }
+    };
+
     // The slices 0..3 of a row's epilogue, the same for both groups: output transform and PReLU of one block row (the bias
     // is already in M1) -> the pair's two pixels as packed fp16, 4 channels each.  On float pairs: v_pk_add_f32 / v_pk_mul_f32;
     // differences as fma(x, -1, y): one rounding like y - x, and it stays a packed instruction (y - x on float pairs is
@@ -419,8 +499,14 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
         // entries fetched one iteration ahead through the scalar cache: e_own = masks of step it, e_dma = rows of step it + 2 (where the
         // producers would issue pieces of them: they issue none)
         uint4 e_own = load_a(0);
-        int a6 = 0;                    // (4 * it) mod 6: A-ring position of the step's first input row
+        [[maybe_unused]] int a6 = 0;   // (no carry) (4 * it) mod 6: A-ring position of the step's first input row
         int b10 = 0;                   // (4 * it) mod 10: B-ring position of the block written in iteration it
+        if constexpr (CARRY) {
+            // a segment start's carried sums are garbage like its two shared rows were (zeros at a workgroup's start)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[4][j] = acc[5][j] = zero4;
+            if (six) carry_in();
+        }
         // lane (p, cg) writes units of channel octet 2 wave + (cg >> 1): even cg V0 and V1, odd cg V2 and V3; the lanes of
         // pair 15 (the B-ring holds 15 pairs per plane) write to a spare unit behind the parameters instead: no exec mask
         const int cg = lane >> 4, p = lane & 15;
@@ -431,7 +517,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
         const unsigned w64 = (unsigned)(TW_BRING + (wave >> 1) * (TW_BROWB / 8) + p * 64 + ((oo ^ ((p >> 1) & 3)) << 4) + 8 * (cg & 1));
         const unsigned wrow = p < 15 ? (unsigned)TW_BROWB : 0u;      // (pair 15: every row and both units to the same spare place)
         const unsigned wj = p < 15 ? (unsigned)(TW_BROWB / 4) : 0u;
-        half8 pre[PFF_A];
+        [[maybe_unused]] half8 pre[PFF_A];
         for (int it = 0; it < niter; ++it) {
             TW_STAMP(0);
             // what the epilogue of a step needs: the masks of a step at its plane's edge, and where its block lies in the B-ring
@@ -500,7 +586,8 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
                 __builtin_amdgcn_s_setprio(TW_PRIO_KA);
                 // steps that touch their plane's edge (uniform, few) mask what lies outside
                 auto no_hook = [](auto) __attribute__((always_inline)) {};
-                kloop(std::false_type{}, a6, [&](auto nc, auto kc) __attribute__((always_inline)) { slice(st2[0], std::false_type{}, nc, kc); }, no_hook, pre);
+                if constexpr (CARRY) kloop_carry();
+                else kloop(std::false_type{}, a6, [&](auto nc, auto kc) __attribute__((always_inline)) { slice(st2[0], std::false_type{}, nc, kc); }, no_hook, pre);
                 __builtin_amdgcn_s_setprio(TW_PRIO_EA);
             }
             // the rows of step it + 1 (issued one iteration ago) are complete once only this phase's pieces are outstanding
@@ -521,14 +608,14 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
             }
             e_own = load_a(it + 1 < nsteps ? it + 1 : nsteps - 1);
             TW_STAMP(3);
-            a6 = a6 + 4 >= TW_AROWS ? a6 + 4 - TW_AROWS : a6 + 4;
+            if constexpr (!CARRY) a6 = a6 + 4 >= TW_AROWS ? a6 + 4 - TW_AROWS : a6 + 4;
             group_barrier();
             b10 = b10 + 4 >= TW_BROWS ? b10 + 4 - TW_BROWS : b10 + 4;
         }
     } else {
         // ---- group B: step s: k-loop in iteration s + 1 (phase Y), its rows 0..2 stored from inside that k-loop, row 3 in
         // phase X of iteration s + 2.  e_k = the entry of the step whose k-loop runs in this iteration, e_3 = of the one before.
-        int a6 = 0, b10 = 0;
+        int a6 = 0, b10 = 0;           // (CARRY: the A-ring is the step's four rows, a6 stays 0)
         uint4 e_k = make_uint4(0, 0, 0, 0), e_3 = make_uint4(0, 0, 0, 0);
         const int cg = lane >> 4, p = lane & 15;
         const int col = 2 * p + (cg & 1);
@@ -624,7 +711,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
             // nothing is left behind the k-loop, when the LDS store path would be all that moves.
             [[maybe_unused]] auto raw_rows = [&]() __attribute__((always_inline)) {
                 if (it + 1 < nsteps) {
-                    int pos0 = a6 + 4 + 2;         // step it + 1's new rows follow its two shared ones
+                    int pos0 = CARRY ? 0 : a6 + 4 + 2;         // step it + 1's new rows follow its two shared ones
                     pos0 = pos0 >= TW_AROWS ? pos0 - TW_AROWS : pos0;
                     transform_rows((it + 1) & 1, pos0);
                 }
@@ -632,7 +719,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
             unsigned solo = (unsigned)__builtin_amdgcn_readfirstlane((int)((kact ^ 1u) & (it + 1 < nsteps ? 1u : 0u)));
             asm volatile("" : "+s"(solo));         // (opaque: seen as the k-loop's `else`, hipcc lays the two out as one region and spills 115 registers)
             if (solo) {                            // (no k-loop to hide it in: the first iteration, a segment's fill step) -- half a
-                int pos = a6 + 4 + 2 + wave;       // row at a time: the 32 registers of transform_row() do not fit beside the hook's
+                int pos = CARRY ? wave : a6 + 4 + 2 + wave;       // row at a time: the 32 registers of transform_row() do not fit beside the hook's
                 pos = pos >= 2 * TW_AROWS ? pos - 2 * TW_AROWS : pos >= TW_AROWS ? pos - TW_AROWS : pos;
                 const char* const rr = smem + TW_RAW + ((it + 1) & 1) * TW_RAWSLOTB + wave * TW_RAWROWB;
                 transform_half(rr, pos, 0);
@@ -647,7 +734,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
                 // ds_read_b128 (d0..d3 of one channel half) at fragment F0, then one V row (four v_pk_add_f16, one ds_write_b128) every
                 // STRIDE fragments from F0 + GAP on -- an LDS round trip later --, then the other half.  Past the frame's last step
                 // it transforms whatever the look-ahead DMA brought into rows nobody reads.
-                int rpos = a6 + 4 + 2 + wave;
+                int rpos = CARRY ? wave : a6 + 4 + 2 + wave;
                 rpos = rpos >= 2 * TW_AROWS ? rpos - 2 * TW_AROWS : rpos >= TW_AROWS ? rpos - TW_AROWS : rpos;
                 const char* const rrow = smem + TW_RAW + ((it + 1) & 1) * TW_RAWSLOTB + wave * TW_RAWROWB;
                 char* const vrow = smem + TW_ARING + rpos * TW_AROWB + vlane_c;
@@ -672,7 +759,7 @@ __global__ __launch_bounds__(512, 2) UVA_NO_PK_F32 void trunkw_kernel(TrunkwArgs
             e_3 = e_k;
             TW_STAMP(3);
             group_barrier();
-            a6 = a6 + 4 >= TW_AROWS ? a6 + 4 - TW_AROWS : a6 + 4;
+            if constexpr (!CARRY) a6 = a6 + 4 >= TW_AROWS ? a6 + 4 - TW_AROWS : a6 + 4;
             b10 = b10 + 4 >= TW_BROWS ? b10 + 4 - TW_BROWS : b10 + 4;
         }
     }
