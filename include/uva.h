@@ -58,7 +58,10 @@ extern "C" {
                                    uva_debug_png_deflate_host16, uva_png_decode_bgr16, uva_net_submit_u16_png (additive: every 8-bit PNG
                                    entry keeps its signature and its bytes)
                                15 + 16-bit denoise: + uva_denoise_u16, uva_denoise_u16_device, uva_debug_denoise16_stage (additive: the
-                                   8-bit stage keeps its kernels and its bytes) */
+                                   8-bit stage keeps its kernels and its bytes)
+                               15 + deinterlacing: + uva_deint_check, uva_deint_frames, uva_deint_frames_device, uva_debug_deint_frames,
+                                   uva_debug_deint_host, uva_deint_create, uva_deint_push, uva_deint_reset, uva_deint_destroy,
+                                   UVA_DEINT_* (additive: nothing runs unless asked for) */
 
 typedef struct uva_net uva_net;
 
@@ -330,6 +333,49 @@ int uva_pix_window_device(int device, const void* d_in, int fmt, int src_h, int 
  * switch it off (the default).  Setting it forgets the kept frame of uva_net_set_skip_repeats and zeroes its counters: the
  * comparison is between uploaded windows.  Host only: works with no GPU present. */
 int uva_net_set_input_window(uva_net* net, int src_h, int src_w, int x, int y);
+
+/* ---- deinterlacing (csrc/uva_deint.hip, csrc/uva_deint_host.cpp) ---------------------------------
+ * DVD, broadcast and tape material is interlaced: the rows of a frame alternate between two instants, and every moving edge is a
+ * comb that a net would sharpen.  These entries are yadif's spatio-temporal rule restated (its definition for this project:
+ * tests/yadif_ref.py; parity with ffmpeg's yadif filter is unpinned) on frames of any UVA_PIX_* format, exact in integers, per
+ * component plane: the interleaved chroma of nv12 / p010le is two planes, a packed BGR frame three; the chroma rows of a 4:2:0
+ * frame alternate fields as luma rows do.  Samples are code values as the input conversion reads them (bytes; word >> 6 for
+ * p010le; word & 1023 for yuv420p10le / yuv422p10le; whole words for bgr48le).
+ * A frame `cur` between `prev` and `next` has two outputs.  A keeps the rows of cur's first field byte for byte (bits the
+ * converter ignores too) and interpolates the others between prev and cur; B keeps the second field's rows and interpolates the
+ * others between cur and next.  Interpolated samples are clean code values in the format's placement.  The first field is the
+ * even rows (top field first) unless UVA_DEINT_BFF is set.  Without UVA_DEINT_FIELD only A exists (one frame out per frame in);
+ * with it A and B (two out per frame in, twice the frame rate). */
+#define UVA_DEINT_FIELD 1
+#define UVA_DEINT_BFF 2
+typedef struct uva_deint uva_deint;
+/* Host only, no GPU needed: are h x w frames of fmt with these flags ones the entries below take?  Refused, never rounded, with
+ * uva_last_error set: an unknown format, unknown flag bits, a size below 1 or above 2^28 pixels, h < 4 (a 4:2:0 chroma plane
+ * then has fewer than two rows).  Any w >= 1 is taken. */
+int uva_deint_check(int fmt, int h, int w, int flags);
+/* One frame, stateless: out_a / out_b <- the outputs A / B of `cur` on HIP device `device`.  Host to host, synchronous.  prev /
+ * next NULL mean cur (the first / last frame of a stream).  Either output may be NULL, not both; out_b without UVA_DEINT_FIELD is
+ * refused.  Everything is refused before a GPU is looked for. */
+int uva_deint_frames(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a,
+                     void* out_b);
+/* The same between frames in `device`'s HBM, all complete and at 16-byte aligned addresses.  Synchronous. */
+int uva_deint_frames_device(int device, const void* d_prev, const void* d_cur, const void* d_next, int fmt, int h, int w, int flags,
+                            void* d_out_a, void* d_out_b);
+/* Test hook: uva_deint_frames on a grid of at most max_groups workgroups (0: the kernel's own bound), so that a small frame
+ * exercises the kernel's grid-stride walk. */
+int uva_debug_deint_frames(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a,
+                           void* out_b, int max_groups);
+/* Test hook, host only, no GPU needed: uva_deint_frames by the scalar restatement of the rule in csrc/uva_deint_host.cpp. */
+int uva_debug_deint_host(const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b);
+/* A stream, stateful, so that every frame is uploaded once: the handle keeps three frames in `device`'s HBM and a stream of its
+ * own.  uva_deint_push uploads `frame` and produces the outputs of the frame pushed BEFORE it (which now has its next): *produced
+ * is 0 after the first push, else 1 (A in out_a) or, with UVA_DEINT_FIELD, 2 (A in out_a, B in out_b); it returns when they are
+ * in out_a / out_b.  frame NULL flushes: the last frame's outputs with next = cur (0 when nothing was pushed), after which the
+ * handle is as after uva_deint_reset, ready for another stream.  out_a is needed always, out_b with UVA_DEINT_FIELD. */
+int uva_deint_create(int device, int fmt, int h, int w, int flags, uva_deint** out);
+int uva_deint_push(uva_deint* d, const void* frame, void* out_a, void* out_b, int* produced);
+int uva_deint_reset(uva_deint* d);
+void uva_deint_destroy(uva_deint* d);
 
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 

@@ -42,6 +42,9 @@ OPTIONAL_SYMBOLS += ["uva_denoise_u16", "uva_denoise_u16_device", "uva_debug_den
 # Net.set_input_window and rawvideo's --crop / --cropdetect ask)
 OPTIONAL_SYMBOLS += ["uva_crop_sums", "uva_crop_sums_device", "uva_debug_crop_sums", "uva_crop_bounds", "uva_crop_rect",
                      "uva_pix_window_check", "uva_pix_window", "uva_pix_window_device", "uva_net_set_input_window"]
+# 15 + deinterlacing (additive and optional in the same way: ncnn.deint_frames, ncnn.Deinterlacer and rawvideo's --deinterlace ask)
+OPTIONAL_SYMBOLS += ["uva_deint_check", "uva_deint_frames", "uva_deint_frames_device", "uva_debug_deint_frames", "uva_debug_deint_host",
+                     "uva_deint_create", "uva_deint_push", "uva_deint_reset", "uva_deint_destroy"]
 SYMBOLS += OPTIONAL_SYMBOLS
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -129,6 +132,15 @@ def load():
     decl("uva_pix_window", [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p])
     decl("uva_pix_window_device", [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p])
     decl("uva_net_set_input_window", [c_p, c_i, c_i, c_i, c_i])
+    decl("uva_deint_check", [c_i, c_i, c_i, c_i])
+    decl("uva_deint_frames", [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p])
+    decl("uva_deint_frames_device", [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p])
+    decl("uva_debug_deint_frames", [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i])
+    decl("uva_debug_deint_host", [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p])
+    decl("uva_deint_create", [c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_p)])
+    decl("uva_deint_push", [c_p, c_p, c_p, c_p, pi])
+    decl("uva_deint_reset", [c_p])
+    decl("uva_deint_destroy", [c_p], "void")
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

@@ -15,6 +15,7 @@
 #include "uva_plan.h"
 #include "uva_repeat.h"
 #include "uva_crop.h"
+#include "uva_deint.h"
 #include "uva_resize.h"
 #include "uva_png.hip.h"
 #include "uva_wino.h"
@@ -3518,6 +3519,173 @@ int uva_net_set_input_window(uva_net* n, int src_h, int src_w, int x, int y)
     n->rep.valid = false;
     n->rep.submitted = n->rep.skipped = 0;
     return 0;
+}
+
+// ---- deinterlacing (csrc/uva_deint.hip, csrc/uva_deint_host.cpp) ------------------------------------
+struct uva_deint {
+    int device = 0, fmt = 0, h = 0, w = 0, flags = 0;
+    size_t bytes = 0;
+    hipStream_t stream = nullptr;
+    uint8_t* d_frame[3] = {nullptr, nullptr, nullptr};     // frame k of the stream lies in d_frame[k % 3]
+    uint8_t* d_out[2] = {nullptr, nullptr};                // A, and B with UVA_DEINT_FIELD
+    long long pushed = 0;                                  // frames since the last reset
+};
+
+namespace {
+// everything the stateless entries refuse, before a GPU is looked for
+int deint_frames_check(const void* cur, int fmt, int h, int w, int flags, const void* out_a, const void* out_b)
+{
+    if (const char* e = deint_error(fmt, h, w, flags)) return fail(e);
+    if (!cur) return fail("null frame pointer");
+    if (!out_a && !out_b) return fail("deinterlace: neither output A nor output B is asked for");
+    if (out_b && !(flags & DEINT_FIELD)) return fail("deinterlace: output B exists with UVA_DEINT_FIELD only");
+    return 0;
+}
+
+int deint_frames_host(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b,
+                      int max_groups)
+{
+    if (deint_frames_check(cur, fmt, h, w, flags, out_a, out_b)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = deint_format(fmt, h, w).frame_bytes, slot = (bytes + 15) & ~(size_t)15;
+    // prev, cur, next in d_in; A, B in d_out (every frame at a multiple of 16 bytes)
+    if (pix_grow(*c, &c->d_in, &c->in_cap, 3 * slot) || pix_grow(*c, &c->d_out, &c->out_cap, 2 * slot)) return 1;
+    const uint8_t *d_cur = c->d_in + slot, *d_prev = d_cur, *d_next = d_cur;
+    HIP_TRY(hipMemcpyAsync(c->d_in + slot, cur, bytes, hipMemcpyHostToDevice, c->stream));
+    if (prev && prev != cur) {
+        HIP_TRY(hipMemcpyAsync(c->d_in, prev, bytes, hipMemcpyHostToDevice, c->stream));
+        d_prev = c->d_in;
+    }
+    if (next && next != cur) {
+        HIP_TRY(hipMemcpyAsync(c->d_in + 2 * slot, next, bytes, hipMemcpyHostToDevice, c->stream));
+        d_next = c->d_in + 2 * slot;
+    }
+    HIP_TRY(launch_deint(c->stream, d_prev, d_cur, d_next, fmt, h, w, flags, out_a ? c->d_out : nullptr, out_b ? c->d_out + slot : nullptr,
+                         max_groups));
+    if (out_a) HIP_TRY(hipMemcpyAsync(out_a, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_b) HIP_TRY(hipMemcpyAsync(out_b, c->d_out + slot, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the outputs of frame `k` of the handle's stream (prev / next: k -+ 1, or k itself at an end), downloaded and waited for
+int deint_emit(uva_deint* d, long long k, bool has_next, void* out_a, void* out_b, int* produced)
+{
+    const uint8_t* cur = d->d_frame[k % 3];
+    const uint8_t* prev = k > 0 ? d->d_frame[(k - 1) % 3] : cur;
+    const uint8_t* next = has_next ? d->d_frame[(k + 1) % 3] : cur;
+    const bool field = (d->flags & DEINT_FIELD) != 0;
+    HIP_TRY(launch_deint(d->stream, prev, cur, next, d->fmt, d->h, d->w, d->flags, d->d_out[0], field ? d->d_out[1] : nullptr, 0));
+    HIP_TRY(hipMemcpyAsync(out_a, d->d_out[0], d->bytes, hipMemcpyDeviceToHost, d->stream));
+    if (field) HIP_TRY(hipMemcpyAsync(out_b, d->d_out[1], d->bytes, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    *produced = field ? 2 : 1;
+    return 0;
+}
+}  // namespace
+
+int uva_deint_check(int fmt, int h, int w, int flags)
+{
+    if (const char* e = deint_error(fmt, h, w, flags)) return fail(e);
+    return 0;
+}
+
+int uva_deint_frames(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b)
+{
+    return deint_frames_host(device, prev, cur, next, fmt, h, w, flags, out_a, out_b, 0);
+}
+
+int uva_debug_deint_frames(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a,
+                           void* out_b, int max_groups)
+{
+    if (max_groups < 0) return fail("uva_debug_deint_frames: max_groups is 0 (the kernel's own bound) or a number of workgroups");
+    return deint_frames_host(device, prev, cur, next, fmt, h, w, flags, out_a, out_b, max_groups);
+}
+
+int uva_deint_frames_device(int device, const void* d_prev, const void* d_cur, const void* d_next, int fmt, int h, int w, int flags,
+                            void* d_out_a, void* d_out_b)
+{
+    if (deint_frames_check(d_cur, fmt, h, w, flags, d_out_a, d_out_b)) return 1;
+    if ((((uintptr_t)d_prev | (uintptr_t)d_cur | (uintptr_t)d_next | (uintptr_t)d_out_a | (uintptr_t)d_out_b) & 15) != 0)
+        return fail("uva_deint_frames_device: the frames must start at 16-byte aligned addresses");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    HIP_TRY(launch_deint(c->stream, d_prev ? d_prev : d_cur, d_cur, d_next ? d_next : d_cur, fmt, h, w, flags, d_out_a, d_out_b, 0));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_debug_deint_host(const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b)
+{
+    if (deint_frames_check(cur, fmt, h, w, flags, out_a, out_b)) return 1;
+    deint_host((const uint8_t*)prev, (const uint8_t*)cur, (const uint8_t*)next, fmt, h, w, flags, (uint8_t*)out_a, (uint8_t*)out_b);
+    return 0;
+}
+
+int uva_deint_create(int device, int fmt, int h, int w, int flags, uva_deint** out)
+{
+    if (!out) return fail("uva_deint_create: null pointer");
+    *out = nullptr;
+    if (const char* e = deint_error(fmt, h, w, flags)) return fail(e);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail("no HIP device available: libuva has no CPU path");
+    if (device < 0 || device >= count) return fail("HIP device " + std::to_string(device) + " does not exist");
+    HIP_TRY(hipSetDevice(device));
+    uva_deint* d = new uva_deint;
+    d->device = device; d->fmt = fmt; d->h = h; d->w = w; d->flags = flags;
+    d->bytes = deint_format(fmt, h, w).frame_bytes;
+    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipMalloc((void**)&d->d_frame[k], d->bytes);
+    for (int k = 0; k < ((flags & DEINT_FIELD) ? 2 : 1) && e == hipSuccess; ++k) e = hipMalloc((void**)&d->d_out[k], d->bytes);
+    if (e != hipSuccess) {
+        uva_deint_destroy(d);
+        return fail(std::string("uva_deint_create: ") + hipGetErrorString(e));
+    }
+    *out = d;
+    return 0;
+}
+
+int uva_deint_push(uva_deint* d, const void* frame, void* out_a, void* out_b, int* produced)
+{
+    if (!d || !produced) return fail("uva_deint_push: null pointer");
+    *produced = 0;
+    if (!out_a || ((d->flags & DEINT_FIELD) && !out_b)) return fail("uva_deint_push: null output frame");
+    HIP_TRY(hipSetDevice(d->device));
+    if (!frame) {                                   // flush: the last frame has no next
+        const long long n = d->pushed;
+        d->pushed = 0;
+        return n ? deint_emit(d, n - 1, false, out_a, out_b, produced) : 0;
+    }
+    // (frame k - 2's slot is free: the outputs of frame k - 1, the last to read it, were waited for)
+    const long long k = d->pushed;
+    HIP_TRY(hipMemcpyAsync(d->d_frame[k % 3], frame, d->bytes, hipMemcpyHostToDevice, d->stream));
+    d->pushed = k + 1;
+    if (k == 0) {
+        HIP_TRY(hipStreamSynchronize(d->stream));   // (`frame` is the caller's again when the call returns)
+        return 0;
+    }
+    return deint_emit(d, k - 1, true, out_a, out_b, produced);
+}
+
+int uva_deint_reset(uva_deint* d)
+{
+    if (!d) return fail("uva_deint_reset: null pointer");
+    d->pushed = 0;
+    return 0;
+}
+
+void uva_deint_destroy(uva_deint* d)
+{
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    for (uint8_t* p : {d->d_frame[0], d->d_frame[1], d->d_frame[2], d->d_out[0], d->d_out[1]})
+        if (p) (void)hipFree(p);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
 }
 
 size_t uva_png_workspace_bytes(int h, int w)

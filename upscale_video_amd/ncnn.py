@@ -417,6 +417,127 @@ class CropDetector:
         return crop_rect(self.state, self.round)
 
 
+# ---- deinterlacing (include/uva.h uva_deint_*) ---------------------------------------------------------
+DEINT_MODES = {"frame": 0, "field": 1}               # UVA_DEINT_FIELD: outputs A and B, twice the frame rate
+FIELD_ORDERS = {"tff": 0, "bff": 2}                  # UVA_DEINT_BFF
+
+
+def deint_flags(mode="frame", field_order="tff"):
+    """the C ABI's flags argument: UVA_DEINT_FIELD | UVA_DEINT_BFF"""
+    if mode not in DEINT_MODES:
+        raise ValueError("unknown deinterlace mode %r (%s)" % (mode, ", ".join(DEINT_MODES)))
+    if field_order not in FIELD_ORDERS:
+        raise ValueError("unknown field order %r (%s)" % (field_order, ", ".join(FIELD_ORDERS)))
+    return DEINT_MODES[mode] | FIELD_ORDERS[field_order]
+
+
+def deint_check(fmt, h, w, mode="frame", field_order="tff"):
+    """Raises UvaError with the reason if the library refuses to deinterlace h x w frames of `fmt` (include/uva.h
+    uva_deint_check; no GPU needed)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    _lib.check(_crop_lib("uva_deint_check").uva_deint_check(PIX_FORMATS_ALL[fmt], int(h), int(w), deint_flags(mode, field_order)))
+
+
+def deint_frames(prev, cur, nxt, fmt, h, w, mode="frame", field_order="tff", gpu=0, device=False, host=False, max_groups=None,
+                 out_a=None, out_b=None):
+    """One dense h x w frame `cur` of `fmt` deinterlaced between `prev` and `nxt` (None: cur, the ends of a stream) by yadif's
+    rule on HIP device `gpu` (include/uva.h uva_deint_frames) -> (A, B): A keeps cur's first field and
+    interpolates the other rows, B (mode="field" only, else None) keeps the second.  Flat u8 arrays of the frame's bytes.
+    device=True: the three frames and out_a / out_b (out_b: mode="field") are raw device pointers (ints) of frames in that
+    GPU's HBM (uva_deint_frames_device); returns None.  host=True: the library's scalar restatement, no GPU
+    (uva_debug_deint_host).  max_groups: the test hook uva_debug_deint_frames (a grid of at most that many workgroups)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    flags = deint_flags(mode, field_order)
+    f, h, w = PIX_FORMATS_ALL[fmt], int(h), int(w)
+    if device:
+        ptr = lambda v: None if v is None else ctypes.c_void_p(int(v))          # noqa: E731
+        _lib.check(_crop_lib("uva_deint_frames_device").uva_deint_frames_device(int(gpu), ptr(prev), ptr(cur), ptr(nxt), f, h, w, flags,
+                                                                                ptr(out_a), ptr(out_b)))
+        return None
+    _lib.check(_crop_lib("uva_deint_check").uva_deint_check(f, h, w, flags))
+    frames = [None if v is None else _pix_frame(v, fmt, h, w, what) for v, what in ((prev, "prev"), (cur, "cur"), (nxt, "next"))]
+    p, c, n = (None if v is None else v.ctypes.data for v in frames)
+    nb = pix_frame_bytes(fmt, h, w)
+    a = np.empty(nb, np.uint8) if out_a is None else out_a
+    b = (np.empty(nb, np.uint8) if out_b is None else out_b) if mode == "field" else None
+    for o in (a, b):
+        if o is not None and (not o.flags.c_contiguous or o.nbytes != nb):
+            raise ValueError("an output must be a C-contiguous buffer of %d bytes" % nb)
+    pb = None if b is None else b.ctypes.data
+    if host:
+        _lib.check(_crop_lib("uva_debug_deint_host").uva_debug_deint_host(p, c, n, f, h, w, flags, a.ctypes.data, pb))
+    elif max_groups is None:
+        _lib.check(_crop_lib("uva_deint_frames").uva_deint_frames(int(gpu), p, c, n, f, h, w, flags, a.ctypes.data, pb))
+    else:
+        _lib.check(_crop_lib("uva_debug_deint_frames").uva_debug_deint_frames(int(gpu), p, c, n, f, h, w, flags, a.ctypes.data, pb,
+                                                                              int(max_groups)))
+    return a, b
+
+
+class Deinterlacer:
+    """A stream of dense h x w frames of `fmt` deinterlaced on HIP device `gpu`, every frame uploaded once (include/uva.h
+    uva_deint_create / uva_deint_push).  push(frame, outs) hands a frame in and writes the outputs of the
+    frame BEFORE it -- which now has its successor -- into outs[0] (mode "field": outs[0] and outs[1]); it returns how many it
+    wrote: 0 after the first push, then `per_frame` (1, or 2 for "field").  flush(outs) does the same for the last frame and
+    leaves the object ready for another stream; reset() forgets the frames pushed so far."""
+
+    def __init__(self, fmt, h, w, mode="frame", field_order="tff", gpu=0):
+        if fmt not in PIX_FORMATS_ALL:
+            raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+        self.fmt, self.h, self.w, self.mode, self.field_order, self.gpu = fmt, int(h), int(w), mode, field_order, int(gpu)
+        self.flags = deint_flags(mode, field_order)
+        self.per_frame = 2 if mode == "field" else 1
+        self.nbytes = pix_frame_bytes(fmt, self.h, self.w)
+        self._L = _crop_lib("uva_deint_create")
+        self._h = ctypes.c_void_p()
+        _lib.check(self._L.uva_deint_create(self.gpu, PIX_FORMATS_ALL[fmt], self.h, self.w, self.flags, ctypes.byref(self._h)))
+
+    def _push(self, frame, outs):
+        if self._h is None:
+            raise ValueError("the deinterlacer is closed")
+        if len(outs) < self.per_frame:
+            raise ValueError("%d output buffers are needed" % self.per_frame)
+        for o in outs[:self.per_frame]:
+            if not o.flags.c_contiguous or o.nbytes != self.nbytes or not o.flags.writeable:
+                raise ValueError("an output must be a writable C-contiguous buffer of %d bytes" % self.nbytes)
+        n = ctypes.c_int(0)
+        src = None if frame is None else _pix_frame(frame, self.fmt, self.h, self.w, "frame")
+        _lib.check(self._L.uva_deint_push(self._h, None if src is None else src.ctypes.data, outs[0].ctypes.data,
+                                          outs[1].ctypes.data if self.per_frame == 2 else None, ctypes.byref(n)))
+        return n.value
+
+    def push(self, frame, outs):
+        if frame is None:
+            raise ValueError("push() takes a frame; flush() ends the stream")
+        return self._push(frame, outs)
+
+    def flush(self, outs):
+        return self._push(None, outs)
+
+    def reset(self):
+        if self._h is not None:
+            _lib.check(self._L.uva_deint_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._L.uva_deint_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 class Ticket:
     """One frame in flight on the pipelined host route; keeps its buffers alive."""
 

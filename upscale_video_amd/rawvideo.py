@@ -50,6 +50,12 @@ the reference does (get_crop_detect, upscale/upscale_processing.py:137-181: ffmp
 frequent rectangle wins), with the per-frame pass on the GPU; it needs a regular file.  --cropdetect only analyses (pipes too) and
 prints one `crop=W:H:X:Y` line for --crop or for ffmpeg's -vf.
 
+--deinterlace frame|field takes interlaced frames (DVD, broadcast and tape material): every frame read goes
+through yadif's spatio-temporal rule on the GPU in front of everything else, per component plane of the input format and exact
+in integers, so no ffmpeg `yadif` process has to sit in front of the pipe and the nets never see a comb.  frame: one frame out per
+frame in; field: one per field, so twice the frames leave at twice the rate (give the encoder behind the pipe `-r` accordingly).
+--field-order tff|bff names the field that comes first in time (default tff).  --frames counts input frames.
+
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
 conversions run on the net's stream around its kernels); nets in between pass u8 BGR (u16 BGR with --bit-depth 16).  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
@@ -372,6 +378,84 @@ class Lane:
         return self.stages[last].collect()
 
 
+class DeintSpec:
+    """--deinterlace: yadif in front of everything else (ncnn.Deinterlacer).  mode "frame": one frame out
+    per frame in; "field": two, at twice the frame rate.  field_order "tff" / "bff"."""
+
+    def __init__(self, mode="frame", field_order="tff"):
+        ncnn.deint_flags(mode, field_order)              # (checks the names)
+        self.mode, self.field_order = mode, field_order
+        self.per_frame = 2 if mode == "field" else 1
+
+    def open(self, fmt, h, w, gpu):
+        return ncnn.Deinterlacer(fmt, h, w, self.mode, self.field_order, gpu=gpu)
+
+
+def _lane_gpu(spec):
+    """the HIP ordinal of a lane's first stage"""
+    first = spec[0][0]
+    return first[1] if isinstance(first, tuple) else first.device_index
+
+
+def deinterlaced(fin, di, raw, outs_for, max_frames=None, lead=False, trail=False):
+    """The reader with --deinterlace: frames are read from fin into `raw` and pushed through the Deinterlacer `di`; yields the
+    number of deinterlaced frames (0, 1 or 2) that a push or the final flush wrote into the buffers outs_for() named.
+    max_frames counts input frames.  lead: the first frame read is the frame BEFORE the stream's first -- context only, it is
+    read on top of max_frames and its outputs are discarded (yielded as 0).  trail: when max_frames frames were read, one more
+    is read as the last frame's successor instead of flushing, if the input has one."""
+    view = memoryview(raw).cast("B")
+    limit = None if max_frames is None else max_frames + (1 if lead else 0)
+    n_read = n_done = 0                  # frames read; frames whose outputs have been produced
+
+    def produced(k):
+        nonlocal n_done
+        if k:
+            n_done += 1
+            if lead and n_done == 1:
+                return 0
+        return k
+    while limit is None or n_read < limit:
+        if not read_exact(fin, view):
+            break
+        n_read += 1
+        yield produced(di.push(raw, outs_for()))
+    if trail and limit is not None and n_read == limit and read_exact(fin, view):
+        yield produced(di.push(raw, outs_for()))
+        di.reset()
+    else:
+        yield produced(di.flush(outs_for()))
+
+
+class DeintReader:
+    """A byte stream of deinterlaced frames over the input `fin`, for the routes that read frames with read_exact and run no lane
+    (copy_through): readinto() serves the outputs of deinterlaced() one after the other.  max_frames counts input frames."""
+
+    def __init__(self, fin, deint, fmt, h, w, gpu=0, max_frames=None):
+        self._di = deint.open(fmt, h, w, gpu)
+        nb = ncnn.pix_frame_bytes(fmt, h, w)
+        self._outs = [np.empty(nb, np.uint8) for _ in range(deint.per_frame)]
+        self._gen = deinterlaced(fin, self._di, np.empty(nb, np.uint8), lambda: self._outs, max_frames)
+        self._ready, self._pos = [], 0       # frames produced and not served yet; bytes served of the first
+
+    def readinto(self, view):
+        while not self._ready:
+            k = next(self._gen, None)
+            if k is None:
+                return 0
+            self._ready = [memoryview(o) for o in self._outs[:k]]
+        src = self._ready[0]
+        n = min(len(view), len(src) - self._pos)
+        view[:n] = src[self._pos:self._pos + n]
+        self._pos += n
+        if self._pos == len(src):
+            self._ready.pop(0)
+            self._pos = 0
+        return n
+
+    def close(self):
+        self._di.close()
+
+
 def _regular_fd(f):
     """the descriptor behind f if it is a regular file we may write to with os.pwrite, else None"""
     import stat
@@ -382,7 +466,8 @@ def _regular_fd(f):
         return None
 
 
-def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threads=1, pix=None):
+def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threads=1, pix=None, deint=None, deint_lead=False,
+           deint_trail=False):
     """Reads h x w frames of pix.in_fmt (PixFormats; default u8 [h][w][3] bgr24 at both ends) from fin until EOF, pushes each through the nets in order, writes the
     results to fout.  nets_tiles: list of (Net, tile_size) -- one GPU worker -- or a list of such lists,
     one per `-g` entry (duplicates allowed, as in the reference's worker list, README.md:45-61): ONE reader
@@ -390,7 +475,11 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
     independent units), every entry keeps up to PIPE_DEPTH frames in flight per net, and ONE writer puts
     the results out in frame order.  write_threads > 1 and fout a regular file: every result frame is cut into that many pieces
     written with os.pwrite by a small pool (one thread copies ~5 GB/s into the page cache: a 4K frame every 5 ms, half of what
-    one GPU delivers).  Results are frames of pix.out_fmt.  Returns the number of frames written."""
+    one GPU delivers).  Results are frames of pix.out_fmt.  Returns the number of frames written.
+    deint (DeintSpec): every frame read goes through a Deinterlacer on the first lane's GPU first, and what comes out -- 0, 1 or 2
+    frames of the input's format and size -- is dealt to the lanes as frames read from fin are without it; at the end of the
+    input the deinterlacer is flushed.  max_frames counts input frames.  deint_lead / deint_trail: fin starts one frame before
+    the stream / holds the frame after max_frames, as context (stream_segments; deinterlaced())."""
     alloc = alloc or ncnn.pinned_empty
     pix = pix or BGR
     lanes_spec = nets_tiles if nets_tiles and isinstance(nets_tiles[0], list) else [nets_tiles]
@@ -401,6 +490,12 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
     # an input buffer is free again once its frame has left its lane's first stage: at most PIPE_DEPTH per lane are
     # there, plus the one being read into
     ins = [ncnn.pix_empty(pix.in_fmt, src_h, src_w, alloc) for _ in range(nl * PIPE_DEPTH + 2)]
+    if deint is not None:
+        # with the deinterlacer the ring holds ITS outputs: a push writes up to two frames (A and B) before either is handed to
+        # a lane, so beside the PIPE_DEPTH per lane that are in first stages two are being written, plus one to spare as above;
+        # the frame read from the input has a buffer of its own (the push has uploaded it when it returns)
+        ins += [ncnn.pix_empty(pix.in_fmt, src_h, src_w, alloc) for _ in range(deint.per_frame - 1)]
+        raw = ncnn.pix_empty(pix.in_fmt, src_h, src_w, alloc)
 
     # writer thread: the blocking write of frame i overlaps the read of frame i+k and the GPUs
     wq = queue.Queue(maxsize=2)
@@ -460,8 +555,19 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
         written += 1
 
     n_in = 0
+    di = None
     try:
-        while max_frames is None or n_in < max_frames:
+        if deint is not None:
+            di = deint.open(pix.in_fmt, src_h, src_w, _lane_gpu(lanes_spec[0]))
+            for k in deinterlaced(fin, di, raw, lambda: [ins[(n_in + j) % len(ins)] for j in range(deint.per_frame)], max_frames,
+                                  deint_lead, deint_trail):
+                for _ in range(k):
+                    lane = lanes[n_in % nl]
+                    while lane.full():
+                        pop_next()
+                    lane.submit(ins[n_in % len(ins)])
+                    n_in += 1
+        while deint is None and (max_frames is None or n_in < max_frames):
             buf = ins[n_in % len(ins)]
             if not read_exact(fin, memoryview(buf).cast("B")):
                 break
@@ -477,6 +583,8 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
         wt.join()
         if pool is not None:
             pool.shutdown()
+        if di is not None:
+            di.close()
     if werr:
         raise werr[0]
     fout.flush()
@@ -552,7 +660,7 @@ class MappedSegment:
 
 
 def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames=None, alloc=None, opener=open, mapped=None,
-                    write_threads=1, pix=None):
+                    write_threads=1, pix=None, deint=None):
     """The same frames -> the same bytes as stream(), for regular FILES, with NO shared serial copy: one contiguous segment of
     frames per `-g` entry (the reference's batches, upscale/upscale_processing.py:923-948, are such segments), and every entry
     runs its own stream() -- its own reader, its own pipelined chain of nets, its own writer thread -- on its own file handles.
@@ -564,8 +672,14 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
     One reader and one writer thread copy ~10 GB/s each, two or three GPUs' worth of 1080p -> 4K frames; N independent pairs
     scale with the entries.  A worker that fails takes the output with it: the file(s) this call created are removed (a
     full-size file of zeros and holes is worse than none).  pix: PixFormats of the two ends (default bgr24).  Returns the number
-    of frames written."""
+    of frames written.
+    deint (DeintSpec): every segment deinterlaces its own frames (stream(deint=...)).  A segment of ONE input file that does not
+    begin the file reads the frame before its first as context, its outputs discarded, and one that does not end the stream
+    reads the frame after its last instead of flushing: the bytes are those of a single lane.  Output counts, offsets and the
+    file's size are in output frames, twice the input frames for mode "field".  One input file per entry: every file is a
+    stream of its own."""
     pix = pix or BGR
+    per = deint.per_frame if deint is not None else 1          # output frames per input frame
     net_h, net_w = pix.net_size(h, w)      # (pix.crop: the lanes work on a window of the h x w frames in the file)
     fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(*pix.result_size(net_h * scale_total, net_w * scale_total), out=True)
     nl = len(lanes_spec)
@@ -600,7 +714,9 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
             counts.append(c)
         in_first = [0] * nl
         total = sum(counts)
-    out_first = [0] * nl if outs is not None else [sum(counts[:k]) for k in range(nl)]
+    in_total = total                                            # input frames of the stream
+    out_first = [0] * nl if outs is not None else [sum(counts[:k]) * per for k in range(nl)]
+    total *= per                                                # (from here on: output frames)
     created = [o for o in (outs if outs is not None else [out_path]) if not os.path.exists(o)]
     if outs is None:
         with opener(out_path, "wb") as f:       # the output exists at its full size before anybody writes into it
@@ -629,16 +745,22 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
                 if outs is not None:
                     opener(outs[k], "wb").close()
                 return
+            kw = {}
+            lead = False
+            if deint is not None:
+                # context frames: the one before the segment's first and the one after its last, where the stream has them
+                lead = ins is None and in_first[k] > 0
+                kw = dict(deint=deint, deint_lead=lead, deint_trail=ins is None and in_first[k] + counts[k] < in_total)
             with opener(in_path if ins is None else ins[k], "rb") as fin:
-                fin.seek(in_first[k] * fb_in)
+                fin.seek((in_first[k] - (1 if lead else 0)) * fb_in)
                 if outs is None and mapped:
-                    with MappedSegment(opener(out_path, "r+b"), out_first[k] * fb_out, counts[k] * fb_out) as fout:
-                        done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], pix=pix)
+                    with MappedSegment(opener(out_path, "r+b"), out_first[k] * fb_out, counts[k] * per * fb_out) as fout:
+                        done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], pix=pix, **kw)
                 else:
                     with opener(out_path if outs is None else outs[k], "r+b" if outs is None else "wb") as fout:
                         fout.seek(out_first[k] * fb_out)
                         done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], write_threads=write_threads,
-                                         pix=pix)
+                                         pix=pix, **kw)
         except Exception as e:  # noqa: BLE001
             errs.append(e)
     threads = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(nl)]
@@ -754,12 +876,19 @@ class PipeSink:
             time.sleep(0.001)
 
 
-def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0):
+def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0, deint=None):
     """`-s 1` without `-m a`: the reference renames the frames, nothing is computed (:924-929).  Formats that differ at the two
     ends (pix): every frame is converted once on HIP device `gpu` (include/uva.h uva_pix_convert; with pix.bit_depth 16
     uva_pix_convert16, through u16 BGR).  With pix.out_size every frame is converted to BGR, resampled (include/uva.h uva_resize)
-    and converted to the output format at the new size."""
+    and converted to the output format at the new size.  deint (DeintSpec): the frames are deinterlaced first, on the same
+    device (DeintReader; max_frames counts input frames) -- with equal formats at both ends a deinterlace-only run."""
     pix = pix or BGR
+    if deint is not None:
+        reader = DeintReader(fin, deint, pix.in_fmt, h, w, gpu=gpu, max_frames=max_frames)
+        try:
+            return copy_through(reader, fout, h, w, None, pix=pix, gpu=gpu)
+        finally:
+            reader.close()
     src_h, src_w = h, w
     h, w = pix.net_size(h, w)              # (pix.crop: every frame is cut first, ncnn.pix_window)
     if pix.out_size is not None and pix.out_size != (h, w):
@@ -983,9 +1112,27 @@ def main(argv=None):
                          "cropdetect's default 24)")
     ap.add_argument("--crop-round", type=int, default=16, metavar="R",
                     help="--crop auto / --cropdetect: width and height are rounded down to a multiple of R (cropdetect's default 16)")
+    ap.add_argument("--deinterlace", default=None, metavar="frame|field",
+                    help="deinterlace the input on the GPU in front of everything else, by yadif's spatio-temporal rule per component "
+                         "plane (DVD, broadcast and tape material; DESIGN.md section 7.13).  frame: one frame out per frame in; "
+                         "field: one per field, twice the frames at twice the rate.  --frames counts input frames.  --crop auto "
+                         "and --cropdetect keep sampling the source frames directly: bars are black in both fields")
+    ap.add_argument("--field-order", default=None, metavar="tff|bff",
+                    help="with --deinterlace: which rows come first in time, tff (default: the even rows, top field first) or bff")
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
+    deint = None
+    if a.field_order is not None and a.deinterlace is None:
+        ap.error("--field-order needs --deinterlace frame|field")
+    if a.deinterlace is not None:
+        if a.deinterlace not in ncnn.DEINT_MODES:
+            ap.error("--deinterlace takes frame or field, not %r" % a.deinterlace)
+        if a.field_order is not None and a.field_order not in ncnn.FIELD_ORDERS:
+            ap.error("--field-order takes tff or bff, not %r" % a.field_order)
+        if a.height < 4:
+            ap.error("--deinterlace: frames of fewer than 4 rows (-H %d) have no two rows of either field in every plane" % a.height)
+        deint = DeintSpec(a.deinterlace, a.field_order or "tff")
     if a.skip_repeats is not None and not 0 <= a.skip_repeats <= 65535:
         ap.error("--skip-repeats takes a threshold T of 0 ... 65535 code values, not %d" % a.skip_repeats)
     try:
@@ -1170,7 +1317,7 @@ def main(argv=None):
         for net, _ in nets[0]:
             scale_total *= 1 if isinstance(net, tuple) else net.scale
         n = stream_segments(ins if len(ins) > 1 else ins[0], outs if len(outs) > 1 else outs[0], a.height, a.width, nets, scale_total,
-                            max_frames=a.frames, write_threads=wthreads, pix=pix)
+                            max_frames=a.frames, write_threads=wthreads, pix=pix, **({"deint": deint} if deint is not None else {}))
         print(summary(n), file=sys.stderr)
         ncnn.destroy_gpu_instance()
         return 0
@@ -1182,9 +1329,10 @@ def main(argv=None):
     ok = False
     try:
         if nets:
-            n = stream(fin, fout, a.height, a.width, nets, max_frames=a.frames, write_threads=wthreads, pix=pix)
+            n = stream(fin, fout, a.height, a.width, nets, max_frames=a.frames, write_threads=wthreads, pix=pix,
+                       **({"deint": deint} if deint is not None else {}))
         else:
-            n = copy_through(fin, fout, a.height, a.width, a.frames, pix=pix, gpu=gpus[0])
+            n = copy_through(fin, fout, a.height, a.width, a.frames, pix=pix, gpu=gpus[0], **({"deint": deint} if deint is not None else {}))
         ok = True
     finally:
         if fin is not sys.stdin.buffer:
