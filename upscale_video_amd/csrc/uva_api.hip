@@ -17,6 +17,7 @@
 #include "uva_crop.h"
 #include "uva_deint.h"
 #include "uva_resize.h"
+#include "uva_submit.h"
 #include "uva_png.hip.h"
 #include "uva_wino.h"
 #include "uva_sub5.h"
@@ -54,6 +55,8 @@ int fail(const std::string& msg)
     g_err = msg;
     return 1;
 }
+
+int tryhip(hipError_t e, const char* what) { return e == hipSuccess ? 0 : fail(std::string(what) + ": " + hipGetErrorString(e)); }
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -203,14 +206,7 @@ struct uva_net {
     struct Repeat {
         int threshold = -1;              // -1: off
         bool valid = false;              // there is a kept frame, key says with which arguments it ran
-        struct Key {
-            int h, w, in_fmt, out_fmt, colour, u16, tile_size, border, res_h, res_w, filter;
-            bool operator==(const Key& o) const
-            {
-                return h == o.h && w == o.w && in_fmt == o.in_fmt && out_fmt == o.out_fmt && colour == o.colour && u16 == o.u16 &&
-                       tile_size == o.tile_size && border == o.border && res_h == o.res_h && res_w == o.res_w && filter == o.filter;
-            }
-        } key = {};
+        SubmitKey key = {};
         uint8_t *d_in = nullptr, *d_res = nullptr;
         size_t d_in_cap = 0, d_res_cap = 0;
         FrameDiffStats *d_stats = nullptr, *h_stats = nullptr;    // the kernel's record, and where it is read back (page-locked)
@@ -221,10 +217,7 @@ struct uva_net {
     Repeat rep;
     // uva_net_set_input_window: the frames the pixel-format submit entries are given are dense
     // src_h x src_w frames of which the call's h x w at (x, y) is uploaded; src_h == 0: off
-    struct Window {
-        int src_h = 0, src_w = 0, x = 0, y = 0;
-    };
-    Window win;
+    SubmitWindow win;
     void release_repeat()                // the device is current, nothing of this net is running
     {
         if (rep.d_in) (void)hipFree(rep.d_in);
@@ -972,6 +965,40 @@ hipEvent_t take_sync_event(uva_net* n)
         return nullptr;
     }
     return e;
+}
+
+// The stateless device stages (uva_*_device: denoise, pixel formats, resize) run on a stream of their own between two nets'
+// streams.  Both nets, where given, must live on the stage's device ...
+int check_fence_nets(int device, uva_net* after, uva_net* before, const char* entry)
+{
+    for (uva_net* n : {after, before})
+        if (n) {
+            if (ensure_device(n)) return 1;
+            if (n->device != device) return fail(std::string(entry) + ": the net is on another device");
+        }
+    return 0;
+}
+
+// ... what `after` has been asked to do so far (it wrote the stage's input, or still reads its output) comes first ...
+int fence_after(uva_net* after, hipStream_t stream)
+{
+    if (!after) return 0;
+    SyncEventScope ev(after);
+    if (!ev.e) return 1;
+    HIP_TRY(hipEventRecord(ev.e, after->stream));
+    HIP_TRY(hipStreamWaitEvent(stream, ev.e, 0));
+    return 0;
+}
+
+// ... and whatever `before` is asked to do from now on comes after the stage's frame
+int fence_before(uva_net* before, hipStream_t stream)
+{
+    if (!before) return 0;
+    SyncEventScope ev(before);
+    if (!ev.e) return 1;
+    HIP_TRY(hipEventRecord(ev.e, stream));
+    HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
+    return 0;
 }
 
 // Frames whose last event has completed are added to the statistics and their events recycled; frames still
@@ -1923,37 +1950,49 @@ int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, i
     return 0;
 }
 
-// d_in (in_fmt) -> d_out (out_fmt) on the context's stream, through u8 BGR in d_mid when neither end is BGR24
-int pix_convert_launch(PixCtx& c, const uint8_t* d_in, int in_fmt, uint8_t* d_out, int out_fmt, int h, int w, int colour)
+// the packed frame `src` of fmt -> the net's BGR frame `bgr` at `bits` (8: u8 [h][w][3], 16: u16) on `stream` ...
+int pix_to_native(hipStream_t stream, int bits, int fmt, int colour, const void* src, void* bgr, int h, int w)
 {
-    if (in_fmt == out_fmt) {
-        HIP_TRY(hipMemcpyAsync(d_out, d_in, pix_frame_bytes(in_fmt, h, w), hipMemcpyDeviceToDevice, c.stream));
-    } else if (in_fmt == PIX_BGR24) {
-        HIP_TRY(launch_pix_from_bgr(c.stream, out_fmt, colour, d_in, d_out, h, w));
-    } else if (out_fmt == PIX_BGR24) {
-        HIP_TRY(launch_pix_to_bgr(c.stream, in_fmt, colour, d_in, d_out, h, w));
-    } else {
-        if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(PIX_BGR24, h, w))) return 1;
-        HIP_TRY(launch_pix_to_bgr(c.stream, in_fmt, colour, d_in, c.d_mid, h, w));
-        HIP_TRY(launch_pix_from_bgr(c.stream, out_fmt, colour, c.d_mid, d_out, h, w));
-    }
-    return 0;
+    return bits == 16 ? tryhip(launch_pix16_to_bgr(stream, fmt, colour, src, (uint16_t*)bgr, h, w), "pix16_to_bgr")
+                      : tryhip(launch_pix_to_bgr(stream, fmt, colour, src, (uint8_t*)bgr, h, w), "pix_to_bgr");
 }
 
-// the 16-bit form: d_in (in_fmt) -> d_out (out_fmt) through u16 BGR (d_mid) when neither end is BGR48LE
-int pix_convert16_launch(PixCtx& c, const uint8_t* d_in, int in_fmt, uint8_t* d_out, int out_fmt, int h, int w, int colour)
+// ... and back
+int pix_from_native(hipStream_t stream, int bits, int fmt, int colour, const void* bgr, void* dst, int h, int w)
 {
+    return bits == 16 ? tryhip(launch_pix16_from_bgr(stream, fmt, colour, (const uint16_t*)bgr, dst, h, w), "pix16_from_bgr")
+                      : tryhip(launch_pix_from_bgr(stream, fmt, colour, (const uint8_t*)bgr, dst, h, w), "pix_from_bgr");
+}
+
+// d_in (in_fmt) -> d_out (out_fmt) on the context's stream, through the BGR of `bits` (BGR24 / BGR48LE) in d_mid when neither end
+// is that
+int pix_convert_launch(PixCtx& c, int bits, const uint8_t* d_in, int in_fmt, uint8_t* d_out, int out_fmt, int h, int w, int colour)
+{
+    const int native = bits == 16 ? PIX_BGR48LE : PIX_BGR24;
     if (in_fmt == out_fmt) {
         HIP_TRY(hipMemcpyAsync(d_out, d_in, pix_frame_bytes(in_fmt, h, w), hipMemcpyDeviceToDevice, c.stream));
-    } else if (in_fmt == PIX_BGR48LE) {
-        HIP_TRY(launch_pix16_from_bgr(c.stream, out_fmt, colour, (const uint16_t*)d_in, d_out, h, w));
-    } else if (out_fmt == PIX_BGR48LE) {
-        HIP_TRY(launch_pix16_to_bgr(c.stream, in_fmt, colour, d_in, (uint16_t*)d_out, h, w));
-    } else {
-        if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(PIX_BGR48LE, h, w))) return 1;
-        HIP_TRY(launch_pix16_to_bgr(c.stream, in_fmt, colour, d_in, (uint16_t*)c.d_mid, h, w));
-        HIP_TRY(launch_pix16_from_bgr(c.stream, out_fmt, colour, (const uint16_t*)c.d_mid, d_out, h, w));
+        return 0;
     }
+    if (in_fmt == native) return pix_from_native(c.stream, bits, out_fmt, colour, d_in, d_out, h, w);
+    if (out_fmt == native) return pix_to_native(c.stream, bits, in_fmt, colour, d_in, d_out, h, w);
+    if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(native, h, w))) return 1;
+    return pix_to_native(c.stream, bits, in_fmt, colour, d_in, c.d_mid, h, w) ||
+           pix_from_native(c.stream, bits, out_fmt, colour, c.d_mid, d_out, h, w);
+}
+
+// uva_pix_convert / uva_pix_convert16: one frame, host to host
+int pix_convert_host(int device, int bits, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
+{
+    if (pix_check(in, in_fmt, out, out_fmt, h, w, colour, bits == 16)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
+    if (pix_convert_launch(*c, bits, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -2340,30 +2379,16 @@ int uva_denoise_u8_device(int device, const void* d_in, int h, int w, size_t in_
     if (!d_in || !d_out || h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image");
     if (in_stride < (size_t)w * 3 || out_stride < (size_t)w * 3) return fail("row stride too small");
     if (!(h_luma > 0.f) || !(h_color > 0.f)) return fail("denoise strength must be positive");
-    for (uva_net* n : {after, before})
-        if (n) {
-            if (ensure_device(n)) return 1;
-            if (n->device != device) return fail("uva_denoise_u8_device: the net is on another device");
-        }
+    if (check_fence_nets(device, after, before, "uva_denoise_u8_device")) return 1;
     std::lock_guard<std::mutex> lk(g_denoise_mu);
     DenoiseCtx* c = nullptr;
     if (denoise_ctx(device, (size_t)h * w, &c)) return 1;
     // the weight tables are uploaded with a blocking copy: the stream must not be reading the old ones
     if (c->table_h[0] != h_luma || c->table_h[1] != h_color) HIP_TRY(hipStreamSynchronize(c->stream));
     if (denoise_table(*c, 0, h_luma, 1) || denoise_table(*c, 1, h_color, 2)) return 1;
-    if (after) {                 // what `after` has been asked to do so far (it wrote d_in, or still reads d_out) comes first
-        SyncEventScope ev(after);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, after->stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, ev.e, 0));
-    }
+    if (fence_after(after, c->stream)) return 1;
     if (denoise_launch(c, (const uint8_t*)d_in, in_stride, (uint8_t*)d_out, out_stride, h, w)) return 1;
-    if (before) {                // ... and whatever `before` is asked to do from now on comes after this frame
-        SyncEventScope ev(before);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, c->stream));
-        HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
-    }
+    if (fence_before(before, c->stream)) return 1;
     return 0;
 }
 
@@ -2447,11 +2472,7 @@ int uva_denoise_u16_device(int device, const void* d_in, int h, int w, size_t in
     if (in_stride < (size_t)w * 6 || out_stride < (size_t)w * 6) return fail("row stride too small");
     if ((in_stride | out_stride | (size_t)d_in | (size_t)d_out) & 1) return fail("uva_denoise_u16_device: u16 rows must be 2-byte aligned");
     if (!(h_luma > 0.f) || !(h_color > 0.f) || h_luma > NLM16_MAX_H || h_color > NLM16_MAX_H) return fail("denoise strength must be in (0, 64]");
-    for (uva_net* n : {after, before})
-        if (n) {
-            if (ensure_device(n)) return 1;
-            if (n->device != device) return fail("uva_denoise_u16_device: the net is on another device");
-        }
+    if (check_fence_nets(device, after, before, "uva_denoise_u16_device")) return 1;
     std::lock_guard<std::mutex> lk(g_denoise_mu);
     Denoise16Ctx* c = nullptr;
     hipStream_t stream = nullptr;
@@ -2459,19 +2480,9 @@ int uva_denoise_u16_device(int device, const void* d_in, int h, int w, size_t in
     // the weight tables are uploaded with a blocking copy: the stream must not be reading the old ones
     if (c->table_h[0] != h_luma || c->table_h[1] != h_color) HIP_TRY(hipStreamSynchronize(stream));
     if (denoise16_table(*c, 0, h_luma, 1) || denoise16_table(*c, 1, h_color, 2)) return 1;
-    if (after) {
-        SyncEventScope ev(after);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, after->stream));
-        HIP_TRY(hipStreamWaitEvent(stream, ev.e, 0));
-    }
+    if (fence_after(after, stream)) return 1;
     if (denoise16_launch(c, stream, (const uint16_t*)d_in, in_stride, (uint16_t*)d_out, out_stride, h, w)) return 1;
-    if (before) {
-        SyncEventScope ev(before);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, stream));
-        HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
-    }
+    if (fence_before(before, stream)) return 1;
     return 0;
 }
 
@@ -2823,244 +2834,273 @@ void uva_host_free(void* p)
 
 }  // extern "C"
 namespace {
-// uva_net_submit_u8 (png_ws == nullptr: the result frame goes to `out`), uva_net_submit_u8_png (the result frame stays
-// in HBM, its PNG deflate blocks go to the page-locked workspace png_ws) and uva_net_submit_pix (in_fmt / out_fmt other than
-// BGR24: the dense packed frame goes to d_pin and is converted into d_in on the net's stream, d_out is converted into d_pout
-// behind the net and d_pout comes back)
-// u16: the 16-bit route -- the net's frames are u16 BGR (BGR48LE), in_stride / out_stride are in bytes, and a packed frame
-// (bgr24 included) is converted to and from u16 BGR
-// rs_oh, rs_ow > 0 and other than the net's result size (uva_net_submit_pix_sized): the net's BGR result is resampled to
-// rs_oh x rs_ow into d_rs on the net's stream, and what follows -- the output conversion, the download -- takes d_rs at that size
-// may_skip (the uva_net_submit_* entries, not the PNG one): with uva_net_set_skip_repeats on, a frame that repeats the kept frame
-// is not computed -- the kept frame's result is downloaded for it
-long long submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out, size_t out_stride,
-                    int tile_size, int border, void* png_ws, size_t png_ws_bytes, int in_fmt = PIX_BGR24, int out_fmt = PIX_BGR24,
-                    int colour = 0, bool u16 = false, int rs_oh = 0, int rs_ow = 0, int rs_filter = 0, bool may_skip = false,
-                    bool windowed = false)
+// The pipelined host route.  An entry fills a SubmitSpec, submit_check refuses what the entries refuse,
+// submit_plan (csrc/uva_submit.cpp) works out every size and branch from the spec alone, and submit runs three stages over that
+// plan: the upload on s_h2d, the compute on the net's stream, the download on s_d2h.
+
+// the refusals of the host entries, in the order every entry has always applied them (a doubly-bad call reports the same one)
+int submit_check(uva_net* n, const SubmitSpec& sp, const char* entry)
 {
-    const int png_bits = u16 ? 16 : 8;     // (png_ws: the encoder that matches the net's frames)
-    if (check_dims(n, h, w)) return -1;
-    // windowed (the pixel-format entries, uva_net_set_input_window on): `in` is a dense src_h x src_w frame of in_fmt and h x w the
-    // window at (x, y) of it.  Only the upload below knows: it leaves the dense window frame where a whole frame's upload would.
-    const bool win = windowed && n->win.src_h > 0;
-    WindowPlane wpl[3];
-    int wn = 0;
-    if (win) {
-        const uva_net::Window& wd = n->win;
-        if (const char* e = crop_window_error(in_fmt, wd.src_h, wd.src_w, wd.x, wd.y, h, w)) { fail(e); return -1; }
-        wn = crop_window_planes(in_fmt, wd.src_h, wd.src_w, wd.x, wd.y, h, w, wpl);
-    }
-    if (!in || (!out && !png_ws)) { fail("null frame pointer"); return -1; }
-    if (png_ws && !is_pinned_host(png_ws)) { fail("PNG workspace must be page-locked host memory (uva_host_alloc)"); return -1; }
-    if (ensure_device(n)) return -1;
-    auto tryhip = [](hipError_t e, const char* what) { return e == hipSuccess ? 0 : fail(std::string(what) + ": " + hipGetErrorString(e)); };
-    const int s = uva_net_scale(n);
-    const size_t bps = u16 ? 2 : 1;        // bytes per sample of the net's frames
-    const size_t in_row = (size_t)w * 3 * bps, out_row = (size_t)w * s * 3 * bps;
-    const bool rs = rs_oh > 0 && rs_ow > 0 && !(rs_oh == h * s && rs_ow == w * s);
-    const int res_h = rs ? rs_oh : h * s, res_w = rs ? rs_ow : w * s;     // the frame that leaves
-    const size_t res_row = (size_t)res_w * 3 * bps, res_bytes = res_row * (size_t)res_h;
-    if (png_ws) out_stride = out_row;
-    if (in_stride < in_row || out_stride < res_row) { fail("row stride too small"); return -1; }
-    const size_t in_bytes = in_row * h, out_bytes = out_row * (size_t)h * s;
-    const int native = u16 ? PIX_BGR48LE : PIX_BGR24;
-    const bool pin = in_fmt != native, pout = out_fmt != native;
-    if (win && !pin) {
-        // the net's own BGR layout: the window is the frame at an offset with the source's row stride, which the upload takes as it is
-        in += (size_t)wpl[0].row0 * wpl[0].src_row + wpl[0].xbytes;
-        in_stride = wpl[0].src_row;
-    }
-    // a window over whole rows (a letterbox) is a contiguous row range of every plane; a narrower one goes up at full width and
-    // pix_window_kernel compacts its columns
-    const bool win_rows = win && pin, win_cols = win_rows && wpl[0].dst_row != wpl[0].src_row;
-    size_t wstage[3] = {0, 0, 0};
-    const size_t wstage_bytes = win_cols ? pix_window_staging(wpl, wn, wstage) : 0;
-    const size_t pin_bytes = pix_frame_bytes(in_fmt, h, w), pout_bytes = pix_frame_bytes(out_fmt, res_h, res_w);
-    if (pout_bytes > (size_t)INT_MAX) { fail("result frame of 2 GB or more"); return -1; }
-    uva_net::PipeSlot* free_slot = nullptr;
+    if (!pix_frame_bytes(sp.in_fmt, 1, 1) || !pix_frame_bytes(sp.out_fmt, 1, 1)) return fail("unknown pixel format");
+    if (sp.bits == 8 && (sp.in_fmt == PIX_BGR48LE || sp.out_fmt == PIX_BGR48LE))
+        return fail(std::string("bgr48le is a 16-bit format: ") +
+                    (std::strcmp(entry, "uva_net_submit_pix_sized") ? "use uva_net_submit_pix16" : "it needs bits = 16"));
+    if (!pix_colour_ok(sp.colour)) return fail("bad colour word");
+    if (check_dims(n, sp.h, sp.w)) return 1;
+    if (sp.bits == 16 && (ensure_device(n) || check_u16_net(n))) return 1;
+    if (sp.windowed && uva_net_scale(n) <= 0) return fail("net has no graph");
+    return 0;
+}
+
+// the net at `bits` on a frame in HBM
+int process_device(uva_net* n, int bits, const void* d_in, int h, int w, size_t in_stride, void* d_out, size_t out_stride, int tile_size,
+                   int border)
+{
+    return bits == 16 ? uva_net_process_u16_device(n, d_in, h, w, in_stride, d_out, out_stride, tile_size, border)
+                      : uva_net_process_u8_device(n, d_in, h, w, in_stride, d_out, out_stride, tile_size, border);
+}
+
+struct SubmitRun {                       // what the stages of one call share
+    uva_net* n;
+    const SubmitSpec& sp;
+    const SubmitPlan& p;
+    const uint8_t* in;                   // (a window of a BGR frame: at its offset)
+    uint8_t* out;
+    uva_net::PipeSlot* ps = nullptr;
+    const uint8_t* d_res = nullptr;      // the BGR frame that leaves: d_out, or d_rs
+    const uint8_t* d_src = nullptr;      // what comes down: d_res, the packed frame d_pout, or the kept frame's result
+    bool rp_on = false, repeat = false;  // uva_net_set_skip_repeats is in force; this frame repeats the kept one
+};
+
+// a free slot, the streams and events, the buffers, and the frame to HBM: into d_in, or (a packed frame) into d_pin
+int submit_upload(SubmitRun& r)
+{
+    uva_net* n = r.n;
+    const SubmitSpec& sp = r.sp;
+    const SubmitPlan& p = r.p;
     for (auto& c : n->pipe)
-        if (!c.busy) { free_slot = &c; break; }
-    if (!free_slot) { fail("uva_net_submit_u8: " + std::to_string(uva_net::PIPE_SLOTS) + " frames already in flight, collect one first"); return -1; }
-    uva_net::PipeSlot& ps = *free_slot;
+        if (!c.busy) { r.ps = &c; break; }
+    if (!r.ps) return fail("uva_net_submit_u8: " + std::to_string(uva_net::PIPE_SLOTS) + " frames already in flight, collect one first");
+    uva_net::PipeSlot& ps = *r.ps;
     if (!n->s_h2d) {
         if (tryhip(hipStreamCreateWithFlags(&n->s_h2d, hipStreamNonBlocking), "hipStreamCreate") ||
-            tryhip(hipStreamCreateWithFlags(&n->s_d2h, hipStreamNonBlocking), "hipStreamCreate")) return -1;
+            tryhip(hipStreamCreateWithFlags(&n->s_d2h, hipStreamNonBlocking), "hipStreamCreate")) return 1;
     }
     if (!ps.ev_h2d) {
         if (tryhip(hipEventCreateWithFlags(&ps.ev_h2d, hipEventDisableTiming), "hipEventCreate") ||
             tryhip(hipEventCreateWithFlags(&ps.ev_done, hipEventDisableTiming), "hipEventCreate") ||
-            tryhip(hipEventCreateWithFlags(&ps.ev_d2h, hipEventDisableTiming), "hipEventCreate")) return -1;
+            tryhip(hipEventCreateWithFlags(&ps.ev_d2h, hipEventDisableTiming), "hipEventCreate")) return 1;
     }
-    if (grow_dev(&ps.d_in, &ps.d_in_cap, in_bytes) || grow_dev(&ps.d_out, &ps.d_out_cap, out_bytes)) return -1;
-    if ((pin && grow_dev(&ps.d_pin, &ps.d_pin_cap, pin_bytes)) || (pout && grow_dev(&ps.d_pout, &ps.d_pout_cap, pout_bytes))) return -1;
-    if (rs && grow_dev(&ps.d_rs, &ps.d_rs_cap, res_bytes)) return -1;
-    if (win_cols && grow_dev(&ps.d_win, &ps.d_win_cap, wstage_bytes)) return -1;
-    const uint8_t* d_res = rs ? ps.d_rs : ps.d_out;                        // the BGR frame that leaves
-    std::string rs_err;
-    if (png_ws) {
-        if (!png_takes(h * s, w * s, png_bits)) { fail("PNG encoder: frame width out of range"); return -1; }
-        if (png_ws_bytes < png_workspace_bytes(h * s, w * s, png_bits)) { fail("PNG workspace too small"); return -1; }
-        if (grow_dev(&ps.d_png, &ps.d_png_cap, png_device_bytes(h * s, w * s, png_bits))) return -1;
+    if (grow_dev(&ps.d_in, &ps.d_in_cap, p.in_bytes) || grow_dev(&ps.d_out, &ps.d_out_cap, p.out_bytes)) return 1;
+    if ((p.pin && grow_dev(&ps.d_pin, &ps.d_pin_cap, p.pin_bytes)) || (p.pout && grow_dev(&ps.d_pout, &ps.d_pout_cap, p.pout_bytes))) return 1;
+    if (p.rs && grow_dev(&ps.d_rs, &ps.d_rs_cap, p.res_bytes)) return 1;
+    if (p.win_cols && grow_dev(&ps.d_win, &ps.d_win_cap, p.wstage_bytes)) return 1;
+    r.d_res = p.rs ? ps.d_rs : ps.d_out;
+    if (sp.png_ws) {                     // (png_ws: the encoder that matches the net's frames)
+        if (!png_takes(p.out_h, p.out_w, sp.bits)) return fail("PNG encoder: frame width out of range");
+        if (sp.png_ws_bytes < png_workspace_bytes(p.out_h, p.out_w, sp.bits)) return fail("PNG workspace too small");
+        if (grow_dev(&ps.d_png, &ps.d_png_cap, png_device_bytes(p.out_h, p.out_w, sp.bits))) return 1;
     }
     // H2D: straight from the caller's buffer when it is pinned (uva_host_alloc / hipHostMalloc /
     // hipHostRegister), through this slot's pinned staging buffer otherwise
-    // (a packed frame goes as one row of pin_bytes)
-    const uint8_t* src = in;
-    size_t src_stride = in_stride;
-    const size_t h2d_row = pin ? pin_bytes : in_row;
-    const int h2d_rows = pin ? 1 : h;
-    if (win_rows) {
+    const bool pinned = is_pinned_host(r.in);
+    if (!pinned && grow_host(&ps.h_in, &ps.h_in_cap, p.h_in_bytes)) return 1;
+    if (p.win_rows) {
         // one copy per plane of the plane's row range: into the packed frame where the rows are whole, into the staging otherwise
-        uint8_t* d_up = win_cols ? ps.d_win : ps.d_pin;
-        const bool pinned = is_pinned_host(in);
-        if (!pinned && grow_host(&ps.h_in, &ps.h_in_cap, win_cols ? wstage_bytes : pin_bytes)) return -1;
-        for (int p = 0; p < wn; ++p) {
-            const size_t at = win_cols ? wstage[p] : wpl[p].dst_off, nb = wpl[p].src_row * (size_t)wpl[p].rows;
-            const uint8_t* from = in + wpl[p].src_off + (size_t)wpl[p].row0 * wpl[p].src_row;
+        uint8_t* d_up = p.win_cols ? ps.d_win : ps.d_pin;
+        for (int k = 0; k < p.wn; ++k) {
+            const WindowPlane& wp = p.wpl[k];
+            const size_t at = p.win_cols ? p.wstage[k] : wp.dst_off, nb = wp.src_row * (size_t)wp.rows;
+            const uint8_t* from = r.in + wp.src_off + (size_t)wp.row0 * wp.src_row;
             if (!pinned) {
                 std::memcpy(ps.h_in + at, from, nb);
                 from = ps.h_in + at;
             }
-            if (tryhip(hipMemcpyAsync(d_up + at, from, nb, hipMemcpyHostToDevice, n->s_h2d), "H2D")) return -1;
+            if (tryhip(hipMemcpyAsync(d_up + at, from, nb, hipMemcpyHostToDevice, n->s_h2d), "H2D")) return 1;
         }
-        if (win_cols && tryhip(launch_pix_window(n->s_h2d, ps.d_win, wstage, ps.d_pin, wpl, wn, crop_sample(in_fmt).bytes), "pix_window")) return -1;
+        if (p.win_cols && tryhip(launch_pix_window(n->s_h2d, ps.d_win, p.wstage, ps.d_pin, p.wpl, p.wn, crop_sample(sp.in_fmt).bytes), "pix_window"))
+            return 1;
     } else {
-        if (!is_pinned_host(in)) {
-            if (grow_host(&ps.h_in, &ps.h_in_cap, pin ? pin_bytes : in_bytes)) return -1;
-            if (pin) std::memcpy(ps.h_in, in, pin_bytes);
+        const uint8_t* src = r.in;
+        size_t src_stride = p.pin ? p.h2d_row : p.in_stride;
+        if (!pinned) {
+            if (p.pin) std::memcpy(ps.h_in, r.in, p.pin_bytes);
             else
-                for (int y = 0; y < h; ++y) std::memcpy(ps.h_in + y * in_row, in + y * in_stride, in_row);
-            src = ps.h_in; src_stride = h2d_row;
+                for (int y = 0; y < sp.h; ++y) std::memcpy(ps.h_in + y * p.in_row, r.in + y * p.in_stride, p.in_row);
+            src = ps.h_in; src_stride = p.h2d_row;
         }
-        if (tryhip(hipMemcpy2DAsync(pin ? ps.d_pin : ps.d_in, h2d_row, src, pin ? h2d_row : src_stride, h2d_row, h2d_rows,
-                                    hipMemcpyHostToDevice, n->s_h2d), "H2D")) return -1;
+        if (tryhip(hipMemcpy2DAsync(p.pin ? ps.d_pin : ps.d_in, p.h2d_row, src, src_stride, p.h2d_row, p.h2d_rows, hipMemcpyHostToDevice,
+                                    n->s_h2d), "H2D")) return 1;
     }
     if (tryhip(hipEventRecord(ps.ev_h2d, n->s_h2d), "hipEventRecord") ||
-        tryhip(hipStreamWaitEvent(n->stream, ps.ev_h2d, 0), "hipStreamWaitEvent")) return -1;
-    // what comes down: the BGR rows of d_out, or the packed frame d_pout -- as "rows" of one byte, so that a band is a byte
-    // range (collect copies it with one memcpy)
-    const uint8_t* d_src = pout ? ps.d_pout : d_res;
-    const size_t dl_bytes = pout ? pout_bytes : res_bytes;
+        tryhip(hipStreamWaitEvent(n->stream, ps.ev_h2d, 0), "hipStreamWaitEvent")) return 1;
+    r.d_src = p.pout ? ps.d_pout : r.d_res;
+    return 0;
+}
+
+// the repeat comparison, then -- unless the frame repeats the kept one -- convert in, the net, the resampler, convert out, the
+// PNG deflate, all on the net's stream behind the upload
+int submit_compute(SubmitRun& r)
+{
+    uva_net* n = r.n;
+    const SubmitSpec& sp = r.sp;
+    const SubmitPlan& p = r.p;
+    uva_net::PipeSlot& ps = *r.ps;
     // --skip-repeats: the frame is compared with the kept frame's input on the upload stream, behind its own upload, and the
     // host waits for the three numbers -- the one blocking point of the route, and only with the option on
     uva_net::Repeat& rp = n->rep;
-    const bool rp_on = may_skip && !png_ws && rp.threshold >= 0;
-    bool repeat = false;
-    if (rp_on) {
-        const uint8_t* d_packed = pin ? ps.d_pin : ps.d_in;
-        const size_t packed_bytes = pin ? pin_bytes : in_bytes;
-        const uva_net::Repeat::Key key = {h, w, in_fmt, out_fmt, colour, u16 ? 1 : 0, tile_size, border, res_h, res_w, rs ? rs_filter : 0};
+    r.rp_on = sp.may_skip && !sp.png_ws && rp.threshold >= 0;
+    if (r.rp_on) {
+        const uint8_t* d_packed = p.pin ? ps.d_pin : ps.d_in;
         ++rp.submitted;
         if (!rp.d_stats) {
             if (tryhip(hipMalloc((void**)&rp.d_stats, sizeof(FrameDiffStats)), "hipMalloc") ||
                 tryhip(hipHostMalloc((void**)&rp.h_stats, sizeof(FrameDiffStats), hipHostMallocDefault), "hipHostMalloc") ||
                 tryhip(hipEventCreateWithFlags(&rp.ev_stats, hipEventDisableTiming), "hipEventCreate") ||
                 tryhip(hipEventCreateWithFlags(&rp.ev_written, hipEventDisableTiming), "hipEventCreate") ||
-                tryhip(hipEventCreateWithFlags(&rp.ev_read, hipEventDisableTiming), "hipEventCreate")) return -1;
+                tryhip(hipEventCreateWithFlags(&rp.ev_read, hipEventDisableTiming), "hipEventCreate")) return 1;
         }
-        if (rp.valid && key == rp.key) {
-            if (tryhip(launch_frame_diff(n->s_h2d, rp.d_in, d_packed, packed_bytes, in_fmt, (unsigned)rp.threshold, rp.d_stats), "frame_diff") ||
+        if (rp.valid && p.key == rp.key) {
+            if (tryhip(launch_frame_diff(n->s_h2d, rp.d_in, d_packed, p.packed_bytes, sp.in_fmt, (unsigned)rp.threshold, rp.d_stats), "frame_diff") ||
                 tryhip(hipMemcpyAsync(rp.h_stats, rp.d_stats, sizeof(FrameDiffStats), hipMemcpyDeviceToHost, n->s_h2d), "D2H") ||
                 tryhip(hipEventRecord(rp.ev_stats, n->s_h2d), "hipEventRecord") ||
-                tryhip(hipEventSynchronize(rp.ev_stats), "hipEventSynchronize")) return -1;
-            repeat = rp.h_stats->over == 0;
+                tryhip(hipEventSynchronize(rp.ev_stats), "hipEventSynchronize")) return 1;
+            r.repeat = rp.h_stats->over == 0;
         }
-        if (!repeat) {
+        if (!r.repeat) {
             // this frame runs and becomes the kept frame.  Kept input: the comparisons read it and this copy replaces it on one
             // stream, s_h2d, so they are ordered (the slot's own upload buffer is free again once the frame is collected).
             rp.valid = false;
-            if (rp.d_in_cap < packed_bytes || rp.d_res_cap < dl_bytes) {      // (a buffer that moves: nothing may still use it)
+            if (rp.d_in_cap < p.packed_bytes || rp.d_res_cap < p.dl_bytes) {      // (a buffer that moves: nothing may still use it)
                 if (tryhip(hipStreamSynchronize(n->s_h2d), "hipStreamSynchronize") || tryhip(hipStreamSynchronize(n->s_d2h), "hipStreamSynchronize") ||
-                    tryhip(hipStreamSynchronize(n->stream), "hipStreamSynchronize")) return -1;
-                if (grow_dev(&rp.d_in, &rp.d_in_cap, packed_bytes) || grow_dev(&rp.d_res, &rp.d_res_cap, dl_bytes)) return -1;
+                    tryhip(hipStreamSynchronize(n->stream), "hipStreamSynchronize")) return 1;
+                if (grow_dev(&rp.d_in, &rp.d_in_cap, p.packed_bytes) || grow_dev(&rp.d_res, &rp.d_res_cap, p.dl_bytes)) return 1;
                 rp.reads_pending = false;
             }
-            if (tryhip(hipMemcpyAsync(rp.d_in, d_packed, packed_bytes, hipMemcpyDeviceToDevice, n->s_h2d), "D2D")) return -1;
-            rp.key = key;
+            if (tryhip(hipMemcpyAsync(rp.d_in, d_packed, p.packed_bytes, hipMemcpyDeviceToDevice, n->s_h2d), "D2D")) return 1;
+            rp.key = p.key;
         }
     }
-    if (repeat) {
+    if (r.repeat) {
         // the kept result's bytes, by a download alone: behind the copy that wrote them (ev_written, on the net's stream)
         ++rp.skipped;
-        d_src = rp.d_res;
-        if (tryhip(hipStreamWaitEvent(n->s_d2h, rp.ev_written, 0), "hipStreamWaitEvent")) return -1;
-    } else if (u16) {
-        if (pin && tryhip(launch_pix16_to_bgr(n->stream, in_fmt, colour, ps.d_pin, (uint16_t*)ps.d_in, h, w), "pix16_to_bgr")) return -1;
-        if (uva_net_process_u16_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
-        if (rs && launch_resize(n->stream, n->device, ps.d_out, h * s, w * s, out_row, ps.d_rs, res_h, res_w, res_row, rs_filter, 16, &rs_err)) { fail(rs_err); return -1; }
-        if (pout && tryhip(launch_pix16_from_bgr(n->stream, out_fmt, colour, (const uint16_t*)d_res, ps.d_pout, res_h, res_w), "pix16_from_bgr"))
-            return -1;
-    } else {
-        if (pin && tryhip(launch_pix_to_bgr(n->stream, in_fmt, colour, ps.d_pin, ps.d_in, h, w), "pix_to_bgr")) return -1;
-        if (uva_net_process_u8_device(n, ps.d_in, h, w, in_row, ps.d_out, out_row, tile_size, border)) return -1;
-        if (rs && launch_resize(n->stream, n->device, ps.d_out, h * s, w * s, out_row, ps.d_rs, res_h, res_w, res_row, rs_filter, 8, &rs_err)) { fail(rs_err); return -1; }
-        if (pout && tryhip(launch_pix_from_bgr(n->stream, out_fmt, colour, d_res, ps.d_pout, res_h, res_w), "pix_from_bgr")) return -1;
+        r.d_src = rp.d_res;
+        return tryhip(hipStreamWaitEvent(n->s_d2h, rp.ev_written, 0), "hipStreamWaitEvent");
     }
+    std::string rs_err;
+    if (p.pin && pix_to_native(n->stream, sp.bits, sp.in_fmt, sp.colour, ps.d_pin, ps.d_in, sp.h, sp.w)) return 1;
+    if (process_device(n, sp.bits, ps.d_in, sp.h, sp.w, p.in_row, ps.d_out, p.out_row, sp.tile_size, sp.border)) return 1;
+    if (p.rs && launch_resize(n->stream, n->device, ps.d_out, p.out_h, p.out_w, p.out_row, ps.d_rs, p.res_h, p.res_w, p.res_row, sp.rs_filter,
+                              sp.bits, &rs_err)) return fail(rs_err);
+    if (p.pout && pix_from_native(n->stream, sp.bits, sp.out_fmt, sp.colour, r.d_res, ps.d_pout, p.res_h, p.res_w)) return 1;
     // png: the deflate kernel follows the net on its stream and leaves the blocks in HBM, packed end to end by a second
     // (device-to-device) kernel: 0.15 ms per 4K frame together
-    if (png_ws && ((u16 ? png_launch16(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png)
-                        : png_launch(n->device, n->stream, ps.d_out, out_row, h * s, w * s, ps.d_png)) ||
-                   png_pack_launch(n->stream, ps.d_png, h * s, w * s, png_bits))) return -1;
-    if (!repeat && (tryhip(hipEventRecord(ps.ev_done, n->stream), "hipEventRecord") ||
-                    tryhip(hipStreamWaitEvent(n->s_d2h, ps.ev_done, 0), "hipStreamWaitEvent"))) return -1;
-    if (rp_on && !repeat) {
+    if (sp.png_ws && ((sp.bits == 16 ? png_launch16(n->device, n->stream, ps.d_out, p.out_row, p.out_h, p.out_w, ps.d_png)
+                                     : png_launch(n->device, n->stream, ps.d_out, p.out_row, p.out_h, p.out_w, ps.d_png)) ||
+                      png_pack_launch(n->stream, ps.d_png, p.out_h, p.out_w, sp.bits))) return 1;
+    if (tryhip(hipEventRecord(ps.ev_done, n->stream), "hipEventRecord") ||
+        tryhip(hipStreamWaitEvent(n->s_d2h, ps.ev_done, 0), "hipStreamWaitEvent")) return 1;
+    if (r.rp_on) {
         // Kept result: skipped frames download it on s_d2h, this copy overwrites it on the net's stream.  s_d2h runs in order,
         // so the event behind the last such download (ev_read) stands for every download of the old contents still pending.
-        if (rp.reads_pending && tryhip(hipStreamWaitEvent(n->stream, rp.ev_read, 0), "hipStreamWaitEvent")) return -1;
-        if (tryhip(hipMemcpyAsync(rp.d_res, d_src, dl_bytes, hipMemcpyDeviceToDevice, n->stream), "D2D") ||
-            tryhip(hipEventRecord(rp.ev_written, n->stream), "hipEventRecord")) return -1;
+        if (rp.reads_pending && tryhip(hipStreamWaitEvent(n->stream, rp.ev_read, 0), "hipStreamWaitEvent")) return 1;
+        if (tryhip(hipMemcpyAsync(rp.d_res, r.d_src, p.dl_bytes, hipMemcpyDeviceToDevice, n->stream), "D2D") ||
+            tryhip(hipEventRecord(rp.ev_written, n->stream), "hipEventRecord")) return 1;
         rp.reads_pending = false;
         rp.valid = true;
     }
-    if (png_ws) {
+    return 0;
+}
+
+// the result to the caller on s_d2h behind the compute, and the ticket uva_net_collect_u8 takes
+int submit_download(SubmitRun& r)
+{
+    uva_net* n = r.n;
+    const SubmitSpec& sp = r.sp;
+    const SubmitPlan& p = r.p;
+    uva_net::PipeSlot& ps = *r.ps;
+    ps.user_out = nullptr;
+    ps.png_ws = nullptr;
+    if (sp.png_ws) {
         // ... and the copy engine takes them to the caller's page-locked workspace while the next frame computes.  How
         // many bytes there are is only known on the device: as many as the previous frame had (+ 6 %) go now, collect
         // fetches the rest should this frame be larger.  (A kernel writing to host memory instead keeps CUs busy for
         // the PCIe transfer: 0.24 ms per 4K frame that the next frame's net then waits for.)
-        const size_t cap = png_workspace_bytes(h * s, w * s, png_bits) - png_meta_bytes(h * s, w * s, png_bits);
-        const size_t last = u16 ? n->png_guess16 : n->png_guess;
-        const size_t guess = last ? std::min(cap, last + last / 16 + 65536) : std::min(cap, out_bytes * 5 / 8);
-        if (png_download(n->s_d2h, ps.d_png, h * s, w * s, png_ws, guess, png_bits)) return -1;
-        if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return -1;
-        ps.png_ws = (uint8_t*)png_ws; ps.png_sent = guess; ps.png_h = h * s; ps.png_w = w * s; ps.png_bits = png_bits;
-        ps.user_out = nullptr;
-        ps.busy = true;
-        ps.ticket = n->next_ticket;
-        return n->next_ticket++;
-    }
-    uint8_t* dst = out;
-    size_t dst_stride = out_stride;
-    ps.user_out = nullptr;
-    ps.png_ws = nullptr;
-    if (!is_pinned_host(out)) {
-        if (grow_host(&ps.h_out, &ps.h_out_cap, dl_bytes)) return -1;
-        dst = ps.h_out; dst_stride = res_row;
-        ps.user_out = out; ps.user_out_stride = pout ? 1 : out_stride; ps.out_row = pout ? 1 : res_row;
-        ps.out_rows = pout ? (int)pout_bytes : res_h;
-    }
-    if (ps.user_out) {
-        const int rows = ps.out_rows, per = (rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
-        const size_t row = ps.out_row;
-        for (int k = 0; k < uva_net::PipeSlot::BANDS; ++k) {
-            if (!ps.ev_band[k] && tryhip(hipEventCreateWithFlags(&ps.ev_band[k], hipEventDisableTiming), "hipEventCreate")) return -1;
-            const int r0 = std::min(rows, k * per), nr = std::min(rows, r0 + per) - r0;
-            if (nr > 0 && tryhip(hipMemcpyAsync(dst + (size_t)r0 * row, d_src + (size_t)r0 * row, (size_t)nr * row,
-                                                hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return -1;
-            if (tryhip(hipEventRecord(ps.ev_band[k], n->s_d2h), "hipEventRecord")) return -1;
+        const size_t cap = png_workspace_bytes(p.out_h, p.out_w, sp.bits) - png_meta_bytes(p.out_h, p.out_w, sp.bits);
+        const size_t last = sp.bits == 16 ? n->png_guess16 : n->png_guess;
+        const size_t guess = last ? std::min(cap, last + last / 16 + 65536) : std::min(cap, p.out_bytes * 5 / 8);
+        if (png_download(n->s_d2h, ps.d_png, p.out_h, p.out_w, sp.png_ws, guess, sp.bits)) return 1;
+        if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return 1;
+        ps.png_ws = (uint8_t*)sp.png_ws; ps.png_sent = guess; ps.png_h = p.out_h; ps.png_w = p.out_w; ps.png_bits = sp.bits;
+    } else {
+        uint8_t* dst = r.out;
+        if (!is_pinned_host(r.out)) {
+            if (grow_host(&ps.h_out, &ps.h_out_cap, p.dl_bytes)) return 1;
+            dst = ps.h_out;
+            ps.user_out = r.out; ps.user_out_stride = p.dl_user_stride; ps.out_row = p.dl_row; ps.out_rows = p.dl_rows;
         }
-    } else if (pout) {
-        if (tryhip(hipMemcpyAsync(dst, d_src, dl_bytes, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return -1;
-    } else if (tryhip(hipMemcpy2DAsync(dst, dst_stride, d_src, res_row, res_row, (size_t)res_h, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) {
-        return -1;
-    }
-    if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return -1;
-    if (repeat) {
-        if (tryhip(hipEventRecord(rp.ev_read, n->s_d2h), "hipEventRecord")) return -1;
-        rp.reads_pending = true;
+        if (ps.user_out) {
+            const int rows = p.dl_rows, per = (rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
+            const size_t row = p.dl_row;
+            for (int k = 0; k < uva_net::PipeSlot::BANDS; ++k) {
+                if (!ps.ev_band[k] && tryhip(hipEventCreateWithFlags(&ps.ev_band[k], hipEventDisableTiming), "hipEventCreate")) return 1;
+                const int r0 = std::min(rows, k * per), nr = std::min(rows, r0 + per) - r0;
+                if (nr > 0 && tryhip(hipMemcpyAsync(dst + (size_t)r0 * row, r.d_src + (size_t)r0 * row, (size_t)nr * row,
+                                                    hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return 1;
+                if (tryhip(hipEventRecord(ps.ev_band[k], n->s_d2h), "hipEventRecord")) return 1;
+            }
+        } else if (p.pout) {
+            if (tryhip(hipMemcpyAsync(dst, r.d_src, p.dl_bytes, hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return 1;
+        } else if (tryhip(hipMemcpy2DAsync(dst, p.out_stride, r.d_src, p.res_row, p.res_row, (size_t)p.res_h, hipMemcpyDeviceToHost, n->s_d2h),
+                          "D2H")) {
+            return 1;
+        }
+        if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return 1;
+        if (r.repeat) {
+            if (tryhip(hipEventRecord(n->rep.ev_read, n->s_d2h), "hipEventRecord")) return 1;
+            n->rep.reads_pending = true;
+        }
     }
     ps.busy = true;
-    ps.ticket = n->next_ticket;
-    return n->next_ticket++;
+    ps.ticket = n->next_ticket++;
+    return 0;
+}
+
+// `in` -> `out` (the PNG route: -> sp.png_ws) as `sp` says; returns the ticket, or -1.  The entry has run submit_check.
+long long submit(uva_net* n, const void* in, void* out, const SubmitSpec& sp)
+{
+    SubmitPlan p;
+    const char* refusal = submit_plan(sp, uva_net_scale(n), sp.windowed && n->win.src_h > 0 ? &n->win : nullptr, &p);
+    // (the plan's refusals keep their places among those that need the pointers and the device: the window's come first)
+    if (refusal && p.window_refused) { fail(refusal); return -1; }
+    if (!in || (!out && !sp.png_ws)) { fail("null frame pointer"); return -1; }
+    if (sp.png_ws && !is_pinned_host(sp.png_ws)) { fail("PNG workspace must be page-locked host memory (uva_host_alloc)"); return -1; }
+    if (ensure_device(n)) return -1;
+    if (refusal) { fail(refusal); return -1; }
+    SubmitRun r = {n, sp, p, (const uint8_t*)in + p.in_offset, (uint8_t*)out};
+    if (submit_upload(r) || submit_compute(r) || submit_download(r)) return -1;
+    return r.ps->ticket;
+}
+
+// a BGR call's spec: the geometry, every other member at its default
+SubmitSpec bgr_spec(int h, int w, size_t in_stride, size_t out_stride, int tile_size, int border)
+{
+    SubmitSpec sp;
+    sp.h = h; sp.w = w;
+    sp.in_stride = in_stride; sp.out_stride = out_stride;
+    sp.tile_size = tile_size; sp.border = border;
+    return sp;
+}
+
+// a pixel-format call's spec: dense frames, the net's BGR at `bits`, the result at the net's size
+SubmitSpec pix_spec(const uva_net* n, int bits, int in_fmt, int out_fmt, int colour, int h, int w, int tile_size, int border)
+{
+    const size_t bps = bits / 8;
+    SubmitSpec sp = bgr_spec(h, w, (size_t)w * 3 * bps, (size_t)w * uva_net_scale(n) * 3 * bps, tile_size, border);
+    sp.in_fmt = in_fmt; sp.out_fmt = out_fmt; sp.colour = colour;
+    sp.bits = bits;
+    sp.may_skip = sp.windowed = true;
+    return sp;
 }
 }  // namespace
 extern "C" {
@@ -3068,96 +3108,70 @@ extern "C" {
 long long uva_net_submit_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out,
                             size_t out_stride, int tile_size, int border)
 {
-    return submit_u8(n, in, h, w, in_stride, out, out_stride, tile_size, border, nullptr, 0, PIX_BGR24, PIX_BGR24, 0, false, 0, 0, 0, true);
+    SubmitSpec sp = bgr_spec(h, w, in_stride, out_stride, tile_size, border);
+    sp.may_skip = true;
+    if (submit_check(n, sp, "uva_net_submit_u8")) return -1;
+    return submit(n, in, out, sp);
 }
 
 long long uva_net_submit_u8_png(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, void* png_ws, size_t png_ws_bytes,
                                 int tile_size, int border)
 {
     if (!png_ws) { fail("null PNG workspace"); return -1; }
-    return submit_u8(n, in, h, w, in_stride, nullptr, 0, tile_size, border, png_ws, png_ws_bytes);
+    SubmitSpec sp = bgr_spec(h, w, in_stride, 0, tile_size, border);
+    sp.png_ws = png_ws; sp.png_ws_bytes = png_ws_bytes;
+    if (submit_check(n, sp, "uva_net_submit_u8_png")) return -1;
+    return submit(n, in, nullptr, sp);
 }
 
 long long uva_net_submit_u16_png(uva_net* n, const uint16_t* in, int h, int w, size_t in_stride, void* png_ws, size_t png_ws_bytes,
                                  int tile_size, int border)
 {
     if (!png_ws) { fail("null PNG workspace"); return -1; }
-    if (check_dims(n, h, w)) return -1;
-    if (ensure_device(n) || check_u16_net(n)) return -1;
+    SubmitSpec sp = bgr_spec(h, w, in_stride, 0, tile_size, border);
+    sp.in_fmt = sp.out_fmt = PIX_BGR48LE; sp.bits = 16;
+    sp.png_ws = png_ws; sp.png_ws_bytes = png_ws_bytes;
+    if (submit_check(n, sp, "uva_net_submit_u16_png")) return -1;
     if (is_sub10_net(n) && tile_size > 0) { fail("the 16-bit route runs the 1x net on whole frames only (tile_size 0)"); return -1; }
     if ((((uintptr_t)in | in_stride) & 1) != 0) { fail("odd address or stride of a 16-bit frame"); return -1; }
-    return submit_u8(n, (const uint8_t*)in, h, w, in_stride, nullptr, 0, tile_size, border, png_ws, png_ws_bytes, PIX_BGR48LE, PIX_BGR48LE,
-                     0, true);
+    return submit(n, in, nullptr, sp);
 }
 
 size_t uva_pix_frame_bytes(int fmt, int h, int w) { return pix_frame_bytes(fmt, h, w); }
 
 int uva_pix_convert(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
 {
-    if (pix_check(in, in_fmt, out, out_fmt, h, w, colour)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
-    PixCtx* c = nullptr;
-    if (pix_ctx(device, &c)) return 1;
-    const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
-    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
-    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
-    if (pix_convert_launch(*c, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
-    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+    return pix_convert_host(device, 8, in, in_fmt, out, out_fmt, h, w, colour);
 }
 
 int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out, int out_fmt, int h, int w, int colour,
                            uva_net* after, uva_net* before)
 {
     if (pix_check(d_in, in_fmt, d_out, out_fmt, h, w, colour)) return 1;
-    for (uva_net* n : {after, before})
-        if (n) {
-            if (ensure_device(n)) return 1;
-            if (n->device != device) return fail("uva_pix_convert_device: the net is on another device");
-        }
+    if (check_fence_nets(device, after, before, "uva_pix_convert_device")) return 1;
     std::lock_guard<std::mutex> lk(g_pix_mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
-    if (after) {                 // what `after` has been asked to do so far (it wrote d_in, or still reads d_out) comes first
-        SyncEventScope ev(after);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, after->stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, ev.e, 0));
-    }
-    if (pix_convert_launch(*c, (const uint8_t*)d_in, in_fmt, (uint8_t*)d_out, out_fmt, h, w, colour)) return 1;
-    if (before) {                // ... and whatever `before` is asked to do from now on comes after this frame
-        SyncEventScope ev(before);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, c->stream));
-        HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
-    }
+    if (fence_after(after, c->stream)) return 1;
+    if (pix_convert_launch(*c, 8, (const uint8_t*)d_in, in_fmt, (uint8_t*)d_out, out_fmt, h, w, colour)) return 1;
+    if (fence_before(before, c->stream)) return 1;
     return 0;
 }
 
 long long uva_net_submit_pix(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
                              int tile_size, int border)
 {
-    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
-    if (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE) { fail("bgr48le is a 16-bit format: use uva_net_submit_pix16"); return -1; }
-    if (!pix_colour_ok(colour)) { fail("bad colour word"); return -1; }
-    if (check_dims(n, h, w)) return -1;
-    const int s = uva_net_scale(n);
-    if (s <= 0) { fail("net has no graph"); return -1; }
-    return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3, (uint8_t*)out, (size_t)w * s * 3, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, false, 0, 0, 0, true, true);
+    const SubmitSpec sp = pix_spec(n, 8, in_fmt, out_fmt, colour, h, w, tile_size, border);
+    if (submit_check(n, sp, "uva_net_submit_pix")) return -1;
+    return submit(n, in, out, sp);
 }
 
 long long uva_net_submit_pix16(uva_net* n, const void* in, int in_fmt, int h, int w, void* out, int out_fmt, int colour,
                                int tile_size, int border)
 {
-    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
-    if (!pix_colour_ok(colour)) { fail("bad colour word"); return -1; }
-    if (check_dims(n, h, w)) return -1;
-    if (ensure_device(n) || check_u16_net(n)) return -1;
-    const int s = uva_net_scale(n);
-    return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 6, (uint8_t*)out, (size_t)w * s * 6, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, true, 0, 0, 0, true, true);
+    const SubmitSpec sp = pix_spec(n, 16, in_fmt, out_fmt, colour, h, w, tile_size, border);
+    if (submit_check(n, sp, "uva_net_submit_pix16")) return -1;
+    return submit(n, in, out, sp);
 }
 
 int uva_net_enable_u16_1x(uva_net* n, int on)
@@ -3177,9 +3191,10 @@ int uva_net_process_u16(uva_net* n, const uint16_t* in, int h, int w, size_t in_
     // as uva_net_process_u16_device: the staging copies would take any stride, but a row of u16 samples at an odd address is
     // no uint16_t array
     if ((((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 1) != 0) return fail("16-bit frames need 2-byte aligned rows");
-    if (ensure_device(n) || check_u16_net(n)) return 1;
-    const long long t = submit_u8(n, (const uint8_t*)in, h, w, in_stride, (uint8_t*)out, out_stride, tile_size, border, nullptr, 0,
-                                  PIX_BGR48LE, PIX_BGR48LE, 0, true);
+    SubmitSpec sp = bgr_spec(h, w, in_stride, out_stride, tile_size, border);
+    sp.in_fmt = sp.out_fmt = PIX_BGR48LE; sp.bits = 16;
+    if (submit_check(n, sp, "uva_net_process_u16")) return 1;
+    const long long t = submit(n, in, out, sp);
     if (t < 0) return 1;
     if (uva_net_collect_u8(n, t)) return 1;
     resolve_events(n);
@@ -3188,17 +3203,7 @@ int uva_net_process_u16(uva_net* n, const uint16_t* in, int h, int w, size_t in_
 
 int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
 {
-    if (pix_check(in, in_fmt, out, out_fmt, h, w, colour, true)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
-    PixCtx* c = nullptr;
-    if (pix_ctx(device, &c)) return 1;
-    const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
-    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
-    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
-    if (pix_convert16_launch(*c, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
-    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+    return pix_convert_host(device, 16, in, in_fmt, out, out_fmt, h, w, colour);
 }
 
 // ---- the resampler (csrc/uva_resize.hip) ----------------------------------------------------------
@@ -3235,28 +3240,14 @@ int uva_resize_device(int device, const void* d_in, int h, int w, size_t in_stri
                       int filter, int bits, uva_net* after, uva_net* before)
 {
     if (resize_check(d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits)) return 1;
-    for (uva_net* n : {after, before})
-        if (n) {
-            if (ensure_device(n)) return 1;
-            if (n->device != device) return fail("uva_resize_device: the net is on another device");
-        }
+    if (check_fence_nets(device, after, before, "uva_resize_device")) return 1;
     std::lock_guard<std::mutex> lk(g_pix_mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
-    if (after) {
-        SyncEventScope ev(after);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, after->stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, ev.e, 0));
-    }
+    if (fence_after(after, c->stream)) return 1;
     std::string err;
     if (launch_resize(c->stream, device, d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits, &err)) return fail(err);
-    if (before) {
-        SyncEventScope ev(before);
-        if (!ev.e) return 1;
-        HIP_TRY(hipEventRecord(ev.e, c->stream));
-        HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
-    }
+    if (fence_before(before, c->stream)) return 1;
     return 0;
 }
 
@@ -3285,18 +3276,14 @@ long long uva_net_submit_pix_sized(uva_net* n, const void* in, int in_fmt, int h
                                    int tile_size, int border, int oh, int ow, int filter, int bits)
 {
     if (bits != 8 && bits != 16) { fail("uva_net_submit_pix_sized: bits must be 8 or 16"); return -1; }
-    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) { fail("unknown pixel format"); return -1; }
-    if (bits == 8 && (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE)) { fail("bgr48le is a 16-bit format: it needs bits = 16"); return -1; }
-    if (!pix_colour_ok(colour)) { fail("bad colour word"); return -1; }
-    if (check_dims(n, h, w)) return -1;
-    if (bits == 16 && (ensure_device(n) || check_u16_net(n))) return -1;
+    SubmitSpec sp = pix_spec(n, bits, in_fmt, out_fmt, colour, h, w, tile_size, border);
+    sp.out_stride = (size_t)ow * 3 * (bits / 8);
+    sp.rs_oh = oh; sp.rs_ow = ow; sp.rs_filter = filter;
+    if (submit_check(n, sp, "uva_net_submit_pix_sized")) return -1;
     const int s = uva_net_scale(n);
-    if (s <= 0) { fail("net has no graph"); return -1; }
     if (const char* e = resize_axis_error(h * s, oh, filter)) { fail(e); return -1; }
     if (const char* e = resize_axis_error(w * s, ow, filter)) { fail(e); return -1; }
-    const size_t bps = bits / 8;
-    return submit_u8(n, (const uint8_t*)in, h, w, (size_t)w * 3 * bps, (uint8_t*)out, (size_t)ow * 3 * bps, tile_size, border, nullptr, 0,
-                     in_fmt, out_fmt, colour, bits == 16, oh, ow, filter, true, true);
+    return submit(n, in, out, sp);
 }
 
 // ---- repeated frames (csrc/uva_repeat.hip) ---------------------------------------------------------
@@ -3862,8 +3849,10 @@ int uva_net_collect_u8(uva_net* n, long long ticket)
 int uva_net_process_u8(uva_net* n, const uint8_t* in, int h, int w, size_t in_stride, uint8_t* out,
                        size_t out_stride, int tile_size, int border)
 {
-    // (not through uva_net_submit_u8: the synchronous calls take no part in uva_net_set_skip_repeats)
-    const long long t = submit_u8(n, in, h, w, in_stride, out, out_stride, tile_size, border, nullptr, 0);
+    // (may_skip stays off: the synchronous calls take no part in uva_net_set_skip_repeats)
+    const SubmitSpec sp = bgr_spec(h, w, in_stride, out_stride, tile_size, border);
+    if (submit_check(n, sp, "uva_net_process_u8")) return 1;
+    const long long t = submit(n, in, out, sp);
     if (t < 0) return 1;
     if (uva_net_collect_u8(n, t)) return 1;
     resolve_events(n);

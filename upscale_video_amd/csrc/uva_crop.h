@@ -1,8 +1,8 @@
 // uva_crop.h -- black-bar detection and cropped input frames on the raw-video route (include/uva.h uva_crop_*, uva_pix_window*,
 // uva_net_set_input_window).  Two halves:
 //   csrc/uva_crop_host.cpp  plain C++ without HIP: the bright-line scan over a frame's line sums, the running state's rectangle
-//                           (ffmpeg cropdetect's rule as tests/cropdetect_ref.py states it), the window validator and the planes
-//                           of a window.  Functions of their arguments; built alone by tests/test_crop_sanitized.py.
+//                           (ffmpeg cropdetect's rule as tests/cropdetect_ref.py states it), the window validator, the planes
+//                           of a window and their staging layout.  Functions of their arguments; built alone by tests/test_crop_sanitized.py.
 //   csrc/uva_crop.hip       the kernels: crop_sums_kernel (exact line sums of the luma plane or the packed BGR frame) and
 //                           pix_window_kernel (the columns of a window compacted in HBM).
 // This header is included by both, so the HIP declarations sit behind __HIPCC__.
@@ -45,6 +45,10 @@ struct WindowPlane {
 // fills planes[3], returns how many there are (0: unknown format)
 int crop_window_planes(int fmt, int src_h, int src_w, int x, int y, int h, int w, WindowPlane planes[3]);
 
+// bytes of the staging that launch_pix_window reads for these planes: every plane's row range at full width, each starting at a
+// multiple of 16 bytes; stage_off[p] receives plane p's offset there
+size_t pix_window_staging(const WindowPlane* planes, int n, size_t stage_off[3]);
+
 }  // namespace uva
 
 #ifdef __HIPCC__
@@ -57,10 +61,6 @@ namespace uva {
 // grid below the kernel's own bound (tests: the grid-stride walk on a small frame).
 hipError_t launch_crop_sums(hipStream_t stream, const void* d_frame, int fmt, int h, int w, unsigned long long* d_rows,
                             unsigned long long* d_cols, int max_groups = 0);
-
-// bytes of the staging that launch_pix_window reads for these planes: every plane's row range at full width, each starting at a
-// multiple of 16 bytes; stage_off[p] receives plane p's offset there
-size_t pix_window_staging(const WindowPlane* planes, int n, size_t stage_off[3]);
 
 // d_dst (dense window frame, 16-byte aligned) <- the planes' window rows, of which plane p's first lies at byte stage_off[p] of
 // d_stage at full width (pix_window_staging's layout, or a whole source frame: src_off + row0 * src_row), the columns compacted,

@@ -229,16 +229,6 @@ hipError_t launch_crop_sums(hipStream_t stream, const void* d_frame, int fmt, in
     return hipGetLastError();
 }
 
-size_t pix_window_staging(const WindowPlane* planes, int n, size_t stage_off[3])
-{
-    size_t at = 0;
-    for (int p = 0; p < n; ++p) {
-        stage_off[p] = at;
-        at += (planes[p].src_row * (size_t)planes[p].rows + 15) & ~(size_t)15;
-    }
-    return at;
-}
-
 hipError_t launch_pix_window(hipStream_t stream, const void* d_stage, const size_t* stage_off, void* d_dst, const WindowPlane* planes, int n,
                              int bytes)
 {

@@ -105,4 +105,14 @@ int crop_window_planes(int fmt, int src_h, int src_w, int x, int y, int h, int w
     return 3;
 }
 
+size_t pix_window_staging(const WindowPlane* planes, int n, size_t stage_off[3])
+{
+    size_t at = 0;
+    for (int p = 0; p < n; ++p) {
+        stage_off[p] = at;
+        at += (planes[p].src_row * (size_t)planes[p].rows + 15) & ~(size_t)15;
+    }
+    return at;
+}
+
 }  // namespace uva

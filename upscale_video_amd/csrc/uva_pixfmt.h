@@ -9,8 +9,9 @@
 //   bgr48le  [h][w][3] u16 (unorm16): the 16-bit route's BGR (section 7.4)
 //   yuv422p  Y [h][w] u8, then U [h][cw], then V [h][cw]: one chroma row per luma row (section 7.7)
 //   yuv422p10le  yuv422p's layout in 16-bit little-endian words, the 10-bit value in the low bits
+// The enums and pix_frame_bytes are plain C++ (csrc/uva_submit.cpp includes this header without HIP); the launchers sit behind
+// __HIPCC__.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -38,7 +39,27 @@ inline int pix_chroma_mode(int colour)
 }
 
 // bytes of one dense h x w frame of `fmt`; 0 for an unknown format or a size <= 0
-size_t pix_frame_bytes(int fmt, int h, int w);
+inline size_t pix_frame_bytes(int fmt, int h, int w)
+{
+    if (h <= 0 || w <= 0) return 0;
+    const size_t wh = (size_t)w * h, c = 2 * ((size_t)(w + 1) / 2) * ((size_t)(h + 1) / 2), c422 = 2 * ((size_t)(w + 1) / 2) * (size_t)h;
+    switch (fmt) {
+    case PIX_BGR24: return 3 * wh;
+    case PIX_YUV420P: case PIX_NV12: return wh + c;
+    case PIX_P010LE: case PIX_YUV420P10LE: return 2 * (wh + c);
+    case PIX_YUV422P: return wh + c422;
+    case PIX_YUV422P10LE: return 2 * (wh + c422);
+    case PIX_BGR48LE: return 6 * wh;
+    default: return 0;
+    }
+}
+
+}  // namespace uva
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+namespace uva {
 
 // bgr (dense u8 [h][w][3]) <- src of format fmt (a Y'CbCr format), on `stream`
 hipError_t launch_pix_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint8_t* bgr, int h, int w);
@@ -49,3 +70,4 @@ hipError_t launch_pix16_to_bgr(hipStream_t stream, int fmt, int colour, const vo
 hipError_t launch_pix16_from_bgr(hipStream_t stream, int fmt, int colour, const uint16_t* bgr, void* dst, int h, int w);
 
 }  // namespace uva
+#endif

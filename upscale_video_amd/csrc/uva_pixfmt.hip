@@ -868,21 +868,6 @@ dim3 grid422_of(int h, int w) { return dim3((unsigned)((w + PX * BX - 1) / (PX *
 
 }  // namespace
 
-size_t pix_frame_bytes(int fmt, int h, int w)
-{
-    if (h <= 0 || w <= 0) return 0;
-    const size_t wh = (size_t)w * h, c = 2 * ((size_t)(w + 1) / 2) * ((size_t)(h + 1) / 2), c422 = 2 * ((size_t)(w + 1) / 2) * (size_t)h;
-    switch (fmt) {
-    case PIX_BGR24: return 3 * wh;
-    case PIX_YUV420P: case PIX_NV12: return wh + c;
-    case PIX_P010LE: case PIX_YUV420P10LE: return 2 * (wh + c);
-    case PIX_YUV422P: return wh + c422;
-    case PIX_YUV422P10LE: return 2 * (wh + c422);
-    case PIX_BGR48LE: return 6 * wh;
-    default: return 0;
-    }
-}
-
 namespace {
 int depth_of(int fmt) { return fmt == PIX_P010LE || fmt == PIX_YUV420P10LE || fmt == PIX_YUV422P10LE ? 10 : 8; }
 

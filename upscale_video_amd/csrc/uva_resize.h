@@ -16,7 +16,13 @@ constexpr int RESIZE_ONE = 1 << 14;     // every row of a tap table sums to exac
 constexpr int RESIZE_MAX_TAPS = 24;     // lanczos at the ratio limit 1/4
 
 // null when (n_in -> n_out, filter) is an axis the resampler takes, else what is wrong with it
-const char* resize_axis_error(int n_in, int n_out, int filter);
+inline const char* resize_axis_error(int n_in, int n_out, int filter)
+{
+    if (filter < 0 || filter >= RESIZE_NFILTER) return "resize: unknown filter (0 lanczos, 1 bicubic, 2 bilinear)";
+    if (n_in < 1 || n_out < 1) return "resize: sizes must be at least 1";
+    if ((long long)n_out * 4 < n_in || (long long)n_out > (long long)n_in * 4) return "resize: the output / input ratio of an axis must lie within [1/4, 4]";
+    return nullptr;
+}
 // taps per output sample, T = 2 ceil(a max(1, n_in / n_out)); 0 for an axis resize_axis_error refuses
 int resize_ntaps(int n_in, int n_out, int filter);
 // the table of one axis, host only: first[n_out], taps[n_out][T] (dense).  Returns T, 0 for a refused axis.

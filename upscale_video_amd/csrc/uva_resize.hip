@@ -292,14 +292,6 @@ hipError_t launch_c(int txc, hipStream_t stream, dim3 grid, size_t lds, const Re
 
 }  // namespace
 
-const char* resize_axis_error(int n_in, int n_out, int filter)
-{
-    if (filter < 0 || filter >= RESIZE_NFILTER) return "resize: unknown filter (0 lanczos, 1 bicubic, 2 bilinear)";
-    if (n_in < 1 || n_out < 1) return "resize: sizes must be at least 1";
-    if ((long long)n_out * 4 < n_in || (long long)n_out > (long long)n_in * 4) return "resize: the output / input ratio of an axis must lie within [1/4, 4]";
-    return nullptr;
-}
-
 int resize_ntaps(int n_in, int n_out, int filter)
 {
     if (resize_axis_error(n_in, n_out, filter)) return 0;
