@@ -333,7 +333,7 @@ def epilogue_audit(conv, bias, res, top):
 
 
 # ---------------------------------------------------------------------------------------------------------------- reference
-MUTANTS = ("mirror_x", "swap_cin", "wino_row", "clamp_slope", "tail_swap", "seam_col", "border_row")
+MUTANTS = ("mirror_x", "swap_cin", "wino_row", "clamp_slope", "tail_swap", "seam_col", "border_row", "lost_carry_rows")
 
 
 def tail_swap_channels(n):
@@ -351,7 +351,13 @@ class Ref:
         clamp_slope  the PReLU behind convolution `layer` has its slopes above 1 clamped to 1
         tail_swap    two output channels of the last convolution exchanged (the two whose biases are nearest)
         seam_col     convolution `layer` computes output column `col` with input column col - 1 read from col - 2
-        border_row   (tiled route) plane `plane`'s innermost top border row is zero: the padding instead of the neighbour"""
+        border_row   (tiled route) plane `plane`'s innermost top border row is zero: the padding instead of the neighbour
+        lost_carry_rows  (tiled route) in plane `plane`, convolution `layer` (the first of a trunkw launch: its result is the
+                     launch's intermediate) has rows r0 - 1 and r0 zero over columns x0 .. x0 + width - 1: the two
+                     intermediate rows a segment whose first output row is r0 needs from above its first full block, i.e.
+                     what its first step must bring (a fill step's two valid rows, a six-row start's first two) -- lost
+                     where a segment starts on the state the previous one left in the rings.  tests/schedule_census.py
+                     carry_starts() gives (plane, x0, r0, width)"""
 
     def __init__(self, key, bin_path):
         self.key = key
@@ -422,6 +428,8 @@ class Ref:
                     if at and mu["kind"] == "clamp_slope":
                         s = np.minimum(s, 1.0)
                     y = np.where(y < 0, y * s[:, None, None], y)
+                    if at and mu["kind"] == "lost_carry_rows":
+                        y[:, max(mu["r0"] - 1, 0):mu["r0"] + 1, mu["x0"]:mu["x0"] + mu["width"]] = 0
                     if audit is not None:
                         audit.blob("conv %d" % conv, y)
                         audit.slopes = getattr(audit, "slopes", True) and _f16_exact(s)
@@ -481,7 +489,8 @@ class Ref:
                 if mu.get("kind") == "border_row" and mu["plane"] == k and top:
                     tile = tile.copy()
                     tile[top - 1] = 0
-                v = self.frame_values(tile, mutant=None if mu.get("kind") == "border_row" else mutant, **kw)
+                here = mu.get("kind") != "border_row" and (mu.get("kind") != "lost_carry_rows" or mu["plane"] == k)
+                v = self.frame_values(tile, mutant=mutant if here else None, **kw)
                 out[s * y0:s * y1, s * x0:s * x1] = v[s * top:s * (top + y1 - y0), s * left:s * (left + x1 - x0)]
                 k += 1
         return out

@@ -11,8 +11,8 @@ output: 100 %); the audit that licenses array_equal for every (net, weight set, 
 == the oracle's product modes, bit for bit, on the float route (output and every tap) and on the u8 route whole and tiled, for every
 probe; every mutant of the reference (one plausible slip each) differing from it; the clamp share of the u8 frames.
 
-GPU (-m gpu): every route and switch against Ref with np.array_equal.  CASES lists them; the table at its end says which kernel
-each reaches."""
+GPU (-m gpu): every route and switch against Ref with np.array_equal.  CASES lists them; kernel_table() says which kernel each
+reaches and how many of the shipped workloads' schedule classes (tests/schedule_census.py) its cases visit."""
 import os
 
 import numpy as np
@@ -20,6 +20,7 @@ import pytest
 
 import compact_probe as cp
 import parity_report as pr
+import schedule_census as sc
 from generic_probe import Audit
 from mutant_net import model_paths
 from oracle import uvoracle
@@ -42,13 +43,43 @@ SHAPES_1X = {0: (50, 33), 1: (37, 121), 2: (130, 216), 3: (3, 2), 4: (50, 33), 5
 SWITCHES_1X = (("UVA_SUB5", "1", (2, 5, 6)), ("UVA_SUB10", "0", (2, 4, 8)))
 BATCH_1X = (1, 37, 121)                          # set, h, w: three different frames in one call
 U16_1X = cp.SHALLOW                             # (the 16-bit route takes the sets whose output lies on 2^-7: epilogue_audit)
+# The frames above give a workgroup a list of at most 4 steps (1x: 24 rows) -- no lap of a ring, no second segment in a list.
+# CENSUS_* are the frames that visit the states the shipped workloads' lists reach (schedule_census: the coverage test below),
+# chosen by greedy cover over the census for the fewest pixels -- the float64 audit costs ~145 us a pixel on the 64-feature
+# nets --, which is why they are NARROW: a strip costs a step whatever its width, a 256-workgroup launch needs ~3000 steps
+# for lists of 12, and 61 columns are a first, an interior and a one-column last strip.  (h, w, tile), border 10:
+#   3841 x 61 / 120   33 planes of 61 columns: lists of >= 12 steps, three segments per list, six-row and fill starts in the middle
+#                     of a plane at every phase of the rings, folded one-column last strips, no idle workgroup
+#   4508 x 31 / 300   lists of 8 steps on full and on folded strips: the phases of fill starts and of stores that the first
+#                     leaves open, above all for the kernels that only run its default lists (UVA_TW_CARRY=0, UVA_TW_ACT16=0)
+#   1696 x 45 / 100   a last strip of 15 columns, too wide to fold and (trunk2_kernel) to be narrow: ragged single stores at
+#                     every phase
+#   760 x 12 / 250    planes of ONE folded strip (lists of 4 steps): folded starts at a plane's top, a folded store phase
+CENSUS_TILED = ((3841, 61, 120), (4508, 31, 300), (1696, 45, 100), (760, 12, 250))
+CENSUS_SETS = (cp.ALL_UP_SET, 6)                # u8; the all-up set's sign carry between launches meets long lists here
+CENSUS_U16 = 1                                  # a cp.SHALLOW set
+# The float route is whole-frame (one plane, its own lists): the two smallest census frames with every layer's tap -- 1696 x 45
+# whole has 242 segments that start in the middle of the plane; the 17 float64 taps of 64 channels are 0.66 GB for it and
+# would be 1.2 / 2 GB for the two larger frames
+CENSUS_F32 = {"2x": 2, "4x": 3}
+CENSUS_SWITCHES = ("UVA_TW_CARRY", "UVA_TW_ACT16", "UVA_TRUNK_WINO", "UVA_TRUNK_FUSION")      # other kernels: every census frame
+PLANNER_SWITCHES = (("UVA_TW_FOLD", "0"), ("UVA_TW_SIX", "1"), ("UVA_TW_SIX", "0"))             # other lists, the same kernel
+SMALL_SWITCH_FRAMES = (("UVA_TRUNK_WINO", 38, 50), ("UVA_TRUNK_FUSION", 16, 64))   # a wide ragged last strip; full tile columns
+# 1x.  4328 x 120: two full 60-column strips, lists of ~90 rows with two segments, segments of more than S10_RES_ROWS = 32 written
+# rows, no idle workgroup; 40 x 230: a first, an interior and a last strip pair for sub5_kernel; 16 x 64: pair24_kernel's full
+# tiles; four frames of 4500 x 61 in one call: lists of >= 160 rows that cross from one frame into the next (--batch 4: 560)
+CENSUS_1X = (4328, 120)
+CENSUS_1X_SMALL = ((40, 230), (16, 64))
+CENSUS_1X_SETS = {"u8": 2, "UVA_SUB5": 5, "UVA_SUB10": 4}
+LONG_BATCH_1X = (1, 4500, 61, 4)                # set, h, w, frames
 
 
 class Case:
-    """one GPU run and its reference: net, weight set, route ("f32", "u8", "u16", "batch"), frame, tile, switch"""
+    """one GPU run and its reference: net, weight set, route ("f32", "u8", "u16", "batch", "batch4"), frame, tile, switch"""
 
     def __init__(self, key, wset, route, h, w, tile=0, env=None):
         self.key, self.wset, self.route, self.h, self.w, self.tile, self.env = key, wset, route, h, w, tile, env
+        self.frames = {"batch": 3, "batch4": 4}.get(route, 1)
         self.id = "%s-w%d-%s-%dx%d-t%d%s" % (key, wset, route, h, w, tile, "-%s=%s" % env if env else "")
         self.frame_key = (key, wset, route, h, w, tile)              # (what the reference depends on: a switch changes nothing)
 
@@ -69,16 +100,51 @@ def _cases():
     out += [Case("1x", s, "u8", *hw, env=(name, val)) for name, val, sets in SWITCHES_1X for s in sets for hw in ((50, 33), (130, 216))]
     out += [Case("1x", BATCH_1X[0], "batch", *BATCH_1X[1:])]
     out += [Case("1x", s, "u16", *hw) for s in U16_1X for hw in ((50, 33), (37, 121))]
+    return out + _census_cases()
+
+
+def _census_cases():
+    out = []
+    for key in ("2x", "4x"):
+        for h, w, t in CENSUS_TILED:
+            out += [Case(key, s, "u8", h, w, t) for s in CENSUS_SETS] + [Case(key, CENSUS_U16, "u16", h, w, t)]
+            out += [Case(key, cp.ALL_UP_SET, "u8", h, w, t, env=(name, "0")) for name in CENSUS_SWITCHES]
+        h, w, t = CENSUS_TILED[0]
+        out += [Case(key, cp.ALL_UP_SET, "u8", h, w, t, env=env) for env in PLANNER_SWITCHES]
+        out += [Case(key, CENSUS_F32[key], "f32", h, w) for h, w, _ in CENSUS_TILED[-2:]]
+        out += [Case(key, 5 if (h, w) == (16, 64) else 0, "u8", h, w, env=(name, "0")) for name, h, w in SMALL_SWITCH_FRAMES]
+    out += [Case("1x", CENSUS_1X_SETS["u8"], "u8", *CENSUS_1X), Case("1x", U16_1X[0], "u16", *CENSUS_1X)]
+    for hw in (CENSUS_1X,) + CENSUS_1X_SMALL:
+        out += [Case("1x", CENSUS_1X_SETS[name], "u8", *hw, env=(name, val)) for name, val, _ in SWITCHES_1X]
+    out += [Case("1x", LONG_BATCH_1X[0], "batch4", *LONG_BATCH_1X[1:3])]
     return out
 
 
 CASES = _cases()
-# which test reaches which kernel (2x: tail_kernel, 4x: tail4_kernel on every u8 / u16 / float case of that net):
-#   headp_kernel          every 2x / 4x case by default           head_kernel       UVA_HEAD_PERSIST=0
-#   trunkw_kernel<64>     every 2x / 4x case by default, and with UVA_TW_ACT16=0 (fp32 PReLU), UVA_TW_FOLD=0, UVA_TW_CARRY=0
-#   trunk2_kernel         UVA_TRUNK_WINO=0                         trunk_kernel      UVA_TRUNK_FUSION=0, and the odd debug taps
-#   sub10_kernel          1x u8 by default, the batch              sub10_kernel16    1x u16
-#   sub5_kernel           UVA_SUB5=1                               pair24_kernel     UVA_SUB10=0, and the 1x float route
+
+
+def kernel_table(uva):
+    """which case reaches which kernel, from the census (it cannot go stale): 2x tail_kernel / 4x tail4_kernel and headp_kernel
+    on every frame case of that net (head_kernel: UVA_HEAD_PERSIST=0), pair24_kernel also on the 1x float route; per trunk /
+    1x kernel group the cases that run it and the classes of the workloads' lists they visit
+    -> [(kernel, cases, classes reached, {workload: its classes}, text)]"""
+    rows = []
+    for kernel in sc.TRUNK_KERNELS + sc.ROW_KERNELS:
+        cases = [c for c in CASES if c.route != "f32" and sc.kernel_of(c.key, c.route, c.env)[0] == kernel]
+        have = _reached(uva, cases)
+        want = {name: w for name, w in ((name, sc.workload_census(uva, name, kernel)) for name in sc.WORKLOADS) if w is not None}
+        every = set().union(*want.values())
+        rows.append((kernel, cases, have, want, "%-30s %3d cases, %3d classes visited, %3d of the workloads' %3d" %
+                     (kernel, len(cases), len(have), len(have & every), len(every))))
+    return rows
+
+
+def _reached(uva, cases):
+    """the union of the census over the geometries (and planner switches) of `cases`, which all run one kernel group"""
+    out = set()
+    for kernel, planner, h, w, tile, frames in sorted({sc.kernel_of(c.key, c.route, c.env) + (c.h, c.w, c.tile, c.frames) for c in cases}):
+        out |= sc.census(uva, kernel, h, w, tile, 10 if tile else 0, frames, planner)
+    return out
 
 
 class Probes:
@@ -183,8 +249,7 @@ def test_exactness_audit(probes, key):
     cases = _unique([c for c in CASES if c.key == key])
     clamp_worst, near_all, ties_all = 0.0, 0, 0
     for c in cases:
-        frames = 3 if c.route == "batch" else 1
-        for k in range(frames):
+        for k in range(c.frames):
             v, _, a = probes.want(c, k)
             assert a.bad() == [], (c.id, a.bad())
             assert a.slopes is True
@@ -217,6 +282,26 @@ def test_exactness_audit(probes, key):
           f"; worst clamp share {100 * clamp_worst:.1f} %; {near_all} samples within 0.05 of a half-integer, {ties_all} exact ties, "
           "every one with the exact value's code in fp32 either way")
     assert worst.max() <= 11 and (key == "1x" or worst[:-1].max() <= 10)          # (in front of a Winograd layer: 10)
+
+
+def test_bit_exact_cases_reach_every_schedule_class_of_the_workloads(uva):
+    """Every state of a strip-walking kernel that a shipped workload's lists reach (tests/schedule_census.py: ring phase of a
+    segment start and of a store, kind of start, rows stored, list length, segments per list, ...) is reached by a case that is
+    held to the float64 reference bit for bit -- per kernel group, because a switch that selects another kernel (or another
+    instantiation of one) has lists and states of its own; UVA_TW_FOLD / UVA_TW_SIX only give the default kernel other lists.
+    The classes are the issue's: a segment start is (kind, top of plane or not, list index mod 5, folded or not, rmask), a store
+    (list index mod 5, folded or not, rows, full or ragged columns); the union is taken over every case of the group.
+    There is no allow-list.  One bucket is wider than a first count would make it, because the class cannot be reached below a
+    frame size whose float64 audit takes minutes (a 256-workgroup launch, ~145 us of audit per pixel): trunk_kernel's turns
+    per workgroup are 1 and >= 2, not "a lap of its 5 slots" -- 6 turns are 3072 tiles of 4 x 32 pixels, 0.39 M pixels."""
+    missing = []
+    for kernel, cases, have, want, text in kernel_table(uva):
+        print(text)
+        assert cases, kernel
+        for name, classes in want.items():
+            missing += [(kernel, name, cls) for cls in sorted(classes - have, key=str)]
+    assert not missing, "%d schedule classes of the workloads reached by no bit-exact case:\n%s" % (
+        len(missing), "\n".join("  %-32s %-20s %s" % m for m in missing))
 
 
 TAP_SHAPE = (9, 35)
@@ -267,22 +352,47 @@ def _mutants(key):
            dict(kind="clamp_slope", layer=None), dict(kind="tail_swap", layer=n_conv - 1), dict(kind="border_row", plane=2)]
     if key != "1x":
         out += [dict(kind="wino_row", layer=7, row=1), dict(kind="wino_row", layer=8, row=0), dict(kind="wino_row", layer=8, row=2),
-                dict(kind="seam_col", layer=8, col=cp.STRIP), dict(kind="seam_col", layer=3, col=2 * cp.STRIP)]
+                dict(kind="seam_col", layer=8, col=cp.STRIP), dict(kind="seam_col", layer=3, col=2 * cp.STRIP),
+                dict(kind="lost_carry_rows", layer=7)]
     return out
 
 
+def _old_geometries():
+    """the 2x / 4x frame cases from before the census frames, each with the planner switch it runs under"""
+    new = {(h, w, t) for h, w, t in CENSUS_TILED}
+    return sorted({(c.h, c.w, c.tile, sc.kernel_of(c.key, c.route, c.env)[1]) for c in CASES
+                   if c.key != "1x" and c.route in ("u8", "u16") and (c.h, c.w, c.tile) not in new})
+
+
 @pytest.mark.parametrize("key", cp.KEYS)
-def test_mutants_bite(probes, key):
+def test_mutants_bite(probes, uva, key):
     """one plausible slip each, restated in numpy on the reference: the probes see every one, with every weight set it is tried
-    on (the float route's 37 x 70 / 50 x 33 frame and the tiled u8 frame of that set)"""
+    on (the float route's 37 x 70 / 50 x 33 frame and the tiled u8 frame of that set).  lost_carry_rows sits where the census
+    puts a segment that needs rows from above it -- a later segment of a list, or a six-row start in the middle of a plane --
+    on a census frame (4508 x 31 at tile 300) with the weight sets the GPU runs there; NO frame from before the census has such a place (carry_starts is empty for every one of
+    them, under the planner switch it runs with): that is why they could not have seen this slip."""
     assert {m["kind"] for k in cp.KEYS for m in _mutants(k)} == set(cp.MUTANTS)
     for mu in _mutants(key):
         for s in (0, 4, 6) if key != "1x" else (0, 2, 5):
+            if mu["kind"] == "lost_carry_rows" and s not in CENSUS_SETS:
+                continue
             m = dict(mu)
             r = probes.ref(key, s)
             if m["kind"] == "clamp_slope":
                 m["layer"] = max(cp.WINDOWS[key][s], key=lambda i: int((r.S[i] > 1).sum()))
-            if m["kind"] == "border_row":
+            if m["kind"] == "lost_carry_rows":
+                for h, w, t, planner in _old_geometries():
+                    assert sc.carry_starts(uva, h, w, t, 10 if t else 0, planner) == [], (h, w, t, planner)
+                h, w, t = CENSUS_TILED[1]
+                starts = sc.carry_starts(uva, h, w, t, 10)
+                assert starts
+                plane, x0, r0, width = starts[len(starts) // 2]
+                m.update(plane=plane, x0=x0, r0=r0, width=width)
+                c = Case(key, s, "u8", h, w, t)
+                img = probes.input(c)
+                want = cp.to_codes(r.tiled_values(img, t))
+                got = cp.to_codes(r.tiled_values(img, t, mutant=m))
+            elif m["kind"] == "border_row":
                 c = Case(key, s, "u8", 64, 64, 32)
                 img = probes.input(c)
                 want = cp.to_codes(r.tiled_values(img, 32))
@@ -363,4 +473,17 @@ def test_gpu_batch_of_three_frames(uva, probes):
     frames = [probes.input(c, k) for k in range(3)]
     got = run_batch(net, frames)
     for k in range(3):
+        _hold(f"probe {c.id} frame {k}", got[k], cp.to_codes(probes.want(c, k)[0]))
+
+
+@pytest.mark.gpu
+def test_gpu_long_batch_of_four_frames(uva, probes):
+    """process_u8_device_batch with four frames whose row lists are >= 160 rows long and run on from one frame into the next
+    (the workload's --batch 4 runs lists of 560 rows; the batch of three above: 24), each frame against Ref"""
+    from test_gpu_batch import run_batch
+    assert uva.get_gpu_count() > 0
+    (c,) = [c for c in CASES if c.route == "batch4"]
+    net = _load(uva, probes.bin(c.key, c.wset), c.key)
+    got = run_batch(net, [probes.input(c, k) for k in range(c.frames)])
+    for k in range(c.frames):
         _hold(f"probe {c.id} frame {k}", got[k], cp.to_codes(probes.want(c, k)[0]))
