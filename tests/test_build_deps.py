@@ -33,6 +33,25 @@ def test_every_header_a_source_reaches_is_in_its_list(src):
     assert not missing, "build.SOURCES[%r] lacks %s" % (src, sorted(os.path.relpath(m, build.CSRC) for m in missing))
 
 
+def test_every_kernel_header_is_compiled_by_one_source():
+    """A header that defines kernels (`__global__`) belongs to one translation unit.  Template kernels reached by two
+    sources would still link -- and be compiled twice, minutes each, without anyone noticing."""
+    users = {}
+    for src in build.SOURCES:
+        for dep in reached(os.path.join(build.CSRC, src), set()):
+            users.setdefault(dep, []).append(src)
+    kernel_headers = []
+    for name in sorted(os.listdir(build.CSRC)):
+        path = os.path.join(build.CSRC, name)
+        if name.endswith(".h"):
+            with open(path) as f:
+                if "__global__" in f.read():
+                    kernel_headers.append(path)
+    assert kernel_headers, "no kernel header found under csrc/: the test looks in the wrong place"
+    for path in kernel_headers:
+        assert len(users.get(path, [])) == 1, "%s is reached by %s" % (os.path.relpath(path, build.CSRC), sorted(users.get(path, [])))
+
+
 def test_every_source_file_is_built():
     on_disk = {f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp"))}
     assert on_disk == set(build.SOURCES)

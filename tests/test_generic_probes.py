@@ -424,7 +424,7 @@ def _on(env, name, default=True):
 
 
 def _dense_rule(env, blocks=1, sum2=False):
-    """how often a dense-block probe launches which kernel on an h x w plane under `env` (csrc/uva_api.hip generic_run_planes):
+    """how often a dense-block probe launches which kernel on an h x w plane under `env` (csrc/uva_generic_run.hip generic_run_planes):
     exact counts, so a probe that silently takes another kernel fails here"""
     def rule(c):
         lds = _on(env, "UVA_GENERIC_LDS")

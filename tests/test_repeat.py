@@ -98,7 +98,11 @@ def test_new_symbols_are_exported():
     L = ctypes.CDLL(_lib.LIB_PATH)
     for n in names:
         assert n in _lib.SYMBOLS and hasattr(L, n), n
-    assert "uva_repeat.hip" in build.SOURCES and "uva_repeat.h" in build.SOURCES["uva_api.hip"]
+    assert "uva_repeat.hip" in build.SOURCES
+    # every unit that calls the kernel's launcher: the submit stages (through uva_net.h), the generic executor that shares
+    # uva_net.h with them, and the stateless uva_frame_diff entries
+    for user in ("uva_api.hip", "uva_generic_run.hip", "uva_frames.hip"):
+        assert "uva_repeat.h" in build.SOURCES[user], user
 
 
 def test_frame_diff_refuses_bad_arguments_and_fails_loudly_without_gpu(uva):

@@ -1,0 +1,565 @@
+// uva_frames.hip -- the stateless frame stages of the raw-video route outside a net: pixel formats, the resampler, repeated
+// frames, crop detection, the input window and deinterlacing.  Host code only: it calls the launchers of csrc/uva_pixfmt.hip,
+// csrc/uva_resize.hip, csrc/uva_repeat.hip, csrc/uva_crop.hip and csrc/uva_deint.hip on a per-device stream of its own.
+#include "../../include/uva.h"
+#include "uva_crop.h"
+#include "uva_deint.h"
+#include "uva_pixfmt.h"
+#include "uva_repeat.h"
+#include "uva_resize.h"
+#include "uva_rt.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace uva;
+
+// ---- raw-video pixel formats outside a net (uva_pix_convert, uva_pix_convert_device; csrc/uva_pixfmt.hip) -----------
+namespace {
+
+struct PixCtx {                          // per device: the conversions' own stream and buffers
+    hipStream_t stream = nullptr;
+    uint8_t *d_in = nullptr, *d_mid = nullptr, *d_out = nullptr;
+    size_t in_cap = 0, mid_cap = 0, out_cap = 0;
+    FrameDiffStats* d_stats = nullptr;   // uva_frame_diff's record
+    unsigned long long* d_sums = nullptr;    // uva_crop_sums' line sums: rows, then columns
+    size_t sums_cap = 0;
+};
+std::mutex g_pix_mu;
+PixCtx g_pix[kMaxDevices];
+
+int pix_ctx(int device, PixCtx** out)
+{
+    if (select_device(device)) return 1;
+    PixCtx& c = g_pix[device];
+    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    *out = &c;
+    return 0;
+}
+
+// uva_pix_convert_device is asynchronous: frames queued on the stream may still use a buffer about to be replaced
+int pix_grow(PixCtx& c, uint8_t** p, size_t* cap, size_t bytes)
+{
+    if (*cap >= bytes) return 0;
+    if (*cap) HIP_TRY(hipStreamSynchronize(c.stream));
+    return grow_dev(p, cap, bytes);
+}
+
+int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, int w, int colour, bool u16 = false)
+{
+    if (!in || !out) return fail("null frame pointer");
+    if (h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image size");
+    if (!pix_frame_bytes(in_fmt, 1, 1) || !pix_frame_bytes(out_fmt, 1, 1)) return fail("unknown pixel format");
+    if (!u16 && (in_fmt == PIX_BGR48LE || out_fmt == PIX_BGR48LE)) return fail("bgr48le is a 16-bit format: use the 16-bit entries (uva_pix_convert16)");
+    if (!pix_colour_ok(colour)) return fail("bad colour word");
+    return 0;
+}
+
+// d_in (in_fmt) -> d_out (out_fmt) on the context's stream, through the BGR of `bits` (BGR24 / BGR48LE) in d_mid when neither end
+// is that
+int pix_convert_launch(PixCtx& c, int bits, const uint8_t* d_in, int in_fmt, uint8_t* d_out, int out_fmt, int h, int w, int colour)
+{
+    const int native = bits == 16 ? PIX_BGR48LE : PIX_BGR24;
+    if (in_fmt == out_fmt) {
+        HIP_TRY(hipMemcpyAsync(d_out, d_in, pix_frame_bytes(in_fmt, h, w), hipMemcpyDeviceToDevice, c.stream));
+        return 0;
+    }
+    if (in_fmt == native) return pix_from_native(c.stream, bits, out_fmt, colour, d_in, d_out, h, w);
+    if (out_fmt == native) return pix_to_native(c.stream, bits, in_fmt, colour, d_in, d_out, h, w);
+    if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(native, h, w))) return 1;
+    return pix_to_native(c.stream, bits, in_fmt, colour, d_in, c.d_mid, h, w) ||
+           pix_from_native(c.stream, bits, out_fmt, colour, c.d_mid, d_out, h, w);
+}
+
+// uva_pix_convert / uva_pix_convert16: one frame, host to host
+int pix_convert_host(int device, int bits, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
+{
+    if (pix_check(in, in_fmt, out, out_fmt, h, w, colour, bits == 16)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
+    if (pix_convert_launch(*c, bits, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // namespace
+
+void uva::pix_release_all()
+{
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    for (int d = 0; d < kMaxDevices; ++d) {
+        PixCtx& c = g_pix[d];
+        if (!c.stream) continue;
+        (void)hipSetDevice(d);
+        (void)hipStreamSynchronize(c.stream);
+        for (uint8_t* p : {c.d_in, c.d_mid, c.d_out})
+            if (p) (void)hipFree(p);
+        if (c.d_stats) (void)hipFree(c.d_stats);
+        if (c.d_sums) (void)hipFree(c.d_sums);
+        (void)hipStreamDestroy(c.stream);
+        c = PixCtx();
+    }
+}
+
+// the packed frame `src` of fmt -> the net's BGR frame `bgr` at `bits` (8: u8 [h][w][3], 16: u16) on `stream` ...
+int uva::pix_to_native(hipStream_t stream, int bits, int fmt, int colour, const void* src, void* bgr, int h, int w)
+{
+    return bits == 16 ? tryhip(launch_pix16_to_bgr(stream, fmt, colour, src, (uint16_t*)bgr, h, w), "pix16_to_bgr")
+                      : tryhip(launch_pix_to_bgr(stream, fmt, colour, src, (uint8_t*)bgr, h, w), "pix_to_bgr");
+}
+
+// ... and back
+int uva::pix_from_native(hipStream_t stream, int bits, int fmt, int colour, const void* bgr, void* dst, int h, int w)
+{
+    return bits == 16 ? tryhip(launch_pix16_from_bgr(stream, fmt, colour, (const uint16_t*)bgr, dst, h, w), "pix16_from_bgr")
+                      : tryhip(launch_pix_from_bgr(stream, fmt, colour, (const uint8_t*)bgr, dst, h, w), "pix_from_bgr");
+}
+
+extern "C" {
+
+size_t uva_pix_frame_bytes(int fmt, int h, int w) { return pix_frame_bytes(fmt, h, w); }
+
+int uva_pix_convert(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
+{
+    return pix_convert_host(device, 8, in, in_fmt, out, out_fmt, h, w, colour);
+}
+
+int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out, int out_fmt, int h, int w, int colour,
+                           uva_net* after, uva_net* before)
+{
+    if (pix_check(d_in, in_fmt, d_out, out_fmt, h, w, colour)) return 1;
+    if (check_fence_nets(device, after, before, "uva_pix_convert_device")) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    if (fence_after(after, c->stream)) return 1;
+    if (pix_convert_launch(*c, 8, (const uint8_t*)d_in, in_fmt, (uint8_t*)d_out, out_fmt, h, w, colour)) return 1;
+    if (fence_before(before, c->stream)) return 1;
+    return 0;
+}
+
+int uva_pix_convert16(int device, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
+{
+    return pix_convert_host(device, 16, in, in_fmt, out, out_fmt, h, w, colour);
+}
+
+// ---- the resampler (csrc/uva_resize.hip) ----------------------------------------------------------
+int uva_resize_taps(int n_in, int n_out, int filter, int32_t* first, int16_t* taps, size_t cap, int* ntaps)
+{
+    if (const char* e = resize_axis_error(n_in, n_out, filter)) return fail(e);
+    const int t = resize_ntaps(n_in, n_out, filter);
+    if (ntaps) *ntaps = t;
+    if (!first || !taps || cap < (size_t)n_out * t) return fail("uva_resize_taps: the table needs n_out firsts and n_out * ntaps taps");
+    std::vector<int32_t> f;
+    std::vector<int16_t> tp;
+    if (resize_build_taps(n_in, n_out, filter, f, tp) != t) return fail("uva_resize_taps: the taps of a row do not fit");
+    std::copy(f.begin(), f.end(), first);
+    std::copy(tp.begin(), tp.end(), taps);
+    return 0;
+}
+
+namespace {
+int resize_check(const void* in, int h, int w, size_t in_stride, const void* out, int oh, int ow, size_t out_stride, int filter, int bits)
+{
+    if (!in || !out) return fail("null frame pointer");
+    if (bits != 8 && bits != 16) return fail("resize: bits must be 8 or 16");
+    if (const char* e = resize_axis_error(h, oh, filter)) return fail(e);
+    if (const char* e = resize_axis_error(w, ow, filter)) return fail(e);
+    if ((long long)h * w > (1ll << 28) || (long long)oh * ow > (1ll << 28)) return fail("bad image size");
+    const size_t bps = bits / 8;
+    if (in_stride < (size_t)w * 3 * bps || out_stride < (size_t)ow * 3 * bps) return fail("row stride too small");
+    if (bits == 16 && ((((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 1) != 0)) return fail("16-bit frames need 2-byte aligned rows");
+    return 0;
+}
+}  // namespace
+
+int uva_resize_device(int device, const void* d_in, int h, int w, size_t in_stride, void* d_out, int oh, int ow, size_t out_stride,
+                      int filter, int bits, uva_net* after, uva_net* before)
+{
+    if (resize_check(d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits)) return 1;
+    if (check_fence_nets(device, after, before, "uva_resize_device")) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    if (fence_after(after, c->stream)) return 1;
+    std::string err;
+    if (launch_resize(c->stream, device, d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits, &err)) return fail(err);
+    if (fence_before(before, c->stream)) return 1;
+    return 0;
+}
+
+int uva_resize(int device, const void* in, int h, int w, size_t in_stride, void* out, int oh, int ow, size_t out_stride, int filter,
+               int bits)
+{
+    if (resize_check(in, h, w, in_stride, out, oh, ow, out_stride, filter, bits)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    // the frames go up and come down with their row padding, so that the kernel works on the caller's strides; a padded
+    // result buffer goes up first (what lies between its rows comes back as it was)
+    const size_t in_row = (size_t)w * 3 * (bits / 8), out_row = (size_t)ow * 3 * (bits / 8);
+    const size_t nin = in_stride * (size_t)(h - 1) + in_row, nout = out_stride * (size_t)(oh - 1) + out_row;
+    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
+    if (out_stride != out_row) HIP_TRY(hipMemcpyAsync(c->d_out, out, nout, hipMemcpyHostToDevice, c->stream));
+    std::string err;
+    if (launch_resize(c->stream, device, c->d_in, h, w, in_stride, c->d_out, oh, ow, out_stride, filter, bits, &err)) return fail(err);
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- repeated frames (csrc/uva_repeat.hip) ---------------------------------------------------------
+namespace {
+int frame_diff_check(const void* a, const void* b, int fmt, int h, int w, int threshold, const unsigned long long* stats)
+{
+    if (!a || !b || !stats) return fail("null frame pointer");
+    if (h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image size");
+    if (!pix_frame_bytes(fmt, 1, 1) || !frame_diff_sample(fmt, nullptr, nullptr)) return fail("unknown pixel format");
+    if (threshold < 0 || threshold > 65535) return fail("uva_frame_diff: the threshold is 0 ... 65535 code values");
+    return 0;
+}
+
+// the record of the frames d_a, d_b on the conversions' stream, read back and waited for (g_pix_mu held)
+int frame_diff_run(PixCtx& c, const void* d_a, const void* d_b, int fmt, int h, int w, int threshold, unsigned long long* stats)
+{
+    if (!c.d_stats) HIP_TRY(hipMalloc((void**)&c.d_stats, sizeof(FrameDiffStats)));
+    FrameDiffStats st;
+    HIP_TRY(launch_frame_diff(c.stream, d_a, d_b, pix_frame_bytes(fmt, h, w), fmt, (unsigned)threshold, c.d_stats));
+    HIP_TRY(hipMemcpyAsync(&st, c.d_stats, sizeof st, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    stats[0] = st.over; stats[1] = st.max_abs; stats[2] = st.sad;
+    return 0;
+}
+}  // namespace
+
+int uva_frame_diff(int device, const void* a, const void* b, int fmt, int h, int w, int threshold, unsigned long long* stats)
+{
+    if (frame_diff_check(a, b, fmt, h, w, threshold, stats)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = pix_frame_bytes(fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, bytes) || pix_grow(*c, &c->d_out, &c->out_cap, bytes)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, a, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_out, b, bytes, hipMemcpyHostToDevice, c->stream));
+    return frame_diff_run(*c, c->d_in, c->d_out, fmt, h, w, threshold, stats);
+}
+
+int uva_frame_diff_device(int device, const void* d_a, const void* d_b, int fmt, int h, int w, int threshold, unsigned long long* stats)
+{
+    if (frame_diff_check(d_a, d_b, fmt, h, w, threshold, stats)) return 1;
+    if ((((uintptr_t)d_a | (uintptr_t)d_b) & 15) != 0) return fail("uva_frame_diff_device: the frames must start at 16-byte aligned addresses");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    return frame_diff_run(*c, d_a, d_b, fmt, h, w, threshold, stats);
+}
+
+// ---- crop detection and the input window (csrc/uva_crop.hip, csrc/uva_crop_host.cpp) ------------------
+namespace {
+int crop_sums_check(const void* frame, int fmt, int h, int w, const unsigned long long* rows, const unsigned long long* cols)
+{
+    if (!frame || !rows || !cols) return fail("null frame pointer");
+    if (!crop_sample(fmt).bytes || !pix_frame_bytes(fmt, 1, 1)) return fail("unknown pixel format");
+    if (h < 1 || w < 1 || (long long)h * w > (1ll << 28)) return fail("bad image size");
+    return 0;
+}
+
+// the bytes of a frame that the detector reads: the luma plane, which comes first, or all of a packed BGR frame
+size_t crop_read_bytes(int fmt, int h, int w)
+{
+    const CropSample cs = crop_sample(fmt);
+    return (size_t)h * w * cs.comps * cs.bytes;
+}
+
+// the line sums of d_frame on the conversions' stream, read back and waited for (g_pix_mu held)
+int crop_sums_run(PixCtx& c, const void* d_frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
+{
+    const size_t need = sizeof(unsigned long long) * ((size_t)h + w);
+    if (c.sums_cap < need) {
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        if (grow_dev(&c.d_sums, &c.sums_cap, need)) return 1;
+    }
+    HIP_TRY(launch_crop_sums(c.stream, d_frame, fmt, h, w, c.d_sums, c.d_sums + h, max_groups));
+    HIP_TRY(hipMemcpyAsync(rows, c.d_sums, sizeof(unsigned long long) * (size_t)h, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(cols, c.d_sums + h, sizeof(unsigned long long) * (size_t)w, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int crop_sums_host(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
+{
+    if (crop_sums_check(frame, fmt, h, w, rows, cols)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = crop_read_bytes(fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, bytes)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->d_in, frame, bytes, hipMemcpyHostToDevice, c->stream));
+    return crop_sums_run(*c, c->d_in, fmt, h, w, rows, cols, max_groups);
+}
+
+int pix_window_check(const void* in, int fmt, int src_h, int src_w, int x, int y, int h, int w, const void* out)
+{
+    if (!in || !out) return fail("null frame pointer");
+    if (const char* e = crop_window_error(fmt, src_h, src_w, x, y, h, w)) return fail(e);
+    return 0;
+}
+}  // namespace
+
+int uva_crop_sums(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols)
+{
+    return crop_sums_host(device, frame, fmt, h, w, rows, cols, 0);
+}
+
+int uva_debug_crop_sums(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
+{
+    if (max_groups < 0) return fail("uva_debug_crop_sums: max_groups is 0 (the kernel's own bound) or a number of workgroups");
+    return crop_sums_host(device, frame, fmt, h, w, rows, cols, max_groups);
+}
+
+int uva_crop_sums_device(int device, const void* d_frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols)
+{
+    if (crop_sums_check(d_frame, fmt, h, w, rows, cols)) return 1;
+    if (((uintptr_t)d_frame & 15) != 0) return fail("uva_crop_sums_device: the frame must start at a 16-byte aligned address");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    return crop_sums_run(*c, d_frame, fmt, h, w, rows, cols, 0);
+}
+
+int uva_crop_bounds(const unsigned long long* rows, const unsigned long long* cols, int fmt, int h, int w, int limit, int* bounds)
+{
+    if (const char* e = crop_bounds(rows, cols, fmt, h, w, limit, bounds)) return fail(e);
+    return 0;
+}
+
+int uva_crop_rect(const int* state, int round, int* rect)
+{
+    if (!state || !rect) return fail("uva_crop_rect: null pointer");
+    if (!crop_rect(state, round, rect)) return fail("uva_crop_rect: the state holds no rectangle");
+    return 0;
+}
+
+int uva_pix_window_check(int fmt, int src_h, int src_w, int x, int y, int h, int w)
+{
+    if (const char* e = crop_window_error(fmt, src_h, src_w, x, y, h, w)) return fail(e);
+    return 0;
+}
+
+int uva_pix_window(int device, const void* in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* out)
+{
+    if (pix_window_check(in, fmt, src_h, src_w, x, y, h, w, out)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    WindowPlane pl[3];
+    const int np = crop_window_planes(fmt, src_h, src_w, x, y, h, w, pl);
+    size_t at[3] = {0, 0, 0};
+    const size_t stage = pix_window_staging(pl, np, at), nout = pix_frame_bytes(fmt, h, w);
+    if (pix_grow(*c, &c->d_in, &c->in_cap, stage) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    // the window's rows go up at full width, one copy per plane; the kernel compacts their columns
+    for (int p = 0; p < np; ++p)
+        HIP_TRY(hipMemcpyAsync(c->d_in + at[p], (const uint8_t*)in + pl[p].src_off + (size_t)pl[p].row0 * pl[p].src_row,
+                               pl[p].src_row * (size_t)pl[p].rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_pix_window(c->stream, c->d_in, at, c->d_out, pl, np, crop_sample(fmt).bytes));
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_pix_window_device(int device, const void* d_in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* d_out)
+{
+    if (pix_window_check(d_in, fmt, src_h, src_w, x, y, h, w, d_out)) return 1;
+    if (((uintptr_t)d_out & 15) != 0) return fail("uva_pix_window_device: the result must start at a 16-byte aligned address");
+    if (((uintptr_t)d_in & (uintptr_t)(crop_sample(fmt).bytes - 1)) != 0) return fail("uva_pix_window_device: odd address of a frame of 16-bit words");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    WindowPlane pl[3];
+    const int np = crop_window_planes(fmt, src_h, src_w, x, y, h, w, pl);
+    size_t at[3] = {0, 0, 0};
+    for (int p = 0; p < np; ++p) at[p] = pl[p].src_off + (size_t)pl[p].row0 * pl[p].src_row;
+    HIP_TRY(launch_pix_window(c->stream, d_in, at, d_out, pl, np, crop_sample(fmt).bytes));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- deinterlacing (csrc/uva_deint.hip, csrc/uva_deint_host.cpp) ------------------------------------
+struct uva_deint {
+    int device = 0, fmt = 0, h = 0, w = 0, flags = 0;
+    size_t bytes = 0;
+    hipStream_t stream = nullptr;
+    uint8_t* d_frame[3] = {nullptr, nullptr, nullptr};     // frame k of the stream lies in d_frame[k % 3]
+    uint8_t* d_out[2] = {nullptr, nullptr};                // A, and B with UVA_DEINT_FIELD
+    long long pushed = 0;                                  // frames since the last reset
+};
+
+namespace {
+// everything the stateless entries refuse, before a GPU is looked for
+int deint_frames_check(const void* cur, int fmt, int h, int w, int flags, const void* out_a, const void* out_b)
+{
+    if (const char* e = deint_error(fmt, h, w, flags)) return fail(e);
+    if (!cur) return fail("null frame pointer");
+    if (!out_a && !out_b) return fail("deinterlace: neither output A nor output B is asked for");
+    if (out_b && !(flags & DEINT_FIELD)) return fail("deinterlace: output B exists with UVA_DEINT_FIELD only");
+    return 0;
+}
+
+int deint_frames_host(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b,
+                      int max_groups)
+{
+    if (deint_frames_check(cur, fmt, h, w, flags, out_a, out_b)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = deint_format(fmt, h, w).frame_bytes, slot = (bytes + 15) & ~(size_t)15;
+    // prev, cur, next in d_in; A, B in d_out (every frame at a multiple of 16 bytes)
+    if (pix_grow(*c, &c->d_in, &c->in_cap, 3 * slot) || pix_grow(*c, &c->d_out, &c->out_cap, 2 * slot)) return 1;
+    const uint8_t *d_cur = c->d_in + slot, *d_prev = d_cur, *d_next = d_cur;
+    HIP_TRY(hipMemcpyAsync(c->d_in + slot, cur, bytes, hipMemcpyHostToDevice, c->stream));
+    if (prev && prev != cur) {
+        HIP_TRY(hipMemcpyAsync(c->d_in, prev, bytes, hipMemcpyHostToDevice, c->stream));
+        d_prev = c->d_in;
+    }
+    if (next && next != cur) {
+        HIP_TRY(hipMemcpyAsync(c->d_in + 2 * slot, next, bytes, hipMemcpyHostToDevice, c->stream));
+        d_next = c->d_in + 2 * slot;
+    }
+    HIP_TRY(launch_deint(c->stream, d_prev, d_cur, d_next, fmt, h, w, flags, out_a ? c->d_out : nullptr, out_b ? c->d_out + slot : nullptr,
+                         max_groups));
+    if (out_a) HIP_TRY(hipMemcpyAsync(out_a, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_b) HIP_TRY(hipMemcpyAsync(out_b, c->d_out + slot, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the outputs of frame `k` of the handle's stream (prev / next: k -+ 1, or k itself at an end), downloaded and waited for
+int deint_emit(uva_deint* d, long long k, bool has_next, void* out_a, void* out_b, int* produced)
+{
+    const uint8_t* cur = d->d_frame[k % 3];
+    const uint8_t* prev = k > 0 ? d->d_frame[(k - 1) % 3] : cur;
+    const uint8_t* next = has_next ? d->d_frame[(k + 1) % 3] : cur;
+    const bool field = (d->flags & DEINT_FIELD) != 0;
+    HIP_TRY(launch_deint(d->stream, prev, cur, next, d->fmt, d->h, d->w, d->flags, d->d_out[0], field ? d->d_out[1] : nullptr, 0));
+    HIP_TRY(hipMemcpyAsync(out_a, d->d_out[0], d->bytes, hipMemcpyDeviceToHost, d->stream));
+    if (field) HIP_TRY(hipMemcpyAsync(out_b, d->d_out[1], d->bytes, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    *produced = field ? 2 : 1;
+    return 0;
+}
+}  // namespace
+
+int uva_deint_check(int fmt, int h, int w, int flags)
+{
+    if (const char* e = deint_error(fmt, h, w, flags)) return fail(e);
+    return 0;
+}
+
+int uva_deint_frames(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b)
+{
+    return deint_frames_host(device, prev, cur, next, fmt, h, w, flags, out_a, out_b, 0);
+}
+
+int uva_debug_deint_frames(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a,
+                           void* out_b, int max_groups)
+{
+    if (max_groups < 0) return fail("uva_debug_deint_frames: max_groups is 0 (the kernel's own bound) or a number of workgroups");
+    return deint_frames_host(device, prev, cur, next, fmt, h, w, flags, out_a, out_b, max_groups);
+}
+
+int uva_deint_frames_device(int device, const void* d_prev, const void* d_cur, const void* d_next, int fmt, int h, int w, int flags,
+                            void* d_out_a, void* d_out_b)
+{
+    if (deint_frames_check(d_cur, fmt, h, w, flags, d_out_a, d_out_b)) return 1;
+    if ((((uintptr_t)d_prev | (uintptr_t)d_cur | (uintptr_t)d_next | (uintptr_t)d_out_a | (uintptr_t)d_out_b) & 15) != 0)
+        return fail("uva_deint_frames_device: the frames must start at 16-byte aligned addresses");
+    std::lock_guard<std::mutex> lk(g_pix_mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    HIP_TRY(launch_deint(c->stream, d_prev ? d_prev : d_cur, d_cur, d_next ? d_next : d_cur, fmt, h, w, flags, d_out_a, d_out_b, 0));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_debug_deint_host(const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, void* out_a, void* out_b)
+{
+    if (deint_frames_check(cur, fmt, h, w, flags, out_a, out_b)) return 1;
+    deint_host((const uint8_t*)prev, (const uint8_t*)cur, (const uint8_t*)next, fmt, h, w, flags, (uint8_t*)out_a, (uint8_t*)out_b);
+    return 0;
+}
+
+int uva_deint_create(int device, int fmt, int h, int w, int flags, uva_deint** out)
+{
+    if (!out) return fail("uva_deint_create: null pointer");
+    *out = nullptr;
+    if (const char* e = deint_error(fmt, h, w, flags)) return fail(e);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail("no HIP device available: libuva has no CPU path");
+    if (device < 0 || device >= count) return fail("HIP device " + std::to_string(device) + " does not exist");
+    HIP_TRY(hipSetDevice(device));
+    uva_deint* d = new uva_deint;
+    d->device = device; d->fmt = fmt; d->h = h; d->w = w; d->flags = flags;
+    d->bytes = deint_format(fmt, h, w).frame_bytes;
+    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipMalloc((void**)&d->d_frame[k], d->bytes);
+    for (int k = 0; k < ((flags & DEINT_FIELD) ? 2 : 1) && e == hipSuccess; ++k) e = hipMalloc((void**)&d->d_out[k], d->bytes);
+    if (e != hipSuccess) {
+        uva_deint_destroy(d);
+        return fail(std::string("uva_deint_create: ") + hipGetErrorString(e));
+    }
+    *out = d;
+    return 0;
+}
+
+int uva_deint_push(uva_deint* d, const void* frame, void* out_a, void* out_b, int* produced)
+{
+    if (!d || !produced) return fail("uva_deint_push: null pointer");
+    *produced = 0;
+    if (!out_a || ((d->flags & DEINT_FIELD) && !out_b)) return fail("uva_deint_push: null output frame");
+    HIP_TRY(hipSetDevice(d->device));
+    if (!frame) {                                   // flush: the last frame has no next
+        const long long n = d->pushed;
+        d->pushed = 0;
+        return n ? deint_emit(d, n - 1, false, out_a, out_b, produced) : 0;
+    }
+    // (frame k - 2's slot is free: the outputs of frame k - 1, the last to read it, were waited for)
+    const long long k = d->pushed;
+    HIP_TRY(hipMemcpyAsync(d->d_frame[k % 3], frame, d->bytes, hipMemcpyHostToDevice, d->stream));
+    d->pushed = k + 1;
+    if (k == 0) {
+        HIP_TRY(hipStreamSynchronize(d->stream));   // (`frame` is the caller's again when the call returns)
+        return 0;
+    }
+    return deint_emit(d, k - 1, true, out_a, out_b, produced);
+}
+
+int uva_deint_reset(uva_deint* d)
+{
+    if (!d) return fail("uva_deint_reset: null pointer");
+    d->pushed = 0;
+    return 0;
+}
+
+void uva_deint_destroy(uva_deint* d)
+{
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    for (uint8_t* p : {d->d_frame[0], d->d_frame[1], d->d_frame[2], d->d_out[0], d->d_out[1]})
+        if (p) (void)hipFree(p);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+}
+
+}  // extern "C"

@@ -69,5 +69,10 @@ hipError_t launch_pix_from_bgr(hipStream_t stream, int fmt, int colour, const ui
 hipError_t launch_pix16_to_bgr(hipStream_t stream, int fmt, int colour, const void* src, uint16_t* bgr, int h, int w);
 hipError_t launch_pix16_from_bgr(hipStream_t stream, int fmt, int colour, const uint16_t* bgr, void* dst, int h, int w);
 
+// The four above by the net's sample width, errors through uva_last_error (csrc/uva_frames.hip; the submit stages use them too):
+// the packed frame `src` of fmt -> the net's BGR frame `bgr` at `bits` (8: u8 [h][w][3], 16: u16) on `stream`, and back
+int pix_to_native(hipStream_t stream, int bits, int fmt, int colour, const void* src, void* bgr, int h, int w);
+int pix_from_native(hipStream_t stream, int bits, int fmt, int colour, const void* bgr, void* dst, int h, int w);
+
 }  // namespace uva
 #endif

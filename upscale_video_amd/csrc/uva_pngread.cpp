@@ -10,6 +10,8 @@
 // length), a corrupt file is an error, never a crash.  8-bit RGB / RGBA / grey (+alpha), non-interlaced -- what ffmpeg's
 // `%d.extract.png` and cv2.imwrite produce; anything else returns 2 and the caller uses a general reader.  png_read_bgr16 reads
 // the same kinds at 8 or 16 bits into u16 BGR (the PNG route at 16 bits).
+#include "uva_pngread.h"
+
 #include <cstddef>
 #include <cstdint>
 #include <cstring>

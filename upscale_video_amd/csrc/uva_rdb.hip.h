@@ -24,8 +24,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "uva_kernels.hip.h"
+#include "uva_devutil.hip.h"
+#include "uva_generic_dev.h"
+#include "uva_plan.h"
 #include "uva_sw.h"
+
+#ifndef UVA_MEMTIME           // (as csrc/uva_sub10.hip.h: uva_kernels.hip.h, which has it too, is not included here)
+#ifdef UVA_INSTRUMENT
+#define UVA_MEMTIME() __builtin_amdgcn_s_memtime()
+#else
+#define UVA_MEMTIME() 0ull
+#endif
+#endif
 
 #define UVA_SW_D 3
 #define UVA_RA_D 2       // rdb4_kernel: k-steps (of 3 fragment reads) the reads run ahead of the MFMAs
@@ -622,7 +632,6 @@ __global__ __launch_bounds__(256, 1) void g_conv3_sk(GSwArgs a)
 // are written as zero (the next convolution's padding), rows above a segment's first output row are recomputed (3 of x1, 2
 // of x2, 1 of x3).  Rounding points are the layer-by-layer executor's: every convolution result -> fp16, the two sums as
 // g_axpby1 of fp16 operands.
-struct RdbSeg { int c0, yb, ye, own0, own1, plane, pad1, pad2; };   // of plane `plane`: computed columns [c0, c0+48); output rows [yb, ye), columns [own0, own1)
 
 struct RdbArgs {
     _Float16* arr[GEN_MAX_PLANES];   // per plane: the dense chain's array [(h+3)][(w+2)][stride]: channels 0..63 = x (read), 64..191 = x1..x4 (written)
@@ -645,7 +654,7 @@ struct RdbArgs {
                                   // at the barrier, barrier passed} of its first segment here (s_memtime ticks)
 };
 
-constexpr int RA_C = 48, RA_RC = 50, RA_NF = 3;
+constexpr int RA_RC = 50, RA_NF = 3;             // (RA_C = 48: uva_generic_dev.h)
 constexpr int RA_CHB = RA_RC * 64;                                   // one chunk row: 3200 bytes
 constexpr int RA_XS = 10, RA_1S = 8, RA_2S = 6, RA_3S = 4;           // ring rows
 constexpr int RA_X_OFF = 0, RA_X1_OFF = RA_X_OFF + RA_XS * 2 * RA_CHB, RA_X2_OFF = RA_X1_OFF + RA_1S * RA_CHB,
