@@ -61,7 +61,8 @@ extern "C" {
                                    8-bit stage keeps its kernels and its bytes)
                                15 + deinterlacing: + uva_deint_check, uva_deint_frames, uva_deint_frames_device, uva_debug_deint_frames,
                                    uva_debug_deint_host, uva_deint_create, uva_deint_push, uva_deint_reset, uva_deint_destroy,
-                                   UVA_DEINT_* (additive: nothing runs unless asked for) */
+                                   UVA_DEINT_* (additive: nothing runs unless asked for)
+                               15 + live resources: + uva_debug_live_resources (additive: a test hook) */
 
 typedef struct uva_net uva_net;
 
@@ -81,6 +82,11 @@ int uva_get_gpu_pci_bus_id(int index, char* out, size_t out_len);
 /* ncnn.destroy_gpu_instance()     upscale/upscale_processing.py:292, :458
  * Frees every cached device allocation of every live net (nets stay loadable). */
 void uva_destroy_gpu_instance(void);
+/* Test hook: the HIP resources the library holds at this moment -- counts[0] device buffers, [1] page-locked host buffers,
+ * [2] streams, [3] events.  Memory from uva_host_alloc belongs to the caller and is not counted.  All four are zero before
+ * the first call that uses a GPU, and again once every uva_deint and every net is destroyed and uva_destroy_gpu_instance
+ * has run. */
+void uva_debug_live_resources(long long counts[4]);
 
 /* ---- net life cycle ---------------------------------------------------------------- */
 

@@ -45,6 +45,8 @@ OPTIONAL_SYMBOLS += ["uva_crop_sums", "uva_crop_sums_device", "uva_debug_crop_su
 # 15 + deinterlacing (additive and optional in the same way: ncnn.deint_frames, ncnn.Deinterlacer and rawvideo's --deinterlace ask)
 OPTIONAL_SYMBOLS += ["uva_deint_check", "uva_deint_frames", "uva_deint_frames_device", "uva_debug_deint_frames", "uva_debug_deint_host",
                      "uva_deint_create", "uva_deint_push", "uva_deint_reset", "uva_deint_destroy"]
+# 15 + live resources (additive and optional in the same way: a test hook, tests/test_gpu_live_resources.py asks)
+OPTIONAL_SYMBOLS += ["uva_debug_live_resources"]
 SYMBOLS += OPTIONAL_SYMBOLS
 INSTRUMENT_SYMBOLS = ["uva_net_debug_trunk_stamps", "uva_net_debug_rdb_stamps"]     # only in a -DUVA_INSTRUMENT build (build.py --instrument)
 
@@ -168,6 +170,7 @@ def load():
     decl("uva_denoise_u16_device", [c_i, c_p, c_i, c_i, c_sz, c_p, c_sz, ctypes.c_float, ctypes.c_float, c_p, c_p])
     decl("uva_debug_denoise16_stage", [c_i, c_i, c_p, c_i, c_i, ctypes.c_float, c_p])
     decl("uva_destroy_gpu_instance", [], "void")
+    decl("uva_debug_live_resources", [pll], "void")
     decl("uva_net_destroy", [c_p], "void")
     decl("uva_net_set_device", [c_p, c_i])
     decl("uva_net_load_param", [c_p, ctypes.c_char_p])

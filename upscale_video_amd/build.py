@@ -14,19 +14,19 @@ LIB = os.path.join(_HERE, "libuva.so")
 _UVA_H = os.path.join("..", "..", "include", "uva.h")
 # source -> the headers it includes (directly or not)
 SOURCES = {
-    "uva_api.hip": ["uva_kernels.hip.h", "uva_devutil.hip.h", "uva_net.h", "uva_rt.h", "uva_wino.h", "uva_sub5.h", "uva_sub10.h", "uva_sw.h", "uva_generic_dev.h", "uva_generic.h",
+    "uva_api.hip": ["uva_kernels.hip.h", "uva_devutil.hip.h", "uva_net.h", "uva_rt.h", "uva_own.h", "uva_wino.h", "uva_sub5.h", "uva_sub10.h", "uva_sw.h", "uva_generic_dev.h", "uva_generic.h",
                     "uva_model.h", "uva_png.h", "uva_pixfmt.h", "uva_plan.h", "uva_resize.h", "uva_repeat.h", "uva_crop.h", "uva_submit.h", _UVA_H],
-    "uva_generic_run.hip": ["uva_generic.hip.h", "uva_rdb.hip.h", "uva_generic_dev.h", "uva_generic.h", "uva_sw.h", "uva_devutil.hip.h", "uva_net.h", "uva_rt.h", "uva_sub10.h",
+    "uva_generic_run.hip": ["uva_generic.hip.h", "uva_rdb.hip.h", "uva_generic_dev.h", "uva_generic.h", "uva_sw.h", "uva_devutil.hip.h", "uva_net.h", "uva_rt.h", "uva_own.h", "uva_sub10.h",
                             "uva_model.h", "uva_pixfmt.h", "uva_plan.h", "uva_repeat.h", "uva_crop.h", "uva_submit.h", _UVA_H],
-    "uva_denoise.hip": ["uva_denoise.hip.h", "uva_denoise16.hip.h", "uva_denoise16_tables.h", "uva_rt.h", _UVA_H],
-    "uva_png.hip": ["uva_png.hip.h", "uva_png.h", "uva_pngread.h", "uva_rt.h", _UVA_H],
-    "uva_frames.hip": ["uva_pixfmt.h", "uva_resize.h", "uva_repeat.h", "uva_crop.h", "uva_deint.h", "uva_rt.h", _UVA_H],
+    "uva_denoise.hip": ["uva_denoise.hip.h", "uva_denoise16.hip.h", "uva_denoise16_tables.h", "uva_rt.h", "uva_own.h", _UVA_H],
+    "uva_png.hip": ["uva_png.hip.h", "uva_png.h", "uva_pngread.h", "uva_rt.h", "uva_own.h", _UVA_H],
+    "uva_frames.hip": ["uva_pixfmt.h", "uva_resize.h", "uva_repeat.h", "uva_crop.h", "uva_deint.h", "uva_rt.h", "uva_own.h", _UVA_H],
     "uva_wino.hip": ["uva_wino.hip.h", "uva_wino.h", "uva_devutil.hip.h", "uva_plan.h"],
     "uva_sub5.hip": ["uva_sub5.hip.h", "uva_sub5.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
     "uva_sub10.hip": ["uva_sub10.hip.h", "uva_sub10_body.hip.h", "uva_sub10.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
     "uva_sww.hip": ["uva_sww.hip.h", "uva_sw.h", "uva_devutil.hip.h", "uva_plan.h"],
     "uva_pixfmt.hip": ["uva_pixfmt.h"],
-    "uva_resize.hip": ["uva_resize.h"],
+    "uva_resize.hip": ["uva_resize.h", "uva_own.h"],
     "uva_repeat.hip": ["uva_repeat.h", "uva_pixfmt.h"],
     "uva_crop.hip": ["uva_crop.h", "uva_pixfmt.h"],
     "uva_crop_host.cpp": ["uva_crop.h"],

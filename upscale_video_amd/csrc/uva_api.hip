@@ -241,23 +241,17 @@ int launch_sub5(uva_net* n, Workspace* ws, const void* src, size_t src_stride, v
             ws->sub5_unfit = true;
             return 2;
         }
-        // into locals first: a failure half way leaves nothing in the workspace (the next call starts over instead of leaking)
-        char* d_mid = nullptr;
-        uint4* d_rows = nullptr;
-        int* d_nrows = nullptr;
-        hipError_t e = hipMalloc((void**)&d_mid, (size_t)ws->h * ws->w * S5_MIDB);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_rows, rows.size() * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_nrows, nrows.size() * sizeof(int));
+        DevPtr<char> d_mid;
+        DevPtr<uint4> d_rows;
+        DevPtr<int> d_nrows;
+        hipError_t e = alloc_into(d_mid, (size_t)ws->h * ws->w * S5_MIDB);
+        if (e == hipSuccess) e = alloc_into(d_rows, rows.size() * sizeof(uint4));
+        if (e == hipSuccess) e = alloc_into(d_nrows, nrows.size() * sizeof(int));
         if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(uint4), hipMemcpyHostToDevice, n->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_nrows, nrows.data(), nrows.size() * sizeof(int), hipMemcpyHostToDevice, n->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(n->stream);
-        if (e != hipSuccess) {
-            if (d_mid) (void)hipFree(d_mid);
-            if (d_rows) (void)hipFree(d_rows);
-            if (d_nrows) (void)hipFree(d_nrows);
-            return fail(std::string("sub5 workspace: ") + hipGetErrorString(e));
-        }
-        ws->d_mid5 = d_mid; ws->d_rows5 = d_rows; ws->d_nrows5 = d_nrows;
+        if (e != hipSuccess) return fail(std::string("sub5 workspace: ") + hipGetErrorString(e));
+        ws->d_mid5 = std::move(d_mid); ws->d_rows5 = std::move(d_rows); ws->d_nrows5 = std::move(d_nrows);
     }
     for (int part = 0; part < 2; ++part) {
         Sub5Args a;
@@ -296,20 +290,16 @@ int ensure_sub10_rows(uva_net* n, Workspace* ws, int frames)
             ws->sub10_max_batch = frames - 1;
             return 2;
         }
-        uint4* d_rows = nullptr;
-        int* d_nrows = nullptr;
-        hipError_t e = hipMalloc((void**)&d_rows, rows.size() * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_nrows, nrows.size() * sizeof(int));
+        DevPtr<uint4> d_rows;
+        DevPtr<int> d_nrows;
+        hipError_t e = alloc_into(d_rows, rows.size() * sizeof(uint4));
+        if (e == hipSuccess) e = alloc_into(d_nrows, nrows.size() * sizeof(int));
         if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(uint4), hipMemcpyHostToDevice, n->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_nrows, nrows.data(), nrows.size() * sizeof(int), hipMemcpyHostToDevice, n->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(n->stream);
-        if (e != hipSuccess) {                 // nothing half-made stays in the workspace
-            if (d_rows) (void)hipFree(d_rows);
-            if (d_nrows) (void)hipFree(d_nrows);
-            return fail(std::string("sub10 row table: ") + hipGetErrorString(e));
-        }
-        ws->d_rows10[bi] = d_rows;
-        ws->d_nrows10[bi] = d_nrows;
+        if (e != hipSuccess) return fail(std::string("sub10 row table: ") + hipGetErrorString(e));
+        ws->d_rows10[bi] = std::move(d_rows);
+        ws->d_nrows10[bi] = std::move(d_nrows);
     }
     return 0;
 }
@@ -402,6 +392,127 @@ int launch_head(uva_net* n, bool f32, const HeadArgs& a, bool u16 = false)
     return 0;
 }
 
+// the net's weights on its device, into `d` (all of it, or an error: ensure_device keeps nothing of a `d` that is not ready)
+int build_device(const uva_net* n, NetDevice& d)
+{
+    HIP_TRY(make_stream(d.stream));
+    HIP_TRY(alloc_into(d.d_sink, 64 * 128 + 256));
+    if (n->generic) {
+        // generic graph: every convolution's MFMA image ([tap][cin/32][cout/16][lane][8]) and padded bias
+        const GenericGraph& gg = n->gg;
+        d.gd.convs.resize(gg.convs.size());
+        for (const GLayer& gl : gg.layers) {
+            if (gl.kind != GLayer::CONV) continue;
+            const ConvWeights& c = gg.convs[gl.conv];
+            GenericDevice::ConvDev& cd = d.gd.convs[gl.conv];
+            cd.cin_pad = GenericDevice::pad32(c.cin);
+            cd.cout_pad = (c.cout + 15) / 16 * 16;
+            std::vector<uint16_t> pk;
+            pack_generic(c, gl.ksize, cd.cin_pad, cd.cout_pad, pk);
+            if (upload(cd.wpk, pk.data(), pk.size() * 2, d.stream)) return 1;
+            if (cd.cout_pad <= 64 && cd.cin_pad <= 192 && g_conv3_lds_bytes(cd.cin_pad, cd.cout_pad / 16, gl.ksize) <= 160 * 1024) {
+                std::vector<uint16_t> pkl;
+                pack_generic(c, gl.ksize, cd.cin_pad, cd.cout_pad, pkl, true);
+                if (upload(cd.wpk_lds, pkl.data(), pkl.size() * 2, d.stream)) return 1;
+                HIP_TRY(hipStreamSynchronize(d.stream));
+            }
+            if (gl.ksize == 3 && cd.cin_pad == 192 && cd.cout_pad == 64) {           // a dense block's last convolution: g_conv3_sww
+                std::vector<uint16_t> pkw;
+                pack_generic_wino(c, cd.cin_pad, cd.cout_pad, pkw);
+                if (upload(cd.wpk_w, pkw.data(), pkw.size() * 2, d.stream)) return 1;
+                HIP_TRY(hipStreamSynchronize(d.stream));
+            }
+            std::vector<float> b((size_t)cd.cout_pad, 0.f);
+            std::copy(c.bias.begin(), c.bias.end(), b.begin());
+            if (upload(cd.bias, b.data(), b.size() * 4, d.stream)) return 1;
+            HIP_TRY(hipStreamSynchronize(d.stream));
+        }
+        d.gd.rdbs = find_rdbs(gg);
+        d.gd.prelu.resize(gg.prelu.size());
+        for (size_t i = 0; i < gg.prelu.size(); ++i) {
+            if (upload(d.gd.prelu[i], gg.prelu[i].data(), gg.prelu[i].size() * 4, d.stream)) return 1;
+            HIP_TRY(hipStreamSynchronize(d.stream));
+        }
+        d.dev_ready = true;
+        return 0;
+    }
+    // weights: head, trunk..., tail
+    const Graph& g = n->g;
+    d.layers.resize(g.convs.size());
+    for (size_t i = 0; i < g.convs.size(); ++i) {
+        std::vector<uint16_t> pk;
+        int mf = 0;
+        if (i == 0) pack_head(g.convs[i], pk, &mf);
+        else if (g.nf == 64 && i + 1 < g.convs.size()) { pack_trunk64(g.convs[i], pk); mf = 2; }   // trunk_kernel<64>
+        else pack_conv3x3(g.convs[i], g.nf, pk, nullptr, &mf);
+        DeviceLayer& dl = d.layers[i];
+        if (upload(dl.wpk, pk.data(), pk.size() * 2, d.stream)) return 1;
+        std::vector<uint16_t> pkw;
+        if (g.nf == 64 && i > 0 && i + 1 < g.convs.size()) {
+            // Pairs are (1, 2), (3, 4), ...: an odd layer is the first of its launch.  With the PReLU on packed fp16 a channel
+            // whose slope exceeds 1 is computed negated (uva_wino.h): the first layer's stay so on their way through LDS into
+            // the second layer (in_sign), the second layer's get their sign back in front of the stores.
+            std::vector<float> sin(64, 1.f), sout(64, 1.f), bw(64, 0.f);
+            if (n->act16) {
+                if (!(i & 1))
+                    for (int c = 0; c < 64; ++c) sin[c] = g.slopes[i - 1][c] > 1.f ? -1.f : 1.f;
+                for (int c = 0; c < 64; ++c) {
+                    sout[c] = g.slopes[i][c] > 1.f ? -1.f : 1.f;
+                    dl.flip_w = dl.flip_w || sout[c] < 0.f;
+                }
+            }
+            for (int c = 0; c < 64; ++c) bw[c] = sout[c] * g.convs[i].bias[c];
+            pack_trunk64_wino(g.convs[i], pkw, sin.data(), sout.data());
+            if (upload(dl.wpk_w, pkw.data(), pkw.size() * 2, d.stream)) return 1;
+            if (upload(dl.bias_w, bw.data(), bw.size() * 4, d.stream)) return 1;
+            HIP_TRY(hipStreamSynchronize(d.stream));
+            if (n->act16 && (i & 1) && i >= 3) {
+                // first layer of a launch behind another launch: a second image for an input whose flipped channels arrive negated
+                bool any = false;
+                for (int c = 0; c < 64; ++c) {
+                    sin[c] = g.slopes[i - 1][c] > 1.f ? -1.f : 1.f;
+                    any = any || sin[c] < 0.f;
+                }
+                if (any) {
+                    pack_trunk64_wino(g.convs[i], pkw, sin.data(), sout.data());
+                    if (upload(dl.wpk_wn, pkw.data(), pkw.size() * 2, d.stream)) return 1;
+                    HIP_TRY(hipStreamSynchronize(d.stream));
+                }
+            }
+        }
+        std::vector<uint16_t> pk16;
+        if (g.nf == 64 && (g.scale == 2 || g.scale == 4) && i + 1 == g.convs.size()) {
+            pack_tail64(g.convs[i], pk16);
+            if (upload(dl.wpk16, pk16.data(), pk16.size() * 2, d.stream)) return 1;
+        }
+        if (g.nf == 24 && g.scale == 1 && g.convs.size() == (size_t)S10_NL) {
+            // channels whose PReLU slope exceeds 1 travel negated between the layers (uva_model.h pack_sub16)
+            std::vector<float> sin(g.convs[i].cin, 1.f), sout(g.convs[i].cout, 1.f), bs(32, 0.f);
+            if (i > 0)
+                for (int c = 0; c < g.convs[i].cin; ++c) sin[c] = g.slopes[i - 1][c] > 1.f ? -1.f : 1.f;
+            if (i + 1 < g.convs.size())
+                for (int c = 0; c < g.convs[i].cout; ++c) sout[c] = g.slopes[i][c] > 1.f ? -1.f : 1.f;
+            const int brow = g.convs[i].cout == 3 ? 4 : 1;       // (the last layer's channel j sits in MFMA row 4j: pack_sub16)
+            for (int c = 0; c < g.convs[i].cout; ++c) bs[brow * c] = sout[c] * g.convs[i].bias[c];
+            std::vector<uint16_t> pks;
+            pack_sub16(g.convs[i], pks, nullptr, nullptr, sin.data(), sout.data());
+            if (upload(dl.wpk_s10, pks.data(), pks.size() * 2, d.stream)) return 1;
+            if (upload(dl.bias_s10, bs.data(), bs.size() * 4, d.stream)) return 1;
+            HIP_TRY(hipStreamSynchronize(d.stream));
+        }
+        std::vector<float> b((size_t)mf * 32, 0.f), s((size_t)mf * 32, 0.f);
+        std::copy(g.convs[i].bias.begin(), g.convs[i].bias.end(), b.begin());
+        if (upload(dl.bias, b.data(), b.size() * 4, d.stream)) return 1;
+        if (i + 1 < g.convs.size()) {
+            std::copy(g.slopes[i].begin(), g.slopes[i].end(), s.begin());
+            if (upload(dl.slope, s.data(), s.size() * 4, d.stream)) return 1;
+        }
+        HIP_TRY(hipStreamSynchronize(d.stream));   // pk / b / s go out of scope
+    }
+    d.dev_ready = true;
+    return 0;
+}
+
 int ensure_device(uva_net* n)
 {
     if (n->generic ? !(n->gg.param_loaded && n->gg.model_loaded) : !(n->g.param_loaded && n->g.model_loaded))
@@ -421,14 +532,6 @@ int ensure_device(uva_net* n)
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(std::string("libuva is built for gfx950 (MI355X) only; device is ") + prop.gcnArchName);
     n->ncu = prop.multiProcessorCount;
-    // dev_ready is set only once every upload below has succeeded; any failure on the way releases what
-    // was allocated (free_device works on partial state), so a later call starts from scratch
-    n->dev_partial = true;
-    struct Undo {
-        uva_net* n;
-        ~Undo() { if (!n->dev_ready) n->free_device(); }
-    } undo{n};
-    HIP_TRY(hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking));
     if (const char* e = uva::debug_env("UVA_TRUNK_FUSION")) n->fuse_pairs = std::atoi(e) != 0;
     if (const char* e = uva::debug_env("UVA_TRUNK_WINO")) n->wino = std::atoi(e) != 0;
     if (const char* e = uva::debug_env("UVA_TW_ACT16")) n->act16 = std::atoi(e) != 0;
@@ -437,120 +540,14 @@ int ensure_device(uva_net* n)
     if (const char* e = uva::debug_env("UVA_SUB5")) n->split5 = std::atoi(e) != 0;
     if (const char* e = uva::debug_env("UVA_GENERIC_LDS")) n->generic_lds_conv = std::atoi(e) != 0;
     if (const char* e = uva::debug_env("UVA_GENERIC_FUSE_ADD")) n->generic_fuse_add = std::atoi(e) != 0;
-    HIP_TRY(hipMalloc((void**)&n->d_sink, 64 * 128 + 256));
-    if (n->generic) {
-        // generic graph: every convolution's MFMA image ([tap][cin/32][cout/16][lane][8]) and padded bias
-        const GenericGraph& gg = n->gg;
-        n->gd.convs.resize(gg.convs.size());
-        for (const GLayer& gl : gg.layers) {
-            if (gl.kind != GLayer::CONV) continue;
-            const ConvWeights& c = gg.convs[gl.conv];
-            GenericDevice::ConvDev& cd = n->gd.convs[gl.conv];
-            cd.cin_pad = GenericDevice::pad32(c.cin);
-            cd.cout_pad = (c.cout + 15) / 16 * 16;
-            std::vector<uint16_t> pk;
-            pack_generic(c, gl.ksize, cd.cin_pad, cd.cout_pad, pk);
-            if (upload(&cd.wpk, pk.data(), pk.size() * 2, n->stream)) return 1;
-            if (cd.cout_pad <= 64 && cd.cin_pad <= 192 && g_conv3_lds_bytes(cd.cin_pad, cd.cout_pad / 16, gl.ksize) <= 160 * 1024) {
-                std::vector<uint16_t> pkl;
-                pack_generic(c, gl.ksize, cd.cin_pad, cd.cout_pad, pkl, true);
-                if (upload(&cd.wpk_lds, pkl.data(), pkl.size() * 2, n->stream)) return 1;
-                HIP_TRY(hipStreamSynchronize(n->stream));
-            }
-            if (gl.ksize == 3 && cd.cin_pad == 192 && cd.cout_pad == 64) {           // a dense block's last convolution: g_conv3_sww
-                std::vector<uint16_t> pkw;
-                pack_generic_wino(c, cd.cin_pad, cd.cout_pad, pkw);
-                if (upload(&cd.wpk_w, pkw.data(), pkw.size() * 2, n->stream)) return 1;
-                HIP_TRY(hipStreamSynchronize(n->stream));
-            }
-            std::vector<float> b((size_t)cd.cout_pad, 0.f);
-            std::copy(c.bias.begin(), c.bias.end(), b.begin());
-            if (upload(&cd.bias, b.data(), b.size() * 4, n->stream)) return 1;
-            HIP_TRY(hipStreamSynchronize(n->stream));
-        }
-        n->gd.rdbs = find_rdbs(gg);
-        n->gd.prelu.assign(gg.prelu.size(), nullptr);
-        for (size_t i = 0; i < gg.prelu.size(); ++i) {
-            if (upload(&n->gd.prelu[i], gg.prelu[i].data(), gg.prelu[i].size() * 4, n->stream)) return 1;
-            HIP_TRY(hipStreamSynchronize(n->stream));
-        }
-        n->dev_ready = true;
-        return 0;
+    // built in a local and moved in when complete: a failure on the way leaves the net without device state, and a later
+    // call starts from scratch
+    NetDevice d;
+    if (build_device(n, d)) {
+        if (d.stream) (void)hipStreamSynchronize(d.stream);      // (uploads may be queued still)
+        return 1;
     }
-    // weights: head, trunk..., tail
-    const Graph& g = n->g;
-    n->layers.resize(g.convs.size());
-    for (size_t i = 0; i < g.convs.size(); ++i) {
-        std::vector<uint16_t> pk;
-        int mf = 0;
-        if (i == 0) pack_head(g.convs[i], pk, &mf);
-        else if (g.nf == 64 && i + 1 < g.convs.size()) { pack_trunk64(g.convs[i], pk); mf = 2; }   // trunk_kernel<64>
-        else pack_conv3x3(g.convs[i], g.nf, pk, nullptr, &mf);
-        DeviceLayer& dl = n->layers[i];
-        if (upload(&dl.wpk, pk.data(), pk.size() * 2, n->stream)) return 1;
-        std::vector<uint16_t> pkw;
-        if (g.nf == 64 && i > 0 && i + 1 < g.convs.size()) {
-            // Pairs are (1, 2), (3, 4), ...: an odd layer is the first of its launch.  With the PReLU on packed fp16 a channel
-            // whose slope exceeds 1 is computed negated (uva_wino.h): the first layer's stay so on their way through LDS into
-            // the second layer (in_sign), the second layer's get their sign back in front of the stores.
-            std::vector<float> sin(64, 1.f), sout(64, 1.f), bw(64, 0.f);
-            if (n->act16) {
-                if (!(i & 1))
-                    for (int c = 0; c < 64; ++c) sin[c] = g.slopes[i - 1][c] > 1.f ? -1.f : 1.f;
-                for (int c = 0; c < 64; ++c) {
-                    sout[c] = g.slopes[i][c] > 1.f ? -1.f : 1.f;
-                    dl.flip_w = dl.flip_w || sout[c] < 0.f;
-                }
-            }
-            for (int c = 0; c < 64; ++c) bw[c] = sout[c] * g.convs[i].bias[c];
-            pack_trunk64_wino(g.convs[i], pkw, sin.data(), sout.data());
-            if (upload(&dl.wpk_w, pkw.data(), pkw.size() * 2, n->stream)) return 1;
-            if (upload(&dl.bias_w, bw.data(), bw.size() * 4, n->stream)) return 1;
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            if (n->act16 && (i & 1) && i >= 3) {
-                // first layer of a launch behind another launch: a second image for an input whose flipped channels arrive negated
-                bool any = false;
-                for (int c = 0; c < 64; ++c) {
-                    sin[c] = g.slopes[i - 1][c] > 1.f ? -1.f : 1.f;
-                    any = any || sin[c] < 0.f;
-                }
-                if (any) {
-                    pack_trunk64_wino(g.convs[i], pkw, sin.data(), sout.data());
-                    if (upload(&dl.wpk_wn, pkw.data(), pkw.size() * 2, n->stream)) return 1;
-                    HIP_TRY(hipStreamSynchronize(n->stream));
-                }
-            }
-        }
-        std::vector<uint16_t> pk16;
-        if (g.nf == 64 && (g.scale == 2 || g.scale == 4) && i + 1 == g.convs.size()) {
-            pack_tail64(g.convs[i], pk16);
-            if (upload(&dl.wpk16, pk16.data(), pk16.size() * 2, n->stream)) return 1;
-        }
-        if (g.nf == 24 && g.scale == 1 && g.convs.size() == (size_t)S10_NL) {
-            // channels whose PReLU slope exceeds 1 travel negated between the layers (uva_model.h pack_sub16)
-            std::vector<float> sin(g.convs[i].cin, 1.f), sout(g.convs[i].cout, 1.f), bs(32, 0.f);
-            if (i > 0)
-                for (int c = 0; c < g.convs[i].cin; ++c) sin[c] = g.slopes[i - 1][c] > 1.f ? -1.f : 1.f;
-            if (i + 1 < g.convs.size())
-                for (int c = 0; c < g.convs[i].cout; ++c) sout[c] = g.slopes[i][c] > 1.f ? -1.f : 1.f;
-            const int brow = g.convs[i].cout == 3 ? 4 : 1;       // (the last layer's channel j sits in MFMA row 4j: pack_sub16)
-            for (int c = 0; c < g.convs[i].cout; ++c) bs[brow * c] = sout[c] * g.convs[i].bias[c];
-            std::vector<uint16_t> pks;
-            pack_sub16(g.convs[i], pks, nullptr, nullptr, sin.data(), sout.data());
-            if (upload(&dl.wpk_s10, pks.data(), pks.size() * 2, n->stream)) return 1;
-            if (upload(&dl.bias_s10, bs.data(), bs.size() * 4, n->stream)) return 1;
-            HIP_TRY(hipStreamSynchronize(n->stream));
-        }
-        std::vector<float> b((size_t)mf * 32, 0.f), s((size_t)mf * 32, 0.f);
-        std::copy(g.convs[i].bias.begin(), g.convs[i].bias.end(), b.begin());
-        if (upload(&dl.bias, b.data(), b.size() * 4, n->stream)) return 1;
-        if (i + 1 < g.convs.size()) {
-            std::copy(g.slopes[i].begin(), g.slopes[i].end(), s.begin());
-            if (upload(&dl.slope, s.data(), s.size() * 4, n->stream)) return 1;
-        }
-        HIP_TRY(hipStreamSynchronize(n->stream));   // pk / b / s go out of scope
-    }
-    n->dev_ready = true;
+    static_cast<NetDevice&>(*n) = std::move(d);
     return 0;
 }
 
@@ -603,73 +600,63 @@ int get_workspace(uva_net* n, int h, int w, int tile_size, int border, Workspace
     while (!n->wss.empty() && (n->wss.size() >= CACHE_ENTRIES || cached_bytes() + 2 * bytes > CACHE_BYTES)) {
         HIP_TRY(hipStreamSynchronize(n->stream));
         if (n->last.ws == &n->wss.back()) n->last = LastCall();
-        n->wss.back().release();
         n->wss.pop_back();
     }
-    // from here on a failure releases what this workspace already holds
-    struct Guard {
-        Workspace* w;
-        ~Guard() { if (w) w->release(); }
-    } guard{&ws};
+    // (`ws` is a local until it is complete: a failure from here on releases what it already holds)
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipMalloc((void**)&ws.act_base[i], bytes));
+        HIP_TRY(alloc_into(ws.act_base[i], bytes));
         HIP_TRY(hipMemsetAsync(ws.act_base[i], 0, bytes, n->stream));   // the zero border lives here forever
         ws.act[i] = (_Float16*)(ws.act_base[i] + ws.guard_bytes);
     }
     ws.alloc_bytes = 2 * bytes;
-    if (upload(&ws.d_planes, ws.planes.data(), ws.planes.size() * sizeof(PlaneDesc), n->stream)) return 1;
+    if (upload(ws.d_planes, ws.planes.data(), ws.planes.size() * sizeof(PlaneDesc), n->stream)) return 1;
     if (n->g.nf == 64) {
-        if (upload(&ws.d_sched4, plan.sched4.data(), plan.sched4.size() * sizeof(uint4), n->stream)) return 1;
-        if (upload(&ws.d_steps2, plan.steps2.data(), plan.steps2.size() * sizeof(Trunk2Step), n->stream)) return 1;
-        if (upload(&ws.d_nsteps2, plan.nsteps2.data(), plan.nsteps2.size() * sizeof(int), n->stream)) return 1;
-        if (upload(&ws.d_stepsw, plan.stepsw.data(), plan.stepsw.size() * sizeof(Trunk2Step), n->stream)) return 1;
-        if (upload(&ws.d_nstepsw, plan.nstepsw.data(), plan.nstepsw.size() * sizeof(int), n->stream)) return 1;
+        if (upload(ws.d_sched4, plan.sched4.data(), plan.sched4.size() * sizeof(uint4), n->stream)) return 1;
+        if (upload(ws.d_steps2, plan.steps2.data(), plan.steps2.size() * sizeof(Trunk2Step), n->stream)) return 1;
+        if (upload(ws.d_nsteps2, plan.nsteps2.data(), plan.nsteps2.size() * sizeof(int), n->stream)) return 1;
+        if (upload(ws.d_stepsw, plan.stepsw.data(), plan.stepsw.size() * sizeof(Trunk2Step), n->stream)) return 1;
+        if (upload(ws.d_nstepsw, plan.nstepsw.data(), plan.nstepsw.size() * sizeof(int), n->stream)) return 1;
     }
     HIP_TRY(hipStreamSynchronize(n->stream));
-    guard.w = nullptr;
-    n->wss.push_front(ws);
+    n->wss.push_front(std::move(ws));
     *out = &n->wss.front();
     return 0;
 }
 
-hipEvent_t take_sync_event(uva_net* n);
+// an event from `pool`, or a new one with `flags`; an empty handle (with the error recorded) if the runtime cannot create another
+Event take_from(std::vector<Event>& pool, unsigned flags)
+{
+    Event e;
+    if (!pool.empty()) {
+        e = std::move(pool.back());
+        pool.pop_back();
+        return e;
+    }
+    const hipError_t rc = make_event(e, flags);
+    if (rc != hipSuccess) fail(std::string("hipEventCreate: ") + hipGetErrorString(rc));
+    return e;
+}
 
-// take_sync_event() for the length of a scope: the event goes back to its net's pool on EVERY path out (HIP_TRY returns
-// from the middle of a function; a wait has captured the recorded state by then, or nothing was recorded at all)
+// An event that orders one stream behind another (default flags: its release makes the producer's writes visible), for the
+// length of a scope: it goes back to its net's pool on EVERY path out (HIP_TRY returns from the middle of a function; a wait
+// has captured the recorded state by then, or nothing was recorded at all)
 struct SyncEventScope {
     uva_net* n;
-    hipEvent_t e;
-    explicit SyncEventScope(uva_net* net) : n(net), e(take_sync_event(net)) {}
-    ~SyncEventScope() { if (e) n->ev_sync_free.push_back(e); }
+    Event e;
+    explicit SyncEventScope(uva_net* net) : n(net), e(take_from(net->ev_sync_free, hipEventDisableTiming)) {}
+    ~SyncEventScope() { if (e) n->ev_sync_free.push_back(std::move(e)); }
     SyncEventScope(const SyncEventScope&) = delete;
     SyncEventScope& operator=(const SyncEventScope&) = delete;
 };
-
-// an event that orders one stream behind another (default flags: its release makes the producer's writes visible)
-hipEvent_t take_sync_event(uva_net* n)
-{
-    if (!n->ev_sync_free.empty()) {
-        hipEvent_t e = n->ev_sync_free.back();
-        n->ev_sync_free.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    if (rc != hipSuccess) {
-        fail(std::string("hipEventCreate: ") + hipGetErrorString(rc));
-        return nullptr;
-    }
-    return e;
-}
 
 // Frames whose last event has completed are added to the statistics and their events recycled; frames still
 // in flight (pipelined submits) stay pending for the next call.
 void resolve_events(uva_net* n)
 {
-    std::vector<uva_net::EvSet> keep;
+    std::vector<EvSet> keep;
     for (auto& s : n->ev_pending) {
         if (hipEventQuery(s.e[3]) == hipErrorNotReady) {
-            keep.push_back(s);
+            keep.push_back(std::move(s));
             continue;
         }
         float ms[3] = {0, 0, 0};
@@ -680,16 +667,16 @@ void resolve_events(uva_net* n)
             n->launches[1] += s.ntrunk; n->total_ms[1] += ms[1];
             n->launches[2] += 1; n->total_ms[2] += ms[2];
         }
-        for (auto e : s.e) n->ev_free.push_back(e);
+        for (Event& e : s.e) n->ev_free.push_back(std::move(e));
     }
     n->ev_pending.swap(keep);
-    std::vector<uva_net::EvPair> keep2;
+    std::vector<EvPair> keep2;
     for (auto& q : n->ev_pairs) {
-        if (hipEventQuery(q.b) == hipErrorNotReady) { keep2.push_back(q); continue; }
+        if (hipEventQuery(q.b) == hipErrorNotReady) { keep2.push_back(std::move(q)); continue; }
         float ms = 0;
         if (hipEventElapsedTime(&ms, q.a, q.b) == hipSuccess) { n->launches[q.kind] += 1; n->total_ms[q.kind] += ms; }
-        n->ev_free.push_back(q.a);
-        n->ev_free.push_back(q.b);
+        n->ev_free.push_back(std::move(q.a));
+        n->ev_free.push_back(std::move(q.b));
     }
     n->ev_pairs.swap(keep2);
 }
@@ -707,29 +694,16 @@ bool sub10_route(const uva_net* n, const Workspace* ws, bool f32, int stop_after
 // launch around it; 0 = done, 1 = error, 2 = does not fit (fewer frames, or for one frame the layer-pair path)
 int run_sub10(uva_net* n, Workspace* ws, const void* const* srcs, size_t src_stride, void* const* dsts, size_t dst_stride, int frames)
 {
-    uva_net::EvSet ev1;
-    const bool prof1 = n->prof;
-    if (prof1) {
-        for (auto& e : ev1.e) e = nullptr;
-        for (auto& e : ev1.e) {
-            e = take_event(n);
-            if (!e) return 1;
-        }
-        HIP_TRY(hipEventRecord(ev1.e[0], n->stream));
-        HIP_TRY(hipEventRecord(ev1.e[1], n->stream));
-    }
+    EvScope ev1(n, 4, n->prof);
+    if (n->prof && !ev1.taken()) return 1;
+    HIP_TRY(ev1.record(0));
+    HIP_TRY(ev1.record(1));
     int rc = 2, launches = 2;
     if (frames == 1 && n->split5 && !ws->sub5_unfit) rc = launch_sub5(n, ws, srcs[0], src_stride, dsts[0], dst_stride);
     if (rc == 2) { rc = launch_sub10(n, ws, srcs, src_stride, dsts, dst_stride, frames); launches = 1; }
-    if (prof1) {
-        if (rc == 0) {
-            HIP_TRY(hipEventRecord(ev1.e[2], n->stream));
-            HIP_TRY(hipEventRecord(ev1.e[3], n->stream));
-            ev1.ntrunk = launches;
-            n->ev_pending.push_back(ev1);
-        } else {
-            for (auto e : ev1.e) n->ev_free.push_back(e);
-        }
+    if (rc == 0) {
+        HIP_TRY(ev1.record(2));
+        HIP_TRY(ev1.last(launches));
     }
     return rc;
 }
@@ -757,21 +731,11 @@ int run_sub10_u16(uva_net* n, Workspace* ws, const void* src, size_t src_stride,
         a.bias[i] = n->layers[i].bias_s10;
         a.slope[i] = n->layers[i].slope;
     }
-    uva_net::EvPair ev = {nullptr, nullptr, 3};
-    if (n->prof) {
-        ev.a = take_event(n);
-        ev.b = ev.a ? take_event(n) : nullptr;
-        if (!ev.b) {
-            if (ev.a) n->ev_free.push_back(ev.a);
-            return 1;
-        }
-        HIP_TRY(hipEventRecord(ev.a, n->stream));
-    }
+    EvScope ev(n, 2, n->prof);
+    if (n->prof && !ev.taken()) return 1;
+    HIP_TRY(ev.record(0));
     HIP_TRY(launch_sub10_kernel16(n->stream, ws->grid10, a));
-    if (n->prof) {
-        HIP_TRY(hipEventRecord(ev.b, n->stream));
-        n->ev_pairs.push_back(ev);
-    }
+    HIP_TRY(ev.last(3));
     return 0;
 }
 
@@ -788,20 +752,10 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
         if (rc != 2) return rc;
     }
     const bool prof = n->prof && stop_after < 0;
-    uva_net::EvSet ev;
-    ev.ntrunk = 0;   // trunk launches of this frame (a fused pair is one launch)
-    if (prof) {
-        for (auto& e : ev.e) e = nullptr;
-        for (auto& e : ev.e) {
-            e = take_event(n);
-            if (!e) {
-                for (auto q : ev.e)
-                    if (q) n->ev_free.push_back(q);
-                return 1;
-            }
-        }
-        HIP_TRY(hipEventRecord(ev.e[0], n->stream));
-    }
+    EvScope ev(n, 4, prof);
+    if (prof && !ev.taken()) return 1;
+    int ntrunk = 0;  // trunk launches of this frame (a fused pair is one launch)
+    HIP_TRY(ev.record(0));
     HeadArgs ha;
     std::memset(&ha, 0, sizeof ha);
     ha.planes = ws->d_planes;
@@ -817,7 +771,7 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
     ha.in_scale = f32 ? 1.0f : (float)(1 / 255.0);      // (u16: the operand is v / 257, see headp_kernel)
     ha.sink = n->d_sink;
     if (launch_head(n, f32, ha, u16)) return 1;
-    if (prof) HIP_TRY(hipEventRecord(ev.e[1], n->stream));
+    HIP_TRY(ev.record(1));
 
     ConvArgs ca;
     std::memset(&ca, 0, sizeof ca);
@@ -850,7 +804,7 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
             wa.sink = n->d_sink;
             if (launch_trunkw(n, ws, wa, i, negated, carry_out)) return 1;
             negated = carry_out;
-            ++ev.ntrunk;
+            ++ntrunk;
             ++i;
             cur ^= 1;
             n->last_act_buf = cur;
@@ -871,7 +825,7 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
             ta.max_steps = ws->max_steps2;
             ta.sink = n->d_sink;
             if (launch_trunk2(n, ws, ta)) return 1;
-            ++ev.ntrunk;
+            ++ntrunk;
             ++i;
             cur ^= 1;
             n->last_act_buf = cur;
@@ -890,19 +844,19 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
             ca.ntiles = ws->ntiles;
             ca.tiles_per_xcd = (ws->ntiles + 7) / 8;
             if (launch_pair24(n, ca)) return 1;
-            ++ev.ntrunk;
+            ++ntrunk;
             ++i;
             cur ^= 1;
             n->last_act_buf = cur;
             continue;
         }
         if (launch_trunk(n, ws, ca)) return 1;
-        ++ev.ntrunk;
+        ++ntrunk;
         cur ^= 1;
         n->last_act_buf = cur;
     }
     if (stop_after >= 0) return 0;
-    if (prof) HIP_TRY(hipEventRecord(ev.e[2], n->stream));
+    HIP_TRY(ev.record(2));
     ca.ntiles = ws->ntiles;
     ca.tiles_per_xcd = (ws->ntiles + 7) / 8;
     ca.in_act = ws->act[cur];
@@ -921,10 +875,7 @@ int run_graph(uva_net* n, Workspace* ws, bool f32, const void* src, size_t src_s
         ca.dst_stride = dst_stride;
     }
     if (f32 ? launch_conv(n, 2, ca) : launch_tail_u8(n, ws, ca, u16)) return 1;
-    if (prof) {
-        HIP_TRY(hipEventRecord(ev.e[3], n->stream));
-        n->ev_pending.push_back(ev);
-    }
+    HIP_TRY(ev.last(ntrunk));
     return 0;
 }
 
@@ -937,24 +888,10 @@ int check_dims(const uva_net* n, int h, int w)
 
 }  // namespace
 
-// -> nullptr (with the error recorded) if the runtime cannot create another event
-hipEvent_t uva::take_event(uva_net* n)
-{
-    if (!n->ev_free.empty()) {
-        hipEvent_t e = n->ev_free.back();
-        n->ev_free.pop_back();
-        return e;
-    }
-    // (hipEventDisableSystemFence -- no L2 write-back at a timing event -- measured: no difference in the frame time or in the
-    // kernel times the events bracket, profiles/r04_ab_results.txt block 18; default events kept)
-    hipEvent_t e = nullptr;
-    const hipError_t rc = hipEventCreate(&e);
-    if (rc != hipSuccess) {
-        fail(std::string("hipEventCreate: ") + hipGetErrorString(rc));
-        return nullptr;
-    }
-    return e;
-}
+// a timing event
+// (hipEventDisableSystemFence -- no L2 write-back at a timing event -- measured: no difference in the frame time or in the
+// kernel times the events bracket, profiles/r04_ab_results.txt block 18; default events kept)
+Event uva::take_event(uva_net* n) { return take_from(n->ev_free, hipEventDefault); }
 
 // The stateless device stages (uva_*_device: denoise, pixel formats, resize) run on a stream of their own between two nets'
 // streams.  Both nets, where given, must live on the stage's device ...
@@ -974,8 +911,8 @@ int uva::fence_after(uva_net* after, hipStream_t stream)
     if (!after) return 0;
     SyncEventScope ev(after);
     if (!ev.e) return 1;
-    HIP_TRY(hipEventRecord(ev.e, after->stream));
-    HIP_TRY(hipStreamWaitEvent(stream, ev.e, 0));
+    HIP_TRY(hipEventRecord(ev.e.get(), after->stream));
+    HIP_TRY(hipStreamWaitEvent(stream, ev.e.get(), 0));
     return 0;
 }
 
@@ -985,7 +922,7 @@ int uva::fence_before(uva_net* before, hipStream_t stream)
     if (!before) return 0;
     SyncEventScope ev(before);
     if (!ev.e) return 1;
-    HIP_TRY(hipEventRecord(ev.e, stream));
+    HIP_TRY(hipEventRecord(ev.e.get(), stream));
     HIP_TRY(hipStreamWaitEvent(before->stream, ev.e, 0));
     return 0;
 }
@@ -1133,7 +1070,7 @@ int uva_net_wait_for(uva_net* n, uva_net* producer)
     if (producer->device != n->device) return fail("uva_net_wait_for: nets are on different devices");
     SyncEventScope ev(n);           // (recycled at the end of the scope: the wait has captured the recorded state)
     if (!ev.e) return 1;
-    HIP_TRY(hipEventRecord(ev.e, producer->stream));
+    HIP_TRY(hipEventRecord(ev.e.get(), producer->stream));
     HIP_TRY(hipStreamWaitEvent(n->stream, ev.e, 0));
     return 0;
 }
@@ -1243,6 +1180,11 @@ void uva_host_free(void* p)
     if (p) (void)hipHostFree(p);
 }
 
+void uva_debug_live_resources(long long counts[4])
+{
+    for (int k = 0; k < LIVE_KINDS; ++k) counts[k] = g_live[k].load();
+}
+
 }  // extern "C"
 namespace {
 // The pipelined host route.  An entry fills a SubmitSpec, submit_check refuses what the entries refuse,
@@ -1277,7 +1219,7 @@ struct SubmitRun {                       // what the stages of one call share
     const SubmitPlan& p;
     const uint8_t* in;                   // (a window of a BGR frame: at its offset)
     uint8_t* out;
-    uva_net::PipeSlot* ps = nullptr;
+    PipeSlot* ps = nullptr;
     const uint8_t* d_res = nullptr;      // the BGR frame that leaves: d_out, or d_rs
     const uint8_t* d_src = nullptr;      // what comes down: d_res, the packed frame d_pout, or the kept frame's result
     bool rp_on = false, repeat = false;  // uva_net_set_skip_repeats is in force; this frame repeats the kept one
@@ -1292,30 +1234,29 @@ int submit_upload(SubmitRun& r)
     for (auto& c : n->pipe)
         if (!c.busy) { r.ps = &c; break; }
     if (!r.ps) return fail("uva_net_submit_u8: " + std::to_string(uva_net::PIPE_SLOTS) + " frames already in flight, collect one first");
-    uva_net::PipeSlot& ps = *r.ps;
-    if (!n->s_h2d) {
-        if (tryhip(hipStreamCreateWithFlags(&n->s_h2d, hipStreamNonBlocking), "hipStreamCreate") ||
-            tryhip(hipStreamCreateWithFlags(&n->s_d2h, hipStreamNonBlocking), "hipStreamCreate")) return 1;
+    PipeSlot& ps = *r.ps;
+    if (!n->s_d2h) {
+        if (tryhip(make_stream(n->s_h2d), "hipStreamCreate") || tryhip(make_stream(n->s_d2h), "hipStreamCreate")) return 1;
     }
-    if (!ps.ev_h2d) {
-        if (tryhip(hipEventCreateWithFlags(&ps.ev_h2d, hipEventDisableTiming), "hipEventCreate") ||
-            tryhip(hipEventCreateWithFlags(&ps.ev_done, hipEventDisableTiming), "hipEventCreate") ||
-            tryhip(hipEventCreateWithFlags(&ps.ev_d2h, hipEventDisableTiming), "hipEventCreate")) return 1;
+    if (!ps.ev_d2h) {
+        if (tryhip(make_event(ps.ev_h2d, hipEventDisableTiming), "hipEventCreate") ||
+            tryhip(make_event(ps.ev_done, hipEventDisableTiming), "hipEventCreate") ||
+            tryhip(make_event(ps.ev_d2h, hipEventDisableTiming), "hipEventCreate")) return 1;
     }
-    if (grow_dev(&ps.d_in, &ps.d_in_cap, p.in_bytes) || grow_dev(&ps.d_out, &ps.d_out_cap, p.out_bytes)) return 1;
-    if ((p.pin && grow_dev(&ps.d_pin, &ps.d_pin_cap, p.pin_bytes)) || (p.pout && grow_dev(&ps.d_pout, &ps.d_pout_cap, p.pout_bytes))) return 1;
-    if (p.rs && grow_dev(&ps.d_rs, &ps.d_rs_cap, p.res_bytes)) return 1;
-    if (p.win_cols && grow_dev(&ps.d_win, &ps.d_win_cap, p.wstage_bytes)) return 1;
+    if (grow_dev(ps.d_in, p.in_bytes) || grow_dev(ps.d_out, p.out_bytes)) return 1;
+    if ((p.pin && grow_dev(ps.d_pin, p.pin_bytes)) || (p.pout && grow_dev(ps.d_pout, p.pout_bytes))) return 1;
+    if (p.rs && grow_dev(ps.d_rs, p.res_bytes)) return 1;
+    if (p.win_cols && grow_dev(ps.d_win, p.wstage_bytes)) return 1;
     r.d_res = p.rs ? ps.d_rs : ps.d_out;
     if (sp.png_ws) {                     // (png_ws: the encoder that matches the net's frames)
         if (!png_takes(p.out_h, p.out_w, sp.bits)) return fail("PNG encoder: frame width out of range");
         if (sp.png_ws_bytes < png_workspace_bytes(p.out_h, p.out_w, sp.bits)) return fail("PNG workspace too small");
-        if (grow_dev(&ps.d_png, &ps.d_png_cap, png_device_bytes(p.out_h, p.out_w, sp.bits))) return 1;
+        if (grow_dev(ps.d_png, png_device_bytes(p.out_h, p.out_w, sp.bits))) return 1;
     }
     // H2D: straight from the caller's buffer when it is pinned (uva_host_alloc / hipHostMalloc /
     // hipHostRegister), through this slot's pinned staging buffer otherwise
     const bool pinned = is_pinned_host(r.in);
-    if (!pinned && grow_host(&ps.h_in, &ps.h_in_cap, p.h_in_bytes)) return 1;
+    if (!pinned && grow_host(ps.h_in, p.h_in_bytes)) return 1;
     if (p.win_rows) {
         // one copy per plane of the plane's row range: into the packed frame where the rows are whole, into the staging otherwise
         uint8_t* d_up = p.win_cols ? ps.d_win : ps.d_pin;
@@ -1356,23 +1297,23 @@ int submit_compute(SubmitRun& r)
     uva_net* n = r.n;
     const SubmitSpec& sp = r.sp;
     const SubmitPlan& p = r.p;
-    uva_net::PipeSlot& ps = *r.ps;
+    PipeSlot& ps = *r.ps;
     // --skip-repeats: the frame is compared with the kept frame's input on the upload stream, behind its own upload, and the
     // host waits for the three numbers -- the one blocking point of the route, and only with the option on
-    uva_net::Repeat& rp = n->rep;
-    r.rp_on = sp.may_skip && !sp.png_ws && rp.threshold >= 0;
+    KeptFrame& rp = n->kept;
+    r.rp_on = sp.may_skip && !sp.png_ws && n->rep.threshold >= 0;
     if (r.rp_on) {
         const uint8_t* d_packed = p.pin ? ps.d_pin : ps.d_in;
-        ++rp.submitted;
-        if (!rp.d_stats) {
-            if (tryhip(hipMalloc((void**)&rp.d_stats, sizeof(FrameDiffStats)), "hipMalloc") ||
-                tryhip(hipHostMalloc((void**)&rp.h_stats, sizeof(FrameDiffStats), hipHostMallocDefault), "hipHostMalloc") ||
-                tryhip(hipEventCreateWithFlags(&rp.ev_stats, hipEventDisableTiming), "hipEventCreate") ||
-                tryhip(hipEventCreateWithFlags(&rp.ev_written, hipEventDisableTiming), "hipEventCreate") ||
-                tryhip(hipEventCreateWithFlags(&rp.ev_read, hipEventDisableTiming), "hipEventCreate")) return 1;
+        ++n->rep.submitted;
+        if (!rp.ev_read) {
+            if (tryhip(alloc_into(rp.d_stats, sizeof(FrameDiffStats)), "hipMalloc") ||
+                tryhip(alloc_into(rp.h_stats, sizeof(FrameDiffStats)), "hipHostMalloc") ||
+                tryhip(make_event(rp.ev_stats, hipEventDisableTiming), "hipEventCreate") ||
+                tryhip(make_event(rp.ev_written, hipEventDisableTiming), "hipEventCreate") ||
+                tryhip(make_event(rp.ev_read, hipEventDisableTiming), "hipEventCreate")) return 1;
         }
         if (rp.valid && p.key == rp.key) {
-            if (tryhip(launch_frame_diff(n->s_h2d, rp.d_in, d_packed, p.packed_bytes, sp.in_fmt, (unsigned)rp.threshold, rp.d_stats), "frame_diff") ||
+            if (tryhip(launch_frame_diff(n->s_h2d, rp.d_in, d_packed, p.packed_bytes, sp.in_fmt, (unsigned)n->rep.threshold, rp.d_stats), "frame_diff") ||
                 tryhip(hipMemcpyAsync(rp.h_stats, rp.d_stats, sizeof(FrameDiffStats), hipMemcpyDeviceToHost, n->s_h2d), "D2H") ||
                 tryhip(hipEventRecord(rp.ev_stats, n->s_h2d), "hipEventRecord") ||
                 tryhip(hipEventSynchronize(rp.ev_stats), "hipEventSynchronize")) return 1;
@@ -1382,10 +1323,10 @@ int submit_compute(SubmitRun& r)
             // this frame runs and becomes the kept frame.  Kept input: the comparisons read it and this copy replaces it on one
             // stream, s_h2d, so they are ordered (the slot's own upload buffer is free again once the frame is collected).
             rp.valid = false;
-            if (rp.d_in_cap < p.packed_bytes || rp.d_res_cap < p.dl_bytes) {      // (a buffer that moves: nothing may still use it)
+            if (rp.d_in.cap() < p.packed_bytes || rp.d_res.cap() < p.dl_bytes) {      // (a buffer that moves: nothing may still use it)
                 if (tryhip(hipStreamSynchronize(n->s_h2d), "hipStreamSynchronize") || tryhip(hipStreamSynchronize(n->s_d2h), "hipStreamSynchronize") ||
                     tryhip(hipStreamSynchronize(n->stream), "hipStreamSynchronize")) return 1;
-                if (grow_dev(&rp.d_in, &rp.d_in_cap, p.packed_bytes) || grow_dev(&rp.d_res, &rp.d_res_cap, p.dl_bytes)) return 1;
+                if (grow_dev(rp.d_in, p.packed_bytes) || grow_dev(rp.d_res, p.dl_bytes)) return 1;
                 rp.reads_pending = false;
             }
             if (tryhip(hipMemcpyAsync(rp.d_in, d_packed, p.packed_bytes, hipMemcpyDeviceToDevice, n->s_h2d), "D2D")) return 1;
@@ -1394,7 +1335,7 @@ int submit_compute(SubmitRun& r)
     }
     if (r.repeat) {
         // the kept result's bytes, by a download alone: behind the copy that wrote them (ev_written, on the net's stream)
-        ++rp.skipped;
+        ++n->rep.skipped;
         r.d_src = rp.d_res;
         return tryhip(hipStreamWaitEvent(n->s_d2h, rp.ev_written, 0), "hipStreamWaitEvent");
     }
@@ -1429,7 +1370,7 @@ int submit_download(SubmitRun& r)
     uva_net* n = r.n;
     const SubmitSpec& sp = r.sp;
     const SubmitPlan& p = r.p;
-    uva_net::PipeSlot& ps = *r.ps;
+    PipeSlot& ps = *r.ps;
     ps.user_out = nullptr;
     ps.png_ws = nullptr;
     if (sp.png_ws) {
@@ -1446,15 +1387,15 @@ int submit_download(SubmitRun& r)
     } else {
         uint8_t* dst = r.out;
         if (!is_pinned_host(r.out)) {
-            if (grow_host(&ps.h_out, &ps.h_out_cap, p.dl_bytes)) return 1;
+            if (grow_host(ps.h_out, p.dl_bytes)) return 1;
             dst = ps.h_out;
             ps.user_out = r.out; ps.user_out_stride = p.dl_user_stride; ps.out_row = p.dl_row; ps.out_rows = p.dl_rows;
         }
         if (ps.user_out) {
-            const int rows = p.dl_rows, per = (rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
+            const int rows = p.dl_rows, per = (rows + PipeSlot::BANDS - 1) / PipeSlot::BANDS;
             const size_t row = p.dl_row;
-            for (int k = 0; k < uva_net::PipeSlot::BANDS; ++k) {
-                if (!ps.ev_band[k] && tryhip(hipEventCreateWithFlags(&ps.ev_band[k], hipEventDisableTiming), "hipEventCreate")) return 1;
+            for (int k = 0; k < PipeSlot::BANDS; ++k) {
+                if (!ps.ev_band[k] && tryhip(make_event(ps.ev_band[k], hipEventDisableTiming), "hipEventCreate")) return 1;
                 const int r0 = std::min(rows, k * per), nr = std::min(rows, r0 + per) - r0;
                 if (nr > 0 && tryhip(hipMemcpyAsync(dst + (size_t)r0 * row, r.d_src + (size_t)r0 * row, (size_t)nr * row,
                                                     hipMemcpyDeviceToHost, n->s_d2h), "D2H")) return 1;
@@ -1468,8 +1409,8 @@ int submit_download(SubmitRun& r)
         }
         if (tryhip(hipEventRecord(ps.ev_d2h, n->s_d2h), "hipEventRecord")) return 1;
         if (r.repeat) {
-            if (tryhip(hipEventRecord(n->rep.ev_read, n->s_d2h), "hipEventRecord")) return 1;
-            n->rep.reads_pending = true;
+            if (tryhip(hipEventRecord(n->kept.ev_read, n->s_d2h), "hipEventRecord")) return 1;
+            n->kept.reads_pending = true;
         }
     }
     ps.busy = true;
@@ -1610,13 +1551,13 @@ int uva_net_set_skip_repeats(uva_net* n, int threshold)
     if (!n) return fail("null net");
     if (threshold < -1 || threshold > 65535) return fail("uva_net_set_skip_repeats: the threshold is -1 (off) or 0 ... 65535 code values");
     n->rep.threshold = threshold;
-    n->rep.valid = false;
+    n->kept.valid = false;
     n->rep.submitted = n->rep.skipped = 0;
-    if (threshold < 0 && (n->rep.d_in || n->rep.d_stats)) {     // off again: the kept frame's buffers go (there is a device: they exist)
+    if (threshold < 0 && (n->kept.d_in || n->kept.d_stats)) {     // off again: the kept frame's buffers go (there is a device: they exist)
         HIP_TRY(hipSetDevice(n->device));
-        for (hipStream_t st : {n->s_h2d, n->s_d2h, n->stream})
+        for (hipStream_t st : {n->s_h2d.get(), n->s_d2h.get(), n->stream.get()})
             if (st) HIP_TRY(hipStreamSynchronize(st));
-        n->release_repeat();
+        n->kept = KeptFrame();
     }
     return 0;
 }
@@ -1624,7 +1565,7 @@ int uva_net_set_skip_repeats(uva_net* n, int threshold)
 int uva_net_reset_reference(uva_net* n)
 {
     if (!n) return fail("null net");
-    n->rep.valid = false;
+    n->kept.valid = false;
     return 0;
 }
 
@@ -1645,7 +1586,7 @@ int uva_net_set_input_window(uva_net* n, int src_h, int src_w, int x, int y)
     if (!off && (x < 0 || y < 0 || x >= src_w || y >= src_h)) return fail("input window: the window leaves the frame");
     n->win.src_h = src_h; n->win.src_w = src_w; n->win.x = x; n->win.y = y;
     // the kept frame of uva_net_set_skip_repeats was compared as another window's bytes: forget it
-    n->rep.valid = false;
+    n->kept.valid = false;
     n->rep.submitted = n->rep.skipped = 0;
     return 0;
 }
@@ -1653,15 +1594,15 @@ int uva_net_set_input_window(uva_net* n, int src_h, int src_w, int x, int y)
 int uva_net_collect_u8(uva_net* n, long long ticket)
 {
     if (!n || ticket < 0) return fail("bad ticket");
-    uva_net::PipeSlot* slot = nullptr;
+    PipeSlot* slot = nullptr;
     for (auto& c : n->pipe)
         if (c.busy && c.ticket == ticket) slot = &c;
     if (!slot) return fail("uva_net_collect_u8: ticket " + std::to_string(ticket) + " is not in flight");
-    uva_net::PipeSlot& ps = *slot;
+    PipeSlot& ps = *slot;
     HIP_TRY(hipSetDevice(n->device));
     if (ps.user_out) {
-        const int per = (ps.out_rows + uva_net::PipeSlot::BANDS - 1) / uva_net::PipeSlot::BANDS;
-        for (int k = 0; k < uva_net::PipeSlot::BANDS; ++k) {
+        const int per = (ps.out_rows + PipeSlot::BANDS - 1) / PipeSlot::BANDS;
+        for (int k = 0; k < PipeSlot::BANDS; ++k) {
             HIP_TRY(hipEventSynchronize(ps.ev_band[k]));
             const int r0 = std::min(ps.out_rows, k * per), r1 = std::min(ps.out_rows, r0 + per);
             if (ps.user_out_stride == ps.out_row) {
@@ -1711,7 +1652,7 @@ int uva_net_extract_f32(uva_net* n, const float* in_chw, int h, int w, float* ou
     if (ensure_device(n)) return 1;
     const int s = uva_net_scale(n);
     const size_t in_bytes = (size_t)3 * h * w * 4, out_bytes = (size_t)3 * h * s * w * s * 4;
-    if (grow_dev(&n->d_fin, &n->d_fin_cap, in_bytes) || grow_dev(&n->d_fout, &n->d_fout_cap, out_bytes)) return 1;
+    if (grow_dev(n->d_fin, in_bytes) || grow_dev(n->d_fout, out_bytes)) return 1;
     if (n->generic) {
         HIP_TRY(hipMemcpyAsync(n->d_fin, in_chw, in_bytes, hipMemcpyHostToDevice, n->stream));
         if (generic_run_plane(n, true, n->d_fin, 0, 0, 0, h, w, n->d_fout, 0, 0, h, 0, w)) return 1;
@@ -1769,6 +1710,38 @@ int uva_net_kernel_stats(uva_net* n, int kind, long long* launches, double* tota
 }
 
 #ifdef UVA_INSTRUMENT
+}  // extern "C"
+namespace {
+// The stamps of one launch and the time of `reps`: a warm-up, `reps` timed launches without stamps, one launch that writes
+// its stamps, the stamps copied out.  launch(dbg) runs the kernel with that stamp buffer (null: none) and returns 0, 1 or
+// its own refusal, which stamped_run hands on.  The buffer and the events are handles: they go on every path out.
+template <typename L>
+int stamped_run(uva_net* n, unsigned long long* out, int max_tiles, float* kernel_ms, int reps, L launch)
+{
+    const size_t bytes = (size_t)max_tiles * 8 * sizeof(unsigned long long);
+    DevPtr<unsigned long long> d;
+    Event e0, e1;
+    HIP_TRY(alloc_into(d, bytes));
+    HIP_TRY(make_event(e0, hipEventDefault));
+    HIP_TRY(make_event(e1, hipEventDefault));
+    int rc = launch(nullptr);
+    HIP_TRY(hipEventRecord(e0, n->stream));
+    for (int r = 0; r < reps && !rc; ++r) rc = launch(nullptr);
+    HIP_TRY(hipEventRecord(e1, n->stream));
+    HIP_TRY(hipMemsetAsync(d, 0, bytes, n->stream));
+    if (!rc) rc = launch(d.get());
+    const hipError_t copied = rc ? hipSuccess : hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream);
+    HIP_TRY(hipStreamSynchronize(n->stream));           // (before `d` goes: the last launch writes to it)
+    if (rc) return rc;
+    HIP_TRY(copied);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    if (kernel_ms) *kernel_ms = ms / reps;
+    return 0;
+}
+}  // namespace
+extern "C" {
+
 // debug: one trunk-layer launch on the last call's workspace with in-kernel s_memtime stamps
 // (block 0, wave 0): out[8*i + {0,1,2,3,4}] = tile i {start, k-loop done, barrier passed, epilogue done,
 // epilogue staging written}
@@ -1778,10 +1751,6 @@ int uva_net_debug_trunk_stamps(uva_net* n, unsigned long long* out, int max_tile
     if (!n || !out || !n->dev_ready || !n->last.valid) return fail("no previous call to replay");
     Workspace* ws = n->last.ws;
     HIP_TRY(hipSetDevice(n->device));
-    unsigned long long* d = nullptr;
-    const size_t bytes = (size_t)max_tiles * 8 * sizeof(unsigned long long);
-    HIP_TRY(hipMalloc((void**)&d, bytes));
-    HIP_TRY(hipMemsetAsync(d, 0, bytes, n->stream));
     ConvArgs ca;
     std::memset(&ca, 0, sizeof ca);
     ca.planes = ws->d_planes;
@@ -1793,152 +1762,75 @@ int uva_net_debug_trunk_stamps(uva_net* n, unsigned long long* out, int max_tile
     ca.wpk = n->layers[1].wpk;
     ca.bias = n->layers[1].bias;
     ca.slope = n->layers[1].slope;
-    ca.dbg = d;
     ca.sink = n->d_sink;
     const bool split = n->g.nf == 64;
     const int grid = persistent_grid(n->ncu);
     const int g8 = (split ? 2 : 1) * grid / 8;
     const int txcd = ((split ? ws->ntiles4 : ws->ntiles) + 7) / 8;
     const int per_block = (txcd + g8 - 1) / g8;
-    if (per_block > max_tiles) { (void)hipFree(d); return fail("max_tiles too small"); }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    if (per_block > max_tiles) return fail("max_tiles too small");
+    const void* const src = n->last.src;
+    void* const dst = n->last.dst;
+    const size_t src_stride = n->last.src_stride, dst_stride = n->last.dst_stride;
     if (ablate == 3) {
         // the u8 tail kernel of the last host-route call instead of a trunk layer
-        if (n->last.f32 || !n->last.dst) { (void)hipFree(d); return fail("tail stamps need a previous uva_net_process_u8 call"); }
+        if (n->last.f32 || !dst) return fail("tail stamps need a previous uva_net_process_u8 call");
         const int nconv = (int)n->g.convs.size();
         ca.in_act = ws->act[n->last_act_buf];
         ca.out_act = nullptr;
         ca.wpk = n->layers[nconv - 1].wpk;
         ca.bias = n->layers[nconv - 1].bias;
         ca.slope = nullptr;
-        ca.src_u8 = (const uint8_t*)n->last.src;
-        ca.src_stride = n->last.src_stride;
-        ca.dst_u8 = (uint8_t*)n->last.dst;
-        ca.dst_stride = n->last.dst_stride;
-        int rc3 = launch_tail_u8(n, ws, ca);
-        ca.dbg = nullptr;
-        HIP_TRY(hipEventRecord(e0, n->stream));
-        for (int r = 0; r < 10 && !rc3; ++r) rc3 = launch_tail_u8(n, ws, ca);
-        HIP_TRY(hipEventRecord(e1, n->stream));
-        ca.dbg = d;
-        HIP_TRY(hipMemsetAsync(d, 0, bytes, n->stream));
-        if (!rc3) rc3 = launch_tail_u8(n, ws, ca);
-        if (!rc3) {
-            HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            if (kernel_ms) *kernel_ms = ms / 10;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipFree(d);
+        ca.src_u8 = (const uint8_t*)src;
+        ca.src_stride = src_stride;
+        ca.dst_u8 = (uint8_t*)dst;
+        ca.dst_stride = dst_stride;
         const int grid3 = persistent_grid(n->ncu);
         const bool pingpong_tail = n->g.nf == 64 && (n->g.scale == 2 || n->g.scale == 4);   // 4-row tiles, 2 groups
         if (tiles) *tiles = pingpong_tail ? per_block : (ca.tiles_per_xcd + grid3 / 8 - 1) / (grid3 / 8);
-        return rc3;
+        return stamped_run(n, out, max_tiles, kernel_ms, 10, [&](unsigned long long* dbg) { ca.dbg = dbg; return launch_tail_u8(n, ws, ca); });
     }
     if (ablate == 7) {
         // sub10_kernel (the whole 1x net): out[(step*12 + wave)*4 + {0 step start, 1 MFMAs done, 2 at the barrier}] of
         // workgroup 0 (max_tiles*8 words must hold 40 per step); *tiles = steps
-        if (n->last.f32 || !n->last.dst || ws->planes.size() != 1) { (void)hipFree(d); return fail("sub10 stamps need a previous whole-frame uva_net_process_u8 call"); }
-        int rc7 = launch_sub10(n, ws, n->last.src, n->last.src_stride, n->last.dst, n->last.dst_stride);
-        if (rc7 == 0 && (size_t)(ws->max_rows10[0] + S10_DRAIN + 2) * 4 * S10_NW > (size_t)max_tiles * 8) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d); return fail("max_tiles too small"); }
-        HIP_TRY(hipEventRecord(e0, n->stream));
-        for (int r = 0; r < 50 && !rc7; ++r) rc7 = launch_sub10(n, ws, n->last.src, n->last.src_stride, n->last.dst, n->last.dst_stride);
-        HIP_TRY(hipEventRecord(e1, n->stream));
-        if (!rc7) rc7 = launch_sub10(n, ws, n->last.src, n->last.src_stride, n->last.dst, n->last.dst_stride, d);
-        if (!rc7) {
-            HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            if (kernel_ms) *kernel_ms = ms / 50;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipFree(d);
+        if (n->last.f32 || !dst || ws->planes.size() != 1) return fail("sub10 stamps need a previous whole-frame uva_net_process_u8 call");
+        int rc7 = launch_sub10(n, ws, src, src_stride, dst, dst_stride);       // (builds the row table: max_rows10)
+        if (rc7 == 0 && (size_t)(ws->max_rows10[0] + S10_DRAIN + 2) * 4 * S10_NW > (size_t)max_tiles * 8) return fail("max_tiles too small");
+        if (!rc7) rc7 = stamped_run(n, out, max_tiles, kernel_ms, 50, [&](unsigned long long* dbg) { return launch_sub10(n, ws, src, src_stride, dst, dst_stride, dbg); });
         if (tiles) *tiles = ws->max_rows10[0] + S10_DRAIN;
         return rc7 ? (rc7 == 2 ? fail("frame too large for sub10_kernel") : 1) : 0;
     }
     if (ablate == 9 || ablate == 10) {
         // sub5_kernel, part 0 / part 1 (the 1x net as two launches of five layers): out[(step*12 + wave)*4 + {0 step start, 1 MFMAs
         // done (front wave), 2 at the barrier}] of workgroup 0; *tiles = steps; kernel_ms = both launches
-        if (n->last.f32 || !n->last.dst || ws->planes.size() != 1) { (void)hipFree(d); return fail("sub5 stamps need a previous whole-frame uva_net_process_u8 call"); }
-        int rc9 = launch_sub5(n, ws, n->last.src, n->last.src_stride, n->last.dst, n->last.dst_stride);
-        if (rc9 == 0 && (size_t)(ws->max_rows5 + 16) * 4 * 12 > (size_t)max_tiles * 8) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d); return fail("max_tiles too small"); }
-        HIP_TRY(hipEventRecord(e0, n->stream));
-        for (int r = 0; r < 50 && !rc9; ++r) rc9 = launch_sub5(n, ws, n->last.src, n->last.src_stride, n->last.dst, n->last.dst_stride);
-        HIP_TRY(hipEventRecord(e1, n->stream));
-        if (!rc9) rc9 = launch_sub5(n, ws, n->last.src, n->last.src_stride, n->last.dst, n->last.dst_stride, d, ablate - 9);
-        if (!rc9) {
-            HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            if (kernel_ms) *kernel_ms = ms / 50;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipFree(d);
+        if (n->last.f32 || !dst || ws->planes.size() != 1) return fail("sub5 stamps need a previous whole-frame uva_net_process_u8 call");
+        int rc9 = launch_sub5(n, ws, src, src_stride, dst, dst_stride);         // (builds the row table: max_rows5)
+        if (rc9 == 0 && (size_t)(ws->max_rows5 + 16) * 4 * 12 > (size_t)max_tiles * 8) return fail("max_tiles too small");
+        if (!rc9) rc9 = stamped_run(n, out, max_tiles, kernel_ms, 50, [&](unsigned long long* dbg) { return launch_sub5(n, ws, src, src_stride, dst, dst_stride, dbg, ablate - 9); });
         if (tiles) *tiles = ws->max_rows5 + 14;
         return rc9 ? (rc9 == 2 ? fail("frame too large for sub5_kernel") : 1) : 0;
     }
     if (ablate == 6) {
         // pair24_kernel (two 24-feature trunk layers): out[8*it + {0 top, 1 tile landed, 2 stage A done, 3 intermediate
         // complete, 4 stage B k-loop done, 5 stores issued}] of workgroup 0 / wave 0
-        if (n->g.nf != 24) { (void)hipFree(d); return fail("pair24 stamps need the 24-feature net"); }
+        if (n->g.nf != 24) return fail("pair24 stamps need the 24-feature net");
         ca.wpk2 = n->layers[2].wpk; ca.bias2 = n->layers[2].bias; ca.slope2 = n->layers[2].slope;
         ca.ntiles = ws->ntiles; ca.tiles_per_xcd = (ws->ntiles + 7) / 8;
-        ca.dbg = nullptr;
-        int rc6 = launch_pair24(n, ca);
-        HIP_TRY(hipEventRecord(e0, n->stream));
-        for (int r = 0; r < 50 && !rc6; ++r) rc6 = launch_pair24(n, ca);
-        HIP_TRY(hipEventRecord(e1, n->stream));
-        ca.dbg = d;
-        if (!rc6) rc6 = launch_pair24(n, ca);
-        if (!rc6) {
-            HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            if (kernel_ms) *kernel_ms = ms / 50;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipFree(d);
         const int grid6 = persistent_grid(n->ncu) * 2;
         if (tiles) *tiles = (ca.tiles_per_xcd + grid6 / 8 - 1) / (grid6 / 8);
-        return rc6;
+        return stamped_run(n, out, max_tiles, kernel_ms, 50, [&](unsigned long long* dbg) { ca.dbg = dbg; return launch_pair24(n, ca); });
     }
     if (ablate == 8) {
         // trunkw_kernel (the fused pair as Winograd F(2,3)): stamps of workgroup 0, both groups (out[16*it + 8*group + k], entry
         // at out[16*niter]); only an instrumented build (-DUVA_INSTRUMENT) writes them
-        if (!ws->d_stepsw || !n->layers[1].wpk_w) { (void)hipFree(d); return fail("no Winograd fused-pair schedule for this net"); }
+        if (!ws->d_stepsw || !n->layers[1].wpk_w) return fail("no Winograd fused-pair schedule for this net");
         TrunkwArgs wa;
         std::memset(&wa, 0, sizeof wa);
         wa.in_act = ws->act_base[0];
         wa.out_act = ws->act_base[1];
         wa.steps = ws->d_stepsw; wa.nsteps = ws->d_nstepsw; wa.max_steps = ws->max_stepsw; wa.sink = n->d_sink;
-        if (2 * (ws->max_stepsw + 3) + 1 > max_tiles) { (void)hipFree(d); return fail("max_tiles too small"); }
-        int rc8 = launch_trunkw(n, ws, wa, 1);
-        HIP_TRY(hipEventRecord(e0, n->stream));
-        for (int r = 0; r < 50 && !rc8; ++r) rc8 = launch_trunkw(n, ws, wa, 1);
-        HIP_TRY(hipEventRecord(e1, n->stream));
-        wa.dbg = d;
-        if (!rc8) rc8 = launch_trunkw(n, ws, wa, 1);
-        if (!rc8) {
-            HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            if (kernel_ms) *kernel_ms = ms / 50;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipFree(d);
+        if (2 * (ws->max_stepsw + 3) + 1 > max_tiles) return fail("max_tiles too small");
+        const int rc8 = stamped_run(n, out, max_tiles, kernel_ms, 50, [&](unsigned long long* dbg) { wa.dbg = dbg; return launch_trunkw(n, ws, wa, 1); });
         int ns0 = 0;
         if (!rc8) HIP_TRY(hipMemcpy(&ns0, ws->d_nstepsw, sizeof(int), hipMemcpyDeviceToHost));
         if (tiles) *tiles = ns0 + 2;
@@ -1946,30 +1838,15 @@ int uva_net_debug_trunk_stamps(uva_net* n, unsigned long long* out, int max_tile
     }
     if (ablate == 5) {
         // the fused pair kernel: stamps of workgroup 0, both groups (out[16*it + 8*group + k], entry at out[16*niter])
-        if (!ws->d_steps2) { (void)hipFree(d); return fail("no fused-pair schedule for this net"); }
+        if (!ws->d_steps2) return fail("no fused-pair schedule for this net");
         Trunk2Args ta;
         std::memset(&ta, 0, sizeof ta);
         ta.in_act = ws->act_base[0];
         ta.out_act = ws->act_base[1];
         for (int k = 0; k < 2; ++k) { ta.wpk[k] = n->layers[1 + k].wpk; ta.bias[k] = n->layers[1 + k].bias; ta.slope[k] = n->layers[1 + k].slope; }
         ta.steps = ws->d_steps2; ta.nsteps = ws->d_nsteps2; ta.max_steps = ws->max_steps2; ta.sink = n->d_sink;
-        if (2 * (ws->max_steps2 + 3) + 1 > max_tiles) { (void)hipFree(d); return fail("max_tiles too small"); }
-        int rc5 = launch_trunk2(n, ws, ta);
-        HIP_TRY(hipEventRecord(e0, n->stream));
-        for (int r = 0; r < 50 && !rc5; ++r) rc5 = launch_trunk2(n, ws, ta);
-        HIP_TRY(hipEventRecord(e1, n->stream));
-        ta.dbg = d;
-        if (!rc5) rc5 = launch_trunk2(n, ws, ta);
-        if (!rc5) {
-            HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-            HIP_TRY(hipStreamSynchronize(n->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            if (kernel_ms) *kernel_ms = ms / 50;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipFree(d);
+        if (2 * (ws->max_steps2 + 3) + 1 > max_tiles) return fail("max_tiles too small");
+        const int rc5 = stamped_run(n, out, max_tiles, kernel_ms, 50, [&](unsigned long long* dbg) { ta.dbg = dbg; return launch_trunk2(n, ws, ta); });
         std::vector<int> ns(ws->grid2);
         HIP_TRY(hipMemcpy(ns.data(), ws->d_nsteps2, ns.size() * sizeof(int), hipMemcpyDeviceToHost));
         if (tiles) *tiles = ns[0] + 2;
@@ -1978,26 +1855,8 @@ int uva_net_debug_trunk_stamps(uva_net* n, unsigned long long* out, int max_tile
     // bits 8.. of `ablate`: hundreds of timed repetitions (sustained, power-limited state) instead of 10
     const int reps = (ablate >> 8) > 0 ? (ablate >> 8) * 100 : 10;
     ablate &= 0xff;
-    int rc = launch_trunk(n, ws, ca, ablate);   // warm
-    ca.dbg = nullptr;
-    HIP_TRY(hipEventRecord(e0, n->stream));
-    for (int r = 0; r < reps && !rc; ++r) rc = launch_trunk(n, ws, ca, ablate);
-    HIP_TRY(hipEventRecord(e1, n->stream));
-    ca.dbg = d;
-    HIP_TRY(hipMemsetAsync(d, 0, bytes, n->stream));
-    if (!rc) rc = launch_trunk(n, ws, ca, ablate);
-    if (!rc) {
-        HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, n->stream));
-        HIP_TRY(hipStreamSynchronize(n->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        if (kernel_ms) *kernel_ms = ms / reps;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(d);
     if (tiles) *tiles = per_block;
-    return rc;
+    return stamped_run(n, out, max_tiles, kernel_ms, reps, [&](unsigned long long* dbg) { ca.dbg = dbg; return launch_trunk(n, ws, ca, ablate); });
 }
 
 #endif  // UVA_INSTRUMENT

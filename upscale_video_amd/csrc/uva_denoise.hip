@@ -18,17 +18,34 @@ using namespace uva;
 // ---- `-m n=K`: non-local-means denoise (upscale/upscale_processing.py:350-361) -------------------------
 namespace {
 
-struct DenoiseCtx {
-    hipStream_t stream = nullptr;
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_l = nullptr, *d_l2 = nullptr, *d_ab = nullptr, *d_ab2 = nullptr;
+// the frame buffers of a stage, all sized for cap_px pixels: in / out at 3 samples per pixel, l / l2 at 1, ab / ab2 at 2
+template <typename S>
+struct NlmFrames {
+    DevPtr<S> d_in, d_out, d_l, d_l2, d_ab, d_ab2;
     size_t cap_px = 0;
-    int* d_table[2] = {nullptr, nullptr};
+    hipError_t alloc(size_t px)
+    {
+        NlmFrames f;
+        hipError_t e = hipSuccess;
+        const size_t per[6] = {3, 3, 1, 1, 2, 2};
+        DevPtr<S>* const to[6] = {&f.d_in, &f.d_out, &f.d_l, &f.d_l2, &f.d_ab, &f.d_ab2};
+        for (int k = 0; k < 6 && e == hipSuccess; ++k) e = alloc_into(*to[k], px * per[k] * sizeof(S));
+        if (e != hipSuccess) return e;
+        f.cap_px = px;
+        *this = std::move(f);
+        return hipSuccess;
+    }
+};
+
+struct DenoiseCtx {
+    NlmFrames<uint8_t> f;
+    DevPtr<int> d_table[2];
     int table_size[2] = {0, 0};
     float table_h[2] = {-1.f, -1.f};
-    LabTables* d_lab = nullptr;          // OpenCV's 8-bit Lab tables (uva_denoise.hip.h)
+    DevPtr<LabTables> d_lab;             // OpenCV's 8-bit Lab tables (uva_denoise.hip.h)
+    Stream stream;
 };
-std::mutex g_denoise_mu;
-DenoiseCtx g_denoise[kMaxDevices];
+DeviceTable<DenoiseCtx>& g_denoise = *new DeviceTable<DenoiseCtx>;
 
 // OpenCV fast_nlmeans_denoising_invoker.hpp: almost_dist2weight_ for 8-bit samples, squared distance
 void nlm_weight_table(float h, int cn, std::vector<int>& table)
@@ -51,30 +68,22 @@ void nlm_weight_table(float h, int cn, std::vector<int>& table)
 
 int denoise_ctx(int device, size_t px, DenoiseCtx** out)
 {
-    if (select_device(device)) return 1;
-    DenoiseCtx& c = g_denoise[device];
-    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    DenoiseCtx* pc = nullptr;
+    if (g_denoise.enter(device, &pc)) return 1;
+    DenoiseCtx& c = *pc;
     if (!c.d_lab) {
         static const LabTables host_tables = [] { LabTables t; lab_tables_host(t); return t; }();
-        HIP_TRY(hipMalloc((void**)&c.d_lab, sizeof(LabTables)));
-        HIP_TRY(hipMemcpy(c.d_lab, &host_tables, sizeof(LabTables), hipMemcpyHostToDevice));
+        DevPtr<LabTables> lab;
+        HIP_TRY(alloc_into(lab, sizeof(LabTables)));
+        HIP_TRY(hipMemcpy(lab.get(), &host_tables, sizeof(LabTables), hipMemcpyHostToDevice));
+        c.d_lab = std::move(lab);
     }
-    if (c.cap_px < px) {
+    if (c.f.cap_px < px) {
         // uva_denoise_u8_device is asynchronous: frames queued on the stream may still use the buffers about to go
         // (hipFree happens to synchronise the device; said here instead of relied on)
-        if (c.cap_px) HIP_TRY(hipStreamSynchronize(c.stream));
-        for (uint8_t** p : {&c.d_in, &c.d_out, &c.d_l, &c.d_l2, &c.d_ab, &c.d_ab2}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        c.cap_px = 0;
-        HIP_TRY(hipMalloc((void**)&c.d_in, px * 3));
-        HIP_TRY(hipMalloc((void**)&c.d_out, px * 3));
-        HIP_TRY(hipMalloc((void**)&c.d_l, px));
-        HIP_TRY(hipMalloc((void**)&c.d_l2, px));
-        HIP_TRY(hipMalloc((void**)&c.d_ab, px * 2));
-        HIP_TRY(hipMalloc((void**)&c.d_ab2, px * 2));
-        c.cap_px = px;
+        if (c.f.cap_px) HIP_TRY(hipStreamSynchronize(c.stream));
+        c.f = NlmFrames<uint8_t>();
+        HIP_TRY(c.f.alloc(px));
     }
     *out = &c;
     return 0;
@@ -85,10 +94,11 @@ int denoise_table(DenoiseCtx& c, int which, float h, int cn)
     if (c.table_h[which] == h && c.d_table[which]) return 0;
     std::vector<int> t;
     nlm_weight_table(h, cn, t);
-    if (c.d_table[which]) (void)hipFree(c.d_table[which]);
-    c.d_table[which] = nullptr;
-    HIP_TRY(hipMalloc((void**)&c.d_table[which], t.size() * sizeof(int)));
-    HIP_TRY(hipMemcpy(c.d_table[which], t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+    c.d_table[which].reset();
+    DevPtr<int> d;
+    HIP_TRY(alloc_into(d, t.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(d.get(), t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+    c.d_table[which] = std::move(d);
     c.table_size[which] = (int)t.size();
     c.table_h[which] = h;
     return 0;
@@ -98,43 +108,33 @@ int denoise_table(DenoiseCtx& c, int which, float h, int cn)
 // ---- `-m n=K` at --bit-depth 16 (uva_denoise16.hip.h): its own buffers and tables, the 8-bit stage's
 // stream (uva_denoise_synchronize waits for both) and lock
 struct Denoise16Ctx {
-    uint16_t *d_in = nullptr, *d_out = nullptr, *d_l = nullptr, *d_l2 = nullptr, *d_ab = nullptr, *d_ab2 = nullptr;
-    size_t cap_px = 0;
-    int* d_table[2] = {nullptr, nullptr};
+    NlmFrames<uint16_t> f;
+    DevPtr<int> d_table[2];
     int table_size[2] = {0, 0};
     float table_h[2] = {-1.f, -1.f};
-    Lab16Tables* d_lab = nullptr;
+    DevPtr<Lab16Tables> d_lab;
 };
-Denoise16Ctx g_denoise16[kMaxDevices];
+DeviceTable<Denoise16Ctx>& g_denoise16 = *new DeviceTable<Denoise16Ctx>;       // (its own lock is not used: g_denoise.mu)
 
 int denoise16_ctx(int device, size_t px, Denoise16Ctx** out, hipStream_t* stream)
 {
-    if (select_device(device)) return 1;
-    DenoiseCtx& c8 = g_denoise[device];
-    if (!c8.stream) HIP_TRY(hipStreamCreateWithFlags(&c8.stream, hipStreamNonBlocking));
-    Denoise16Ctx& c = g_denoise16[device];
+    DenoiseCtx* c8 = nullptr;
+    if (g_denoise.enter(device, &c8)) return 1;
+    Denoise16Ctx& c = g_denoise16.at(device);
     if (!c.d_lab) {
         static const Lab16Tables* host_tables = [] { Lab16Tables* t = new Lab16Tables; lab16_tables_host(*t); return t; }();
-        HIP_TRY(hipMalloc((void**)&c.d_lab, sizeof(Lab16Tables)));
-        HIP_TRY(hipMemcpy(c.d_lab, host_tables, sizeof(Lab16Tables), hipMemcpyHostToDevice));
+        DevPtr<Lab16Tables> lab;
+        HIP_TRY(alloc_into(lab, sizeof(Lab16Tables)));
+        HIP_TRY(hipMemcpy(lab.get(), host_tables, sizeof(Lab16Tables), hipMemcpyHostToDevice));
+        c.d_lab = std::move(lab);
     }
-    if (c.cap_px < px) {
-        if (c.cap_px) HIP_TRY(hipStreamSynchronize(c8.stream));      // queued frames may still use the buffers about to go
-        for (uint16_t** p : {&c.d_in, &c.d_out, &c.d_l, &c.d_l2, &c.d_ab, &c.d_ab2}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        c.cap_px = 0;
-        HIP_TRY(hipMalloc((void**)&c.d_in, px * 6));
-        HIP_TRY(hipMalloc((void**)&c.d_out, px * 6));
-        HIP_TRY(hipMalloc((void**)&c.d_l, px * 2));
-        HIP_TRY(hipMalloc((void**)&c.d_l2, px * 2));
-        HIP_TRY(hipMalloc((void**)&c.d_ab, px * 4));
-        HIP_TRY(hipMalloc((void**)&c.d_ab2, px * 4));
-        c.cap_px = px;
+    if (c.f.cap_px < px) {
+        if (c.f.cap_px) HIP_TRY(hipStreamSynchronize(c8->stream));      // queued frames may still use the buffers about to go
+        c.f = NlmFrames<uint16_t>();
+        HIP_TRY(c.f.alloc(px));
     }
     *out = &c;
-    *stream = c8.stream;
+    *stream = c8->stream;
     return 0;
 }
 
@@ -144,11 +144,12 @@ int denoise16_table(Denoise16Ctx& c, int which, float h, int cn)
     if (c.table_h[which] == h && c.d_table[which]) return 0;
     std::vector<int> t;
     if (!nlm16_weight_table(h, cn, t)) return fail("denoise strength too large for the 16-bit weight table");
-    if (c.d_table[which]) (void)hipFree(c.d_table[which]);
-    c.d_table[which] = nullptr;
+    c.d_table[which].reset();
     c.table_h[which] = -1.f;
-    HIP_TRY(hipMalloc((void**)&c.d_table[which], t.size() * sizeof(int)));
-    HIP_TRY(hipMemcpy(c.d_table[which], t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+    DevPtr<int> d;
+    HIP_TRY(alloc_into(d, t.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(d.get(), t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+    c.d_table[which] = std::move(d);
     c.table_size[which] = (int)t.size();
     c.table_h[which] = h;
     return 0;
@@ -159,10 +160,10 @@ int denoise16_launch(Denoise16Ctx* c, hipStream_t stream, const uint16_t* d_src,
                      int h, int w)
 {
     const dim3 rows((w + 255) / 256, h), tiles((w + NLM_BLK - 1) / NLM_BLK, (h + NLM_BLK - 1) / NLM_BLK);
-    hipLaunchKernelGGL(nlm_bgr2lab16, rows, dim3(256), 0, stream, d_src, src_stride, h, w, c->d_l, c->d_ab, c->d_lab);
-    hipLaunchKernelGGL(nlm_plane16<1>, tiles, dim3(NLM_BLK * NLM_BLK), 0, stream, c->d_l, h, w, c->d_table[0], c->table_size[0], c->d_l2);
-    hipLaunchKernelGGL(nlm_plane16<2>, tiles, dim3(NLM_BLK * NLM_BLK), 0, stream, c->d_ab, h, w, c->d_table[1], c->table_size[1], c->d_ab2);
-    hipLaunchKernelGGL(nlm_lab2bgr16, rows, dim3(256), 0, stream, c->d_l2, c->d_ab2, h, w, d_dst, dst_stride, c->d_lab);
+    hipLaunchKernelGGL(nlm_bgr2lab16, rows, dim3(256), 0, stream, d_src, src_stride, h, w, c->f.d_l, c->f.d_ab, c->d_lab);
+    hipLaunchKernelGGL(nlm_plane16<1>, tiles, dim3(NLM_BLK * NLM_BLK), 0, stream, c->f.d_l, h, w, c->d_table[0], c->table_size[0], c->f.d_l2);
+    hipLaunchKernelGGL(nlm_plane16<2>, tiles, dim3(NLM_BLK * NLM_BLK), 0, stream, c->f.d_ab, h, w, c->d_table[1], c->table_size[1], c->f.d_ab2);
+    hipLaunchKernelGGL(nlm_lab2bgr16, rows, dim3(256), 0, stream, c->f.d_l2, c->f.d_ab2, h, w, d_dst, dst_stride, c->d_lab);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -174,38 +175,15 @@ constexpr float NLM16_MAX_H = 64.f;
 
 void uva::denoise_release_all()
 {
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
-    for (int d = 0; d < kMaxDevices; ++d) {
-        DenoiseCtx& c = g_denoise[d];
-        if (!c.stream && !c.d_in && !c.d_table[0] && !c.d_table[1]) continue;
-        (void)hipSetDevice(d);
-        if (c.stream) (void)hipStreamSynchronize(c.stream);
-        for (uint8_t* p : {c.d_in, c.d_out, c.d_l, c.d_l2, c.d_ab, c.d_ab2})
-            if (p) (void)hipFree(p);
-        for (int* t : c.d_table)
-            if (t) (void)hipFree(t);
-        if (c.d_lab) (void)hipFree(c.d_lab);
-        if (c.stream) (void)hipStreamDestroy(c.stream);
-        c = DenoiseCtx();
-    }
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
+    g_denoise.release_all();
 }
 
-// (called with g_denoise_mu NOT held, before denoise_release_all destroys the stream)
+// (before denoise_release_all destroys the stream that both stages use)
 void uva::denoise16_release_all()
 {
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
-    for (int d = 0; d < kMaxDevices; ++d) {
-        Denoise16Ctx& c = g_denoise16[d];
-        if (!c.d_in && !c.d_table[0] && !c.d_table[1] && !c.d_lab) continue;
-        (void)hipSetDevice(d);
-        if (g_denoise[d].stream) (void)hipStreamSynchronize(g_denoise[d].stream);
-        for (uint16_t* p : {c.d_in, c.d_out, c.d_l, c.d_l2, c.d_ab, c.d_ab2})
-            if (p) (void)hipFree(p);
-        for (int* t : c.d_table)
-            if (t) (void)hipFree(t);
-        if (c.d_lab) (void)hipFree(c.d_lab);
-        c = Denoise16Ctx();
-    }
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
+    g_denoise16.release_all([](int d) { return g_denoise.ctx[d].stream.get(); });
 }
 
 extern "C" {
@@ -218,14 +196,14 @@ int uva_denoise_u8(int device, const uint8_t* in, int h, int w, size_t in_stride
     if (!in || !out || h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image");
     if (in_stride < (size_t)w * 3 || out_stride < (size_t)w * 3) return fail("row stride too small");
     if (!(h_luma > 0.f) || !(h_color > 0.f)) return fail("denoise strength must be positive");
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     DenoiseCtx* c = nullptr;
     const size_t px = (size_t)h * w;
     if (denoise_ctx(device, px, &c)) return 1;
     if (denoise_table(*c, 0, h_luma, 1) || denoise_table(*c, 1, h_color, 2)) return 1;
-    HIP_TRY(hipMemcpy2DAsync(c->d_in, (size_t)w * 3, in, in_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream));
-    if (denoise_launch(c, c->d_in, (size_t)w * 3, c->d_out, (size_t)w * 3, h, w)) return 1;
-    HIP_TRY(hipMemcpy2DAsync(out, out_stride, c->d_out, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(c->f.d_in, (size_t)w * 3, in, in_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream));
+    if (denoise_launch(c, c->f.d_in, (size_t)w * 3, c->f.d_out, (size_t)w * 3, h, w)) return 1;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, c->f.d_out, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -234,10 +212,10 @@ int uva_denoise_u8(int device, const uint8_t* in, int h, int w, size_t in_stride
 static int denoise_launch(DenoiseCtx* c, const uint8_t* d_src, size_t src_stride, uint8_t* d_dst, size_t dst_stride, int h, int w)
 {
     const dim3 rows((w + 255) / 256, h), tiles((w + NLM_BLK - 1) / NLM_BLK, (h + NLM_BLK - 1) / NLM_BLK);
-    hipLaunchKernelGGL(nlm_bgr2lab, rows, dim3(256), 0, c->stream, d_src, src_stride, h, w, c->d_l, c->d_ab, c->d_lab);
-    hipLaunchKernelGGL(nlm_plane<1>, tiles, dim3(NLM_BLK * NLM_BLK), 0, c->stream, c->d_l, h, w, c->d_table[0], c->table_size[0], c->d_l2);
-    hipLaunchKernelGGL(nlm_plane<2>, tiles, dim3(NLM_BLK * NLM_BLK), 0, c->stream, c->d_ab, h, w, c->d_table[1], c->table_size[1], c->d_ab2);
-    hipLaunchKernelGGL(nlm_lab2bgr, rows, dim3(256), 0, c->stream, c->d_l2, c->d_ab2, h, w, d_dst, dst_stride, c->d_lab);
+    hipLaunchKernelGGL(nlm_bgr2lab, rows, dim3(256), 0, c->stream, d_src, src_stride, h, w, c->f.d_l, c->f.d_ab, c->d_lab);
+    hipLaunchKernelGGL(nlm_plane<1>, tiles, dim3(NLM_BLK * NLM_BLK), 0, c->stream, c->f.d_l, h, w, c->d_table[0], c->table_size[0], c->f.d_l2);
+    hipLaunchKernelGGL(nlm_plane<2>, tiles, dim3(NLM_BLK * NLM_BLK), 0, c->stream, c->f.d_ab, h, w, c->d_table[1], c->table_size[1], c->f.d_ab2);
+    hipLaunchKernelGGL(nlm_lab2bgr, rows, dim3(256), 0, c->stream, c->f.d_l2, c->f.d_ab2, h, w, d_dst, dst_stride, c->d_lab);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -249,7 +227,7 @@ int uva_denoise_u8_device(int device, const void* d_in, int h, int w, size_t in_
     if (in_stride < (size_t)w * 3 || out_stride < (size_t)w * 3) return fail("row stride too small");
     if (!(h_luma > 0.f) || !(h_color > 0.f)) return fail("denoise strength must be positive");
     if (check_fence_nets(device, after, before, "uva_denoise_u8_device")) return 1;
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     DenoiseCtx* c = nullptr;
     if (denoise_ctx(device, (size_t)h * w, &c)) return 1;
     // the weight tables are uploaded with a blocking copy: the stream must not be reading the old ones
@@ -263,44 +241,44 @@ int uva_denoise_u8_device(int device, const void* d_in, int h, int w, size_t in_
 
 int uva_denoise_synchronize(int device)
 {
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     if (device < 0 || device >= kMaxDevices) return fail("bad device");
-    if (!g_denoise[device].stream) return 0;
+    if (!g_denoise.ctx[device].stream) return 0;
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamSynchronize(g_denoise[device].stream));
+    HIP_TRY(hipStreamSynchronize(g_denoise.ctx[device].stream));
     return 0;
 }
 
 int uva_debug_denoise_stage(int device, int stage, const uint8_t* in, int h, int w, float strength, uint8_t* out)
 {
     if (!in || !out || h <= 0 || w <= 0) return fail("bad argument");
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     DenoiseCtx* c = nullptr;
     const size_t px = (size_t)h * w;
     if (denoise_ctx(device, px, &c)) return 1;
     const dim3 rows((w + 255) / 256, h), tiles((w + NLM_BLK - 1) / NLM_BLK, (h + NLM_BLK - 1) / NLM_BLK);
     if (stage == 0) {          // bgr [h][w][3] -> Lab interleaved [h][w][3]
-        HIP_TRY(hipMemcpy(c->d_in, in, px * 3, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nlm_bgr2lab, rows, dim3(256), 0, c->stream, c->d_in, (size_t)w * 3, h, w, c->d_l, c->d_ab, c->d_lab);
+        HIP_TRY(hipMemcpy(c->f.d_in, in, px * 3, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nlm_bgr2lab, rows, dim3(256), 0, c->stream, c->f.d_in, (size_t)w * 3, h, w, c->f.d_l, c->f.d_ab, c->d_lab);
         HIP_TRY(hipStreamSynchronize(c->stream));
         std::vector<uint8_t> l(px), ab(px * 2);
-        HIP_TRY(hipMemcpy(l.data(), c->d_l, px, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ab.data(), c->d_ab, px * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(l.data(), c->f.d_l, px, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ab.data(), c->f.d_ab, px * 2, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < px; ++i) { out[3 * i] = l[i]; out[3 * i + 1] = ab[2 * i]; out[3 * i + 2] = ab[2 * i + 1]; }
     } else if (stage == 1) {   // Lab interleaved -> bgr
         std::vector<uint8_t> l(px), ab(px * 2);
         for (size_t i = 0; i < px; ++i) { l[i] = in[3 * i]; ab[2 * i] = in[3 * i + 1]; ab[2 * i + 1] = in[3 * i + 2]; }
-        HIP_TRY(hipMemcpy(c->d_l, l.data(), px, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_ab, ab.data(), px * 2, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nlm_lab2bgr, rows, dim3(256), 0, c->stream, c->d_l, c->d_ab, h, w, c->d_out, (size_t)w * 3, c->d_lab);
+        HIP_TRY(hipMemcpy(c->f.d_l, l.data(), px, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->f.d_ab, ab.data(), px * 2, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nlm_lab2bgr, rows, dim3(256), 0, c->stream, c->f.d_l, c->f.d_ab, h, w, c->f.d_out, (size_t)w * 3, c->d_lab);
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(out, c->d_out, px * 3, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, c->f.d_out, px * 3, hipMemcpyDeviceToHost));
     } else if (stage == 2 || stage == 3) {   // NLM on a 1-channel (2) / 2-channel (3) u8 image
         const int cn = stage - 1;
         if (!(strength > 0.f)) return fail("denoise strength must be positive");
         if (denoise_table(*c, cn - 1, strength, cn)) return 1;
-        uint8_t* src = cn == 1 ? c->d_l : c->d_ab;
-        uint8_t* dst = cn == 1 ? c->d_l2 : c->d_ab2;
+        uint8_t* src = cn == 1 ? c->f.d_l : c->f.d_ab;
+        uint8_t* dst = cn == 1 ? c->f.d_l2 : c->f.d_ab2;
         HIP_TRY(hipMemcpy(src, in, px * cn, hipMemcpyHostToDevice));
         if (cn == 1) hipLaunchKernelGGL(nlm_plane<1>, tiles, dim3(NLM_BLK * NLM_BLK), 0, c->stream, src, h, w, c->d_table[0], c->table_size[0], dst);
         else hipLaunchKernelGGL(nlm_plane<2>, tiles, dim3(NLM_BLK * NLM_BLK), 0, c->stream, src, h, w, c->d_table[1], c->table_size[1], dst);
@@ -320,16 +298,16 @@ int uva_denoise_u16(int device, const uint16_t* in, int h, int w, size_t in_stri
     if (!in || !out || h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad image");
     if (in_stride < (size_t)w * 6 || out_stride < (size_t)w * 6) return fail("row stride too small");
     if (!(h_luma > 0.f) || !(h_color > 0.f) || h_luma > NLM16_MAX_H || h_color > NLM16_MAX_H) return fail("denoise strength must be in (0, 64]");
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     Denoise16Ctx* c = nullptr;
     hipStream_t stream = nullptr;
     const size_t px = (size_t)h * w;
     if (denoise16_ctx(device, px, &c, &stream)) return 1;
     if (c->table_h[0] != h_luma || c->table_h[1] != h_color) HIP_TRY(hipStreamSynchronize(stream));
     if (denoise16_table(*c, 0, h_luma, 1) || denoise16_table(*c, 1, h_color, 2)) return 1;
-    HIP_TRY(hipMemcpy2DAsync(c->d_in, (size_t)w * 6, in, in_stride, (size_t)w * 6, h, hipMemcpyHostToDevice, stream));
-    if (denoise16_launch(c, stream, c->d_in, (size_t)w * 6, c->d_out, (size_t)w * 6, h, w)) return 1;
-    HIP_TRY(hipMemcpy2DAsync(out, out_stride, c->d_out, (size_t)w * 6, (size_t)w * 6, h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpy2DAsync(c->f.d_in, (size_t)w * 6, in, in_stride, (size_t)w * 6, h, hipMemcpyHostToDevice, stream));
+    if (denoise16_launch(c, stream, c->f.d_in, (size_t)w * 6, c->f.d_out, (size_t)w * 6, h, w)) return 1;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, c->f.d_out, (size_t)w * 6, (size_t)w * 6, h, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
 }
@@ -342,7 +320,7 @@ int uva_denoise_u16_device(int device, const void* d_in, int h, int w, size_t in
     if ((in_stride | out_stride | (size_t)d_in | (size_t)d_out) & 1) return fail("uva_denoise_u16_device: u16 rows must be 2-byte aligned");
     if (!(h_luma > 0.f) || !(h_color > 0.f) || h_luma > NLM16_MAX_H || h_color > NLM16_MAX_H) return fail("denoise strength must be in (0, 64]");
     if (check_fence_nets(device, after, before, "uva_denoise_u16_device")) return 1;
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     Denoise16Ctx* c = nullptr;
     hipStream_t stream = nullptr;
     if (denoise16_ctx(device, (size_t)h * w, &c, &stream)) return 1;
@@ -358,7 +336,7 @@ int uva_denoise_u16_device(int device, const void* d_in, int h, int w, size_t in
 int uva_debug_denoise16_stage(int device, int stage, const uint16_t* in, int h, int w, float strength, uint16_t* out)
 {
     if (!in || !out || h <= 0 || w <= 0 || (long long)h * w > (1ll << 28)) return fail("bad argument");
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    std::lock_guard<std::mutex> lk(g_denoise.mu);
     Denoise16Ctx* c = nullptr;
     hipStream_t stream = nullptr;
     const size_t px = (size_t)h * w;
@@ -366,29 +344,29 @@ int uva_debug_denoise16_stage(int device, int stage, const uint16_t* in, int h, 
     HIP_TRY(hipStreamSynchronize(stream));           // the blocking copies below write buffers queued frames may still read
     const dim3 rows((w + 255) / 256, h), tiles((w + NLM_BLK - 1) / NLM_BLK, (h + NLM_BLK - 1) / NLM_BLK);
     if (stage == 0) {          // bgr [h][w][3] -> Lab interleaved [h][w][3]
-        HIP_TRY(hipMemcpy(c->d_in, in, px * 6, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nlm_bgr2lab16, rows, dim3(256), 0, stream, c->d_in, (size_t)w * 6, h, w, c->d_l, c->d_ab, c->d_lab);
+        HIP_TRY(hipMemcpy(c->f.d_in, in, px * 6, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nlm_bgr2lab16, rows, dim3(256), 0, stream, c->f.d_in, (size_t)w * 6, h, w, c->f.d_l, c->f.d_ab, c->d_lab);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
         std::vector<uint16_t> l(px), ab(px * 2);
-        HIP_TRY(hipMemcpy(l.data(), c->d_l, px * 2, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ab.data(), c->d_ab, px * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(l.data(), c->f.d_l, px * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ab.data(), c->f.d_ab, px * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < px; ++i) { out[3 * i] = l[i]; out[3 * i + 1] = ab[2 * i]; out[3 * i + 2] = ab[2 * i + 1]; }
     } else if (stage == 1) {   // Lab interleaved -> bgr
         std::vector<uint16_t> l(px), ab(px * 2);
         for (size_t i = 0; i < px; ++i) { l[i] = in[3 * i]; ab[2 * i] = in[3 * i + 1]; ab[2 * i + 1] = in[3 * i + 2]; }
-        HIP_TRY(hipMemcpy(c->d_l, l.data(), px * 2, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_ab, ab.data(), px * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nlm_lab2bgr16, rows, dim3(256), 0, stream, c->d_l, c->d_ab, h, w, c->d_out, (size_t)w * 6, c->d_lab);
+        HIP_TRY(hipMemcpy(c->f.d_l, l.data(), px * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->f.d_ab, ab.data(), px * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nlm_lab2bgr16, rows, dim3(256), 0, stream, c->f.d_l, c->f.d_ab, h, w, c->f.d_out, (size_t)w * 6, c->d_lab);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(out, c->d_out, px * 6, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, c->f.d_out, px * 6, hipMemcpyDeviceToHost));
     } else if (stage == 2 || stage == 3) {   // NLM on a 1-channel (2) / 2-channel (3) u16 image
         const int cn = stage - 1;
         if (!(strength > 0.f) || strength > NLM16_MAX_H) return fail("denoise strength must be in (0, 64]");
         if (denoise16_table(*c, cn - 1, strength, cn)) return 1;
-        uint16_t* src = cn == 1 ? c->d_l : c->d_ab;
-        uint16_t* dst = cn == 1 ? c->d_l2 : c->d_ab2;
+        uint16_t* src = cn == 1 ? c->f.d_l : c->f.d_ab;
+        uint16_t* dst = cn == 1 ? c->f.d_l2 : c->f.d_ab2;
         HIP_TRY(hipMemcpy(src, in, px * cn * 2, hipMemcpyHostToDevice));
         if (cn == 1) hipLaunchKernelGGL(nlm_plane16<1>, tiles, dim3(NLM_BLK * NLM_BLK), 0, stream, src, h, w, c->d_table[0], c->table_size[0], dst);
         else hipLaunchKernelGGL(nlm_plane16<2>, tiles, dim3(NLM_BLK * NLM_BLK), 0, stream, src, h, w, c->d_table[1], c->table_size[1], dst);

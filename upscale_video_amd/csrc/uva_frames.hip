@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -22,31 +23,21 @@ using namespace uva;
 namespace {
 
 struct PixCtx {                          // per device: the conversions' own stream and buffers
-    hipStream_t stream = nullptr;
-    uint8_t *d_in = nullptr, *d_mid = nullptr, *d_out = nullptr;
-    size_t in_cap = 0, mid_cap = 0, out_cap = 0;
-    FrameDiffStats* d_stats = nullptr;   // uva_frame_diff's record
-    unsigned long long* d_sums = nullptr;    // uva_crop_sums' line sums: rows, then columns
-    size_t sums_cap = 0;
+    DevBuf<uint8_t> d_in, d_mid, d_out;
+    DevPtr<FrameDiffStats> d_stats;      // uva_frame_diff's record
+    DevBuf<unsigned long long> d_sums;   // uva_crop_sums' line sums: rows, then columns
+    Stream stream;
 };
-std::mutex g_pix_mu;
-PixCtx g_pix[kMaxDevices];
+DeviceTable<PixCtx>& g_pix = *new DeviceTable<PixCtx>;
 
-int pix_ctx(int device, PixCtx** out)
-{
-    if (select_device(device)) return 1;
-    PixCtx& c = g_pix[device];
-    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    *out = &c;
-    return 0;
-}
+int pix_ctx(int device, PixCtx** out) { return g_pix.enter(device, out); }
 
 // uva_pix_convert_device is asynchronous: frames queued on the stream may still use a buffer about to be replaced
-int pix_grow(PixCtx& c, uint8_t** p, size_t* cap, size_t bytes)
+int pix_grow(PixCtx& c, DevBuf<uint8_t>& b, size_t bytes)
 {
-    if (*cap >= bytes) return 0;
-    if (*cap) HIP_TRY(hipStreamSynchronize(c.stream));
-    return grow_dev(p, cap, bytes);
+    if (b.cap() >= bytes) return 0;
+    if (b.cap()) HIP_TRY(hipStreamSynchronize(c.stream));
+    return grow_dev(b, bytes);
 }
 
 int pix_check(const void* in, int in_fmt, const void* out, int out_fmt, int h, int w, int colour, bool u16 = false)
@@ -70,7 +61,7 @@ int pix_convert_launch(PixCtx& c, int bits, const uint8_t* d_in, int in_fmt, uin
     }
     if (in_fmt == native) return pix_from_native(c.stream, bits, out_fmt, colour, d_in, d_out, h, w);
     if (out_fmt == native) return pix_to_native(c.stream, bits, in_fmt, colour, d_in, d_out, h, w);
-    if (pix_grow(c, &c.d_mid, &c.mid_cap, pix_frame_bytes(native, h, w))) return 1;
+    if (pix_grow(c, c.d_mid, pix_frame_bytes(native, h, w))) return 1;
     return pix_to_native(c.stream, bits, in_fmt, colour, d_in, c.d_mid, h, w) ||
            pix_from_native(c.stream, bits, out_fmt, colour, c.d_mid, d_out, h, w);
 }
@@ -79,11 +70,11 @@ int pix_convert_launch(PixCtx& c, int bits, const uint8_t* d_in, int in_fmt, uin
 int pix_convert_host(int device, int bits, const void* in, int in_fmt, void* out, int out_fmt, int h, int w, int colour)
 {
     if (pix_check(in, in_fmt, out, out_fmt, h, w, colour, bits == 16)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     const size_t nin = pix_frame_bytes(in_fmt, h, w), nout = pix_frame_bytes(out_fmt, h, w);
-    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    if (pix_grow(*c, c->d_in, nin) || pix_grow(*c, c->d_out, nout)) return 1;
     HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
     if (pix_convert_launch(*c, bits, c->d_in, in_fmt, c->d_out, out_fmt, h, w, colour)) return 1;
     HIP_TRY(hipMemcpyAsync(out, c->d_out, nout, hipMemcpyDeviceToHost, c->stream));
@@ -95,19 +86,8 @@ int pix_convert_host(int device, int bits, const void* in, int in_fmt, void* out
 
 void uva::pix_release_all()
 {
-    std::lock_guard<std::mutex> lk(g_pix_mu);
-    for (int d = 0; d < kMaxDevices; ++d) {
-        PixCtx& c = g_pix[d];
-        if (!c.stream) continue;
-        (void)hipSetDevice(d);
-        (void)hipStreamSynchronize(c.stream);
-        for (uint8_t* p : {c.d_in, c.d_mid, c.d_out})
-            if (p) (void)hipFree(p);
-        if (c.d_stats) (void)hipFree(c.d_stats);
-        if (c.d_sums) (void)hipFree(c.d_sums);
-        (void)hipStreamDestroy(c.stream);
-        c = PixCtx();
-    }
+    std::lock_guard<std::mutex> lk(g_pix.mu);
+    g_pix.release_all();
 }
 
 // the packed frame `src` of fmt -> the net's BGR frame `bgr` at `bits` (8: u8 [h][w][3], 16: u16) on `stream` ...
@@ -138,7 +118,7 @@ int uva_pix_convert_device(int device, const void* d_in, int in_fmt, void* d_out
 {
     if (pix_check(d_in, in_fmt, d_out, out_fmt, h, w, colour)) return 1;
     if (check_fence_nets(device, after, before, "uva_pix_convert_device")) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     if (fence_after(after, c->stream)) return 1;
@@ -187,7 +167,7 @@ int uva_resize_device(int device, const void* d_in, int h, int w, size_t in_stri
 {
     if (resize_check(d_in, h, w, in_stride, d_out, oh, ow, out_stride, filter, bits)) return 1;
     if (check_fence_nets(device, after, before, "uva_resize_device")) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     if (fence_after(after, c->stream)) return 1;
@@ -201,14 +181,14 @@ int uva_resize(int device, const void* in, int h, int w, size_t in_stride, void*
                int bits)
 {
     if (resize_check(in, h, w, in_stride, out, oh, ow, out_stride, filter, bits)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     // the frames go up and come down with their row padding, so that the kernel works on the caller's strides; a padded
     // result buffer goes up first (what lies between its rows comes back as it was)
     const size_t in_row = (size_t)w * 3 * (bits / 8), out_row = (size_t)ow * 3 * (bits / 8);
     const size_t nin = in_stride * (size_t)(h - 1) + in_row, nout = out_stride * (size_t)(oh - 1) + out_row;
-    if (pix_grow(*c, &c->d_in, &c->in_cap, nin) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    if (pix_grow(*c, c->d_in, nin) || pix_grow(*c, c->d_out, nout)) return 1;
     HIP_TRY(hipMemcpyAsync(c->d_in, in, nin, hipMemcpyHostToDevice, c->stream));
     if (out_stride != out_row) HIP_TRY(hipMemcpyAsync(c->d_out, out, nout, hipMemcpyHostToDevice, c->stream));
     std::string err;
@@ -229,10 +209,10 @@ int frame_diff_check(const void* a, const void* b, int fmt, int h, int w, int th
     return 0;
 }
 
-// the record of the frames d_a, d_b on the conversions' stream, read back and waited for (g_pix_mu held)
+// the record of the frames d_a, d_b on the conversions' stream, read back and waited for (g_pix.mu held)
 int frame_diff_run(PixCtx& c, const void* d_a, const void* d_b, int fmt, int h, int w, int threshold, unsigned long long* stats)
 {
-    if (!c.d_stats) HIP_TRY(hipMalloc((void**)&c.d_stats, sizeof(FrameDiffStats)));
+    if (!c.d_stats) HIP_TRY(alloc_into(c.d_stats, sizeof(FrameDiffStats)));
     FrameDiffStats st;
     HIP_TRY(launch_frame_diff(c.stream, d_a, d_b, pix_frame_bytes(fmt, h, w), fmt, (unsigned)threshold, c.d_stats));
     HIP_TRY(hipMemcpyAsync(&st, c.d_stats, sizeof st, hipMemcpyDeviceToHost, c.stream));
@@ -245,11 +225,11 @@ int frame_diff_run(PixCtx& c, const void* d_a, const void* d_b, int fmt, int h, 
 int uva_frame_diff(int device, const void* a, const void* b, int fmt, int h, int w, int threshold, unsigned long long* stats)
 {
     if (frame_diff_check(a, b, fmt, h, w, threshold, stats)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     const size_t bytes = pix_frame_bytes(fmt, h, w);
-    if (pix_grow(*c, &c->d_in, &c->in_cap, bytes) || pix_grow(*c, &c->d_out, &c->out_cap, bytes)) return 1;
+    if (pix_grow(*c, c->d_in, bytes) || pix_grow(*c, c->d_out, bytes)) return 1;
     HIP_TRY(hipMemcpyAsync(c->d_in, a, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_out, b, bytes, hipMemcpyHostToDevice, c->stream));
     return frame_diff_run(*c, c->d_in, c->d_out, fmt, h, w, threshold, stats);
@@ -259,7 +239,7 @@ int uva_frame_diff_device(int device, const void* d_a, const void* d_b, int fmt,
 {
     if (frame_diff_check(d_a, d_b, fmt, h, w, threshold, stats)) return 1;
     if ((((uintptr_t)d_a | (uintptr_t)d_b) & 15) != 0) return fail("uva_frame_diff_device: the frames must start at 16-byte aligned addresses");
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     return frame_diff_run(*c, d_a, d_b, fmt, h, w, threshold, stats);
@@ -282,13 +262,13 @@ size_t crop_read_bytes(int fmt, int h, int w)
     return (size_t)h * w * cs.comps * cs.bytes;
 }
 
-// the line sums of d_frame on the conversions' stream, read back and waited for (g_pix_mu held)
+// the line sums of d_frame on the conversions' stream, read back and waited for (g_pix.mu held)
 int crop_sums_run(PixCtx& c, const void* d_frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
 {
     const size_t need = sizeof(unsigned long long) * ((size_t)h + w);
-    if (c.sums_cap < need) {
+    if (c.d_sums.cap() < need) {
         HIP_TRY(hipStreamSynchronize(c.stream));
-        if (grow_dev(&c.d_sums, &c.sums_cap, need)) return 1;
+        if (grow_dev(c.d_sums, need)) return 1;
     }
     HIP_TRY(launch_crop_sums(c.stream, d_frame, fmt, h, w, c.d_sums, c.d_sums + h, max_groups));
     HIP_TRY(hipMemcpyAsync(rows, c.d_sums, sizeof(unsigned long long) * (size_t)h, hipMemcpyDeviceToHost, c.stream));
@@ -300,11 +280,11 @@ int crop_sums_run(PixCtx& c, const void* d_frame, int fmt, int h, int w, unsigne
 int crop_sums_host(int device, const void* frame, int fmt, int h, int w, unsigned long long* rows, unsigned long long* cols, int max_groups)
 {
     if (crop_sums_check(frame, fmt, h, w, rows, cols)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     const size_t bytes = crop_read_bytes(fmt, h, w);
-    if (pix_grow(*c, &c->d_in, &c->in_cap, bytes)) return 1;
+    if (pix_grow(*c, c->d_in, bytes)) return 1;
     HIP_TRY(hipMemcpyAsync(c->d_in, frame, bytes, hipMemcpyHostToDevice, c->stream));
     return crop_sums_run(*c, c->d_in, fmt, h, w, rows, cols, max_groups);
 }
@@ -332,7 +312,7 @@ int uva_crop_sums_device(int device, const void* d_frame, int fmt, int h, int w,
 {
     if (crop_sums_check(d_frame, fmt, h, w, rows, cols)) return 1;
     if (((uintptr_t)d_frame & 15) != 0) return fail("uva_crop_sums_device: the frame must start at a 16-byte aligned address");
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     return crop_sums_run(*c, d_frame, fmt, h, w, rows, cols, 0);
@@ -360,14 +340,14 @@ int uva_pix_window_check(int fmt, int src_h, int src_w, int x, int y, int h, int
 int uva_pix_window(int device, const void* in, int fmt, int src_h, int src_w, int x, int y, int h, int w, void* out)
 {
     if (pix_window_check(in, fmt, src_h, src_w, x, y, h, w, out)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     WindowPlane pl[3];
     const int np = crop_window_planes(fmt, src_h, src_w, x, y, h, w, pl);
     size_t at[3] = {0, 0, 0};
     const size_t stage = pix_window_staging(pl, np, at), nout = pix_frame_bytes(fmt, h, w);
-    if (pix_grow(*c, &c->d_in, &c->in_cap, stage) || pix_grow(*c, &c->d_out, &c->out_cap, nout)) return 1;
+    if (pix_grow(*c, c->d_in, stage) || pix_grow(*c, c->d_out, nout)) return 1;
     // the window's rows go up at full width, one copy per plane; the kernel compacts their columns
     for (int p = 0; p < np; ++p)
         HIP_TRY(hipMemcpyAsync(c->d_in + at[p], (const uint8_t*)in + pl[p].src_off + (size_t)pl[p].row0 * pl[p].src_row,
@@ -383,7 +363,7 @@ int uva_pix_window_device(int device, const void* d_in, int fmt, int src_h, int 
     if (pix_window_check(d_in, fmt, src_h, src_w, x, y, h, w, d_out)) return 1;
     if (((uintptr_t)d_out & 15) != 0) return fail("uva_pix_window_device: the result must start at a 16-byte aligned address");
     if (((uintptr_t)d_in & (uintptr_t)(crop_sample(fmt).bytes - 1)) != 0) return fail("uva_pix_window_device: odd address of a frame of 16-bit words");
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     WindowPlane pl[3];
@@ -399,10 +379,10 @@ int uva_pix_window_device(int device, const void* d_in, int fmt, int src_h, int 
 struct uva_deint {
     int device = 0, fmt = 0, h = 0, w = 0, flags = 0;
     size_t bytes = 0;
-    hipStream_t stream = nullptr;
-    uint8_t* d_frame[3] = {nullptr, nullptr, nullptr};     // frame k of the stream lies in d_frame[k % 3]
-    uint8_t* d_out[2] = {nullptr, nullptr};                // A, and B with UVA_DEINT_FIELD
     long long pushed = 0;                                  // frames since the last reset
+    DevPtr<uint8_t> d_frame[3];                            // frame k of the stream lies in d_frame[k % 3]
+    DevPtr<uint8_t> d_out[2];                              // A, and B with UVA_DEINT_FIELD
+    Stream stream;
 };
 
 namespace {
@@ -420,12 +400,12 @@ int deint_frames_host(int device, const void* prev, const void* cur, const void*
                       int max_groups)
 {
     if (deint_frames_check(cur, fmt, h, w, flags, out_a, out_b)) return 1;
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     const size_t bytes = deint_format(fmt, h, w).frame_bytes, slot = (bytes + 15) & ~(size_t)15;
     // prev, cur, next in d_in; A, B in d_out (every frame at a multiple of 16 bytes)
-    if (pix_grow(*c, &c->d_in, &c->in_cap, 3 * slot) || pix_grow(*c, &c->d_out, &c->out_cap, 2 * slot)) return 1;
+    if (pix_grow(*c, c->d_in, 3 * slot) || pix_grow(*c, c->d_out, 2 * slot)) return 1;
     const uint8_t *d_cur = c->d_in + slot, *d_prev = d_cur, *d_next = d_cur;
     HIP_TRY(hipMemcpyAsync(c->d_in + slot, cur, bytes, hipMemcpyHostToDevice, c->stream));
     if (prev && prev != cur) {
@@ -484,7 +464,7 @@ int uva_deint_frames_device(int device, const void* d_prev, const void* d_cur, c
     if (deint_frames_check(d_cur, fmt, h, w, flags, d_out_a, d_out_b)) return 1;
     if ((((uintptr_t)d_prev | (uintptr_t)d_cur | (uintptr_t)d_next | (uintptr_t)d_out_a | (uintptr_t)d_out_b) & 15) != 0)
         return fail("uva_deint_frames_device: the frames must start at 16-byte aligned addresses");
-    std::lock_guard<std::mutex> lk(g_pix_mu);
+    std::lock_guard<std::mutex> lk(g_pix.mu);
     PixCtx* c = nullptr;
     if (pix_ctx(device, &c)) return 1;
     HIP_TRY(launch_deint(c->stream, d_prev ? d_prev : d_cur, d_cur, d_next ? d_next : d_cur, fmt, h, w, flags, d_out_a, d_out_b, 0));
@@ -508,17 +488,14 @@ int uva_deint_create(int device, int fmt, int h, int w, int flags, uva_deint** o
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail("no HIP device available: libuva has no CPU path");
     if (device < 0 || device >= count) return fail("HIP device " + std::to_string(device) + " does not exist");
     HIP_TRY(hipSetDevice(device));
-    uva_deint* d = new uva_deint;
+    std::unique_ptr<uva_deint> d(new uva_deint);
     d->device = device; d->fmt = fmt; d->h = h; d->w = w; d->flags = flags;
     d->bytes = deint_format(fmt, h, w).frame_bytes;
-    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipMalloc((void**)&d->d_frame[k], d->bytes);
-    for (int k = 0; k < ((flags & DEINT_FIELD) ? 2 : 1) && e == hipSuccess; ++k) e = hipMalloc((void**)&d->d_out[k], d->bytes);
-    if (e != hipSuccess) {
-        uva_deint_destroy(d);
-        return fail(std::string("uva_deint_create: ") + hipGetErrorString(e));
-    }
-    *out = d;
+    hipError_t e = make_stream(d->stream);
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = alloc_into(d->d_frame[k], d->bytes);
+    for (int k = 0; k < ((flags & DEINT_FIELD) ? 2 : 1) && e == hipSuccess; ++k) e = alloc_into(d->d_out[k], d->bytes);
+    if (e != hipSuccess) return fail(std::string("uva_deint_create: ") + hipGetErrorString(e));     // (nothing is queued yet)
+    *out = d.release();
     return 0;
 }
 
@@ -556,9 +533,6 @@ void uva_deint_destroy(uva_deint* d)
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (d->stream) (void)hipStreamSynchronize(d->stream);
-    for (uint8_t* p : {d->d_frame[0], d->d_frame[1], d->d_frame[2], d->d_out[0], d->d_out[1]})
-        if (p) (void)hipFree(p);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
 

@@ -12,6 +12,7 @@
 
 #include "uva_devutil.hip.h"
 #include "uva_generic.h"
+#include "uva_own.h"
 #include "uva_sw.h"
 
 namespace uva {
@@ -233,55 +234,27 @@ inline void rdb_segments(const std::vector<int>& dims, int grid, std::vector<Rdb
 // ---------------------------------------------------------------------------------------------------
 struct GenericDevice {
     struct ConvDev {
-        half8* wpk = nullptr;
-        half8* wpk_lds = nullptr;     // g_conv3_lds's image (3x3 convolutions with <= 64 output channels)
-        half8* wpk_w = nullptr;       // g_conv3_sww's image (192 -> 64, 3x3: pack_generic_wino)
-        float* bias = nullptr;
+        DevPtr<half8> wpk;
+        DevPtr<half8> wpk_lds;        // g_conv3_lds's image (3x3 convolutions with <= 64 output channels)
+        DevPtr<half8> wpk_w;          // g_conv3_sww's image (192 -> 64, 3x3: pack_generic_wino)
+        DevPtr<float> bias;
         int cin_pad = 0, cout_pad = 0;
     };
     std::vector<ConvDev> convs;
-    std::vector<float*> prelu;
-    std::map<std::tuple<int, int, int>, std::vector<_Float16*>> pool;     // (h, w, channels) -> free zero-bordered arrays
+    std::vector<DevPtr<float>> prelu;
+    // the zero-bordered arrays: `arrays` owns every one of them, lent out (a GBuf) or not; pool lists the ones that are free
+    std::vector<DevPtr<_Float16>> arrays;
+    std::map<std::tuple<int, int, int>, std::vector<_Float16*>> pool;     // (h, w, channels) -> free arrays
     size_t pool_bytes = 0;
     // g_conv3_sw: the strip segments of an h x w plane, dealt out to `grid` workgroups (sw_segments)
-    struct SwPlan { GSwSeg* segs = nullptr; int* seg_begin = nullptr; int grid = 0; };
+    struct SwPlan { DevPtr<GSwSeg> segs; DevPtr<int> seg_begin; int grid = 0; };
     std::map<std::vector<int>, SwPlan> sw_plans;                          // (strip columns, h0, w0, h1, w1, ...)
-    struct RdbPlan { RdbSeg* segs = nullptr; int* seg_begin = nullptr; int grid = 0; };
+    struct RdbPlan { DevPtr<RdbSeg> segs; DevPtr<int> seg_begin; int grid = 0; };
     std::map<std::vector<int>, RdbPlan> rdb_plans;                        // (h0, w0, h1, w1, ...)
     std::vector<RdbMatch> rdbs;                                           // find_rdbs() of the loaded graph
-    unsigned long long* rdb_dbg = nullptr;                                // UVA_INSTRUMENT + UVA_RDB_STAMPS=1: rdb4_kernel's stamps
+    DevPtr<unsigned long long> rdb_dbg;                                   // UVA_INSTRUMENT + UVA_RDB_STAMPS=1: rdb4_kernel's stamps
 
     static int pad32(int c) { return (c + 31) / 32 * 32; }
-
-    void release()
-    {
-        for (auto& c : convs) {
-            if (c.wpk) (void)hipFree(c.wpk);
-            if (c.wpk_lds) (void)hipFree(c.wpk_lds);
-            if (c.wpk_w) (void)hipFree(c.wpk_w);
-            if (c.bias) (void)hipFree(c.bias);
-        }
-        convs.clear();
-        for (auto p : prelu)
-            if (p) (void)hipFree(p);
-        prelu.clear();
-        for (auto& kv : pool)
-            for (auto p : kv.second) (void)hipFree(p);
-        pool.clear();
-        pool_bytes = 0;
-        for (auto& kv : sw_plans) {
-            if (kv.second.segs) (void)hipFree(kv.second.segs);
-            if (kv.second.seg_begin) (void)hipFree(kv.second.seg_begin);
-        }
-        sw_plans.clear();
-        for (auto& kv : rdb_plans) {
-            if (kv.second.segs) (void)hipFree(kv.second.segs);
-            if (kv.second.seg_begin) (void)hipFree(kv.second.seg_begin);
-        }
-        rdb_plans.clear();
-        if (rdb_dbg) (void)hipFree(rdb_dbg);
-        rdb_dbg = nullptr;
-    }
 };
 
 }  // namespace uva

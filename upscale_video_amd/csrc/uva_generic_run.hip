@@ -31,8 +31,11 @@ int generic_acquire(uva_net* n, int h, int w, int c, GBuf* out)
         return 0;
     }
     const size_t bytes = out->elems() * 2;
-    HIP_TRY(hipMalloc((void**)&out->p, bytes));
-    HIP_TRY(hipMemsetAsync(out->p, 0, bytes, n->stream));    // border and padding channels stay zero for the array's life
+    DevPtr<_Float16> d;
+    HIP_TRY(alloc_into(d, bytes));
+    HIP_TRY(hipMemsetAsync(d.get(), 0, bytes, n->stream));    // border and padding channels stay zero for the array's life
+    out->p = d.get();
+    n->gd.arrays.push_back(std::move(d));
     n->gd.pool_bytes += bytes;
     return 0;
 }
@@ -288,11 +291,13 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
             if (!plan.segs) {
                 std::vector<RdbSeg> segs;
                 std::vector<int> sbeg;
-                plan.grid = generic_grid(n);
-                rdb_segments(dims, plan.grid, segs, sbeg);
-                if (upload(&plan.segs, segs.data(), segs.size() * sizeof(RdbSeg), n->stream)) return 1;
-                if (upload(&plan.seg_begin, sbeg.data(), sbeg.size() * sizeof(int), n->stream)) return 1;
+                GenericDevice::RdbPlan fresh;
+                fresh.grid = generic_grid(n);
+                rdb_segments(dims, fresh.grid, segs, sbeg);
+                if (upload(fresh.segs, segs.data(), segs.size() * sizeof(RdbSeg), n->stream)) return 1;
+                if (upload(fresh.seg_begin, sbeg.data(), sbeg.size() * sizeof(int), n->stream)) return 1;
                 HIP_TRY(hipStreamSynchronize(n->stream));
+                plan = std::move(fresh);
             }
             ra.w1 = cdev(m.c1).wpk; ra.w2 = cdev(m.c2).wpk; ra.w2s = cdev(m.c2s).wpk; ra.w3 = cdev(m.c3).wpk; ra.w4 = cdev(m.c4).wpk;
             ra.b1 = cdev(m.c1).bias; ra.b2 = cdev(m.c2).bias; ra.b3 = cdev(m.c3).bias; ra.b4 = cdev(m.c4).bias;
@@ -300,7 +305,7 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
             ra.segs = plan.segs; ra.seg_begin = plan.seg_begin; ra.sink = n->d_sink;
 #ifdef UVA_INSTRUMENT
             if (uva::debug_env("UVA_RDB_STAMPS")) {
-                if (!n->gd.rdb_dbg) HIP_TRY(hipMalloc((void**)&n->gd.rdb_dbg, 1024 * 16 * 8));
+                if (!n->gd.rdb_dbg) HIP_TRY(alloc_into(n->gd.rdb_dbg, 1024 * 16 * 8));
                 HIP_TRY(hipMemsetAsync(n->gd.rdb_dbg, 0, 1024 * 16 * 8, n->stream));
                 ra.dbg = n->gd.rdb_dbg;
             }
@@ -309,12 +314,12 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                 HIP_TRY(hipFuncSetAttribute((const void*)rdb4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                 n->attr_set[28] = true;
             }
-            EvPairScope evp(n, 1, n->prof);
-            HIP_TRY(evp.begin());
+            EvScope evp(n, 2, n->prof);
+            HIP_TRY(evp.record(0));
             hipLaunchKernelGGL(rdb4_kernel, dim3(plan.grid), dim3(256), rdb4_lds_bytes(), n->stream, ra);
             ++n->glaunch[28];
             HIP_TRY(hipGetLastError());
-            HIP_TRY(evp.end());
+            HIP_TRY(evp.last(1));
             for (PlaneState& ps : P) finish_layer(ps);
             continue;
         }
@@ -348,11 +353,13 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                 if (!plan.segs) {
                     std::vector<GSwSeg> segs;
                     std::vector<int> sbeg;
-                    plan.grid = generic_grid(n);
-                    sw_segments(std::vector<int>(dims.begin() + 1, dims.end()), cols, plan.grid, segs, sbeg);
-                    if (upload(&plan.segs, segs.data(), segs.size() * sizeof(GSwSeg), n->stream)) return 1;
-                    if (upload(&plan.seg_begin, sbeg.data(), sbeg.size() * sizeof(int), n->stream)) return 1;
+                    GenericDevice::SwPlan fresh;
+                    fresh.grid = generic_grid(n);
+                    sw_segments(std::vector<int>(dims.begin() + 1, dims.end()), cols, fresh.grid, segs, sbeg);
+                    if (upload(fresh.segs, segs.data(), segs.size() * sizeof(GSwSeg), n->stream)) return 1;
+                    if (upload(fresh.seg_begin, sbeg.data(), sbeg.size() * sizeof(int), n->stream)) return 1;
                     HIP_TRY(hipStreamSynchronize(n->stream));       // (the vectors go away)
+                    plan = std::move(fresh);
                 }
                 sa.wpk = cd.wpk; sa.bias = cd.bias; sa.out_coff = 0; sa.slope = gl.act_slope;
                 if (sum) { sa.ca = sum->coeffs[0]; sa.cb = sum->coeffs[1]; }
@@ -363,11 +370,11 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                         n->attr_set[slot] = true;
                     }
-                    EvPairScope evp(n, 2, n->prof && cd.cin_pad == 192);
-                    HIP_TRY(evp.begin());
+                    EvScope evp(n, 2, n->prof && cd.cin_pad == 192);
+                    HIP_TRY(evp.record(0));
                     hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), lds, n->stream, sa);
                     ++n->glaunch[slot];
-                    HIP_TRY(evp.end());
+                    HIP_TRY(evp.last(2));
                     return 0;
                 };
                 // 192 inputs: UVA_GENERIC_SK=1 takes g_conv3_sk (32x32x16 MFMAs, the k-loop split between wave pairs) instead of
@@ -379,11 +386,11 @@ int generic_run_planes(uva_net* n, bool f32, const std::vector<PlaneJob>& jobs)
                 static const bool wino_on = [] { const char* e = uva::debug_env("UVA_GENERIC_WINO"); return !e || std::atoi(e) != 0; }();
                 if ((variant == 0 || variant == 1 || variant == 4) && wino_on && !sk_on && cd.wpk_w) {
                     sa.wpk = cd.wpk_w;
-                    EvPairScope evp(n, 2, n->prof);
-                    HIP_TRY(evp.begin());
+                    EvScope evp(n, 2, n->prof);
+                    HIP_TRY(evp.record(0));
                     HIP_TRY(launch_conv3_sww(n->stream, plan.grid, sa, variant == 4 ? 0 : 2, variant == 1 ? 2 : 0));
                     ++n->glaunch[variant == 4 ? GL_SWW : variant == 0 ? GL_SWW_SUM : GL_SWW_SUM2];
-                    HIP_TRY(evp.end());
+                    HIP_TRY(evp.last(2));
                 }
                 else if (variant == 0 && sk_on) { if (launch_sw(g_conv3_sk<2, 0>, 32, sk_lds_bytes())) return 1; }
                 else if (variant == 1 && sk_on) { if (launch_sw(g_conv3_sk<2, 2>, 33, sk_lds_bytes())) return 1; }

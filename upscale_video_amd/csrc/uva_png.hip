@@ -16,45 +16,48 @@ using namespace uva;
 namespace {
 
 // ---- PNG encoding on the device (uva_png.hip.h) ---------------------------------------------------
-struct PngDev {
-    uint32_t* d_code = nullptr;
-    uint8_t* d_hdr = nullptr;
-    uint32_t* d_crcmul = nullptr;
-    uint32_t* d_code16 = nullptr;     // the 16-bit encoder's tables (png_tables16)
-    uint8_t* d_hdr16 = nullptr;
-    bool attr_set = false;
-    // the synchronous utility's own buffers
-    hipStream_t stream = nullptr;
-    uint8_t *d_frame = nullptr, *d_blocks = nullptr;
-    size_t d_frame_cap = 0, d_blocks_cap = 0;
+struct PngCodes {                  // the encoders' tables on one device, complete or absent (d_code says which)
+    DevPtr<uint32_t> d_code;
+    DevPtr<uint8_t> d_hdr;
+    DevPtr<uint32_t> d_crcmul;
+    DevPtr<uint32_t> d_code16;     // the 16-bit encoder's tables (png_tables16)
+    DevPtr<uint8_t> d_hdr16;
 };
-std::mutex g_png_mu;          // the table uploads
-std::mutex g_png_util_mu;     // uva_png_deflate_u8's stream and frame buffer (never taken inside g_png_mu, or the reverse)
-PngDev g_png[kMaxDevices];
+struct PngDev : PngCodes {
+    // the synchronous utility's own buffers
+    DevBuf<uint8_t> d_frame, d_blocks;
+    Stream stream;
+};
+// g_png.mu guards the table uploads, g_png_util_mu uva_png_deflate_u8's stream and frame buffer; one is never taken inside
+// the other, except by png_release_all: the utility's first
+std::mutex g_png_util_mu;
+DeviceTable<PngDev>& g_png = *new DeviceTable<PngDev>;
+
+template <typename T>
+int png_table(DevPtr<T>& d, const void* src, size_t bytes)
+{
+    HIP_TRY(alloc_into(d, bytes));
+    HIP_TRY(hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
 
 // the code tables of this device (uploaded on first use); the caller holds no lock
 int png_dev(int device, PngDev** out)
 {
     if (device < 0 || device >= kMaxDevices) return fail("bad device");
-    std::lock_guard<std::mutex> lk(g_png_mu);
-    PngDev& c = g_png[device];
+    std::lock_guard<std::mutex> lk(g_png.mu);
+    PngDev& c = g_png.at(device);
     if (!c.d_code) {
         const PngTables& T = png_tables();
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMalloc((void**)&c.d_code, sizeof T.code));
-        HIP_TRY(hipMalloc((void**)&c.d_hdr, sizeof T.hdr));
-        HIP_TRY(hipMemcpy(c.d_code, T.code, sizeof T.code, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.d_hdr, T.hdr, sizeof T.hdr, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void**)&c.d_crcmul, sizeof T.crcmul));
-        HIP_TRY(hipMemcpy(c.d_crcmul, T.crcmul, sizeof T.crcmul, hipMemcpyHostToDevice));
-        HIP_TRY(hipFuncSetAttribute((const void*)png_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, png_lds_bytes()));
         const PngTables16& T16 = png_tables16();
-        HIP_TRY(hipMalloc((void**)&c.d_code16, sizeof T16.code));
-        HIP_TRY(hipMalloc((void**)&c.d_hdr16, sizeof T16.hdr));
-        HIP_TRY(hipMemcpy(c.d_code16, T16.code, sizeof T16.code, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.d_hdr16, T16.hdr, sizeof T16.hdr, hipMemcpyHostToDevice));
+        HIP_TRY(hipSetDevice(device));
+        PngCodes t;
+        if (png_table(t.d_code, T.code, sizeof T.code) || png_table(t.d_hdr, T.hdr, sizeof T.hdr) ||
+            png_table(t.d_crcmul, T.crcmul, sizeof T.crcmul) || png_table(t.d_code16, T16.code, sizeof T16.code) ||
+            png_table(t.d_hdr16, T16.hdr, sizeof T16.hdr)) return 1;
+        HIP_TRY(hipFuncSetAttribute((const void*)png_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, png_lds_bytes()));
         HIP_TRY(hipFuncSetAttribute((const void*)png_deflate_kernel16, hipFuncAttributeMaxDynamicSharedMemorySize, png_lds_bytes()));
-        c.attr_set = true;
+        static_cast<PngCodes&>(c) = std::move(t);
     }
     *out = &c;
     return 0;
@@ -65,21 +68,8 @@ int png_dev(int device, PngDev** out)
 void uva::png_release_all()
 {
     std::lock_guard<std::mutex> lk2(g_png_util_mu);
-    std::lock_guard<std::mutex> lk(g_png_mu);
-    for (int d = 0; d < kMaxDevices; ++d) {
-        PngDev& c = g_png[d];
-        if (!c.d_code && !c.stream) continue;
-        (void)hipSetDevice(d);
-        if (c.stream) { (void)hipStreamSynchronize(c.stream); (void)hipStreamDestroy(c.stream); }
-        if (c.d_code) (void)hipFree(c.d_code);
-        if (c.d_hdr) (void)hipFree(c.d_hdr);
-        if (c.d_crcmul) (void)hipFree(c.d_crcmul);
-        if (c.d_code16) (void)hipFree(c.d_code16);
-        if (c.d_hdr16) (void)hipFree(c.d_hdr16);
-        if (c.d_frame) (void)hipFree(c.d_frame);
-        if (c.d_blocks) (void)hipFree(c.d_blocks);
-        c = PngDev();
-    }
+    std::lock_guard<std::mutex> lk(g_png.mu);
+    g_png.release_all();
 }
 
 // deflate the h x w u8 BGR frame at d_frame (HBM) into blocks at d_blocks (HBM, png_workspace_bytes(h, w)), on `stream`
@@ -171,10 +161,10 @@ int uva_png_deflate_u8(int device, const uint8_t* bgr, int h, int w, size_t stri
     if (png_dev(device, &c)) return 1;
     std::lock_guard<std::mutex> lk(g_png_util_mu);
     HIP_TRY(hipSetDevice(device));
-    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    if (!c->stream) HIP_TRY(make_stream(c->stream));
     const size_t row = (size_t)w * 3;
     if (png_ws_bytes < png_workspace_bytes(h, w)) return fail("PNG workspace too small");
-    if (grow_dev(&c->d_frame, &c->d_frame_cap, row * h) || grow_dev(&c->d_blocks, &c->d_blocks_cap, png_device_bytes(h, w))) return 1;
+    if (grow_dev(c->d_frame, row * h) || grow_dev(c->d_blocks, png_device_bytes(h, w))) return 1;
     HIP_TRY(hipMemcpy2DAsync(c->d_frame, row, bgr, stride, row, h, hipMemcpyHostToDevice, c->stream));
     if (png_launch(device, c->stream, c->d_frame, row, h, w, c->d_blocks) || png_pack_launch(c->stream, c->d_blocks, h, w)) return 1;
     if (png_download(c->stream, c->d_blocks, h, w, png_ws, 0)) return 1;
@@ -208,11 +198,11 @@ int uva_png_deflate_u16(int device, const uint16_t* bgr, int h, int w, size_t st
     if (png_dev(device, &c)) return 1;
     std::lock_guard<std::mutex> lk(g_png_util_mu);
     HIP_TRY(hipSetDevice(device));
-    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    if (!c->stream) HIP_TRY(make_stream(c->stream));
     // (rows a multiple of 4 bytes apart on the device: the kernel then stages every width with dword loads)
     const size_t row = (size_t)w * 6, pitch = (row + 3) & ~(size_t)3;
     if (png_ws_bytes < png_workspace_bytes(h, w, 16)) return fail("PNG workspace too small");
-    if (grow_dev(&c->d_frame, &c->d_frame_cap, pitch * h) || grow_dev(&c->d_blocks, &c->d_blocks_cap, png_device_bytes(h, w, 16))) return 1;
+    if (grow_dev(c->d_frame, pitch * h) || grow_dev(c->d_blocks, png_device_bytes(h, w, 16))) return 1;
     HIP_TRY(hipMemcpy2DAsync(c->d_frame, pitch, bgr, stride, row, h, hipMemcpyHostToDevice, c->stream));
     if (png_launch16(device, c->stream, c->d_frame, pitch, h, w, c->d_blocks) || png_pack_launch(c->stream, c->d_blocks, h, w, 16)) return 1;
     if (png_download(c->stream, c->d_blocks, h, w, png_ws, 0, 16)) return 1;

@@ -19,6 +19,7 @@
 // in flight together (pass 1 is instantiated per tap-count class like pass 2, picked by a uniform switch).  Pass 2: thread t owns column-channel t of the
 // tile (64 pixels x 3), keeps its taps and LDS offsets in registers (the kernel is instantiated per tap-count class, shorter
 // rows padded with zero taps) and walks the 16 rows; neighbouring lanes read LDS words 1 (within a pixel) or 3 n apart.
+#include "uva_own.h"
 #include "uva_resize.h"
 
 #include <algorithm>
@@ -224,11 +225,12 @@ int tap_class(int t)
 struct Table {
     int device, n_in, n_out, filter, t, pitch;
     std::vector<int32_t> first;      // host copy: the launch sizes the LDS rows from it
-    int32_t* d_first;
-    int16_t* d_taps;                 // [n_out][pitch]
+    DevPtr<int32_t> d_first;
+    DevPtr<int16_t> d_taps;          // [n_out][pitch]
 };
 std::mutex g_rs_mu;
-std::list<Table> g_tables;      // (a list: entries stay where they are while others are added)
+// (a list: entries stay where they are while others are added; never destroyed: no HIP call at process exit)
+std::list<Table>& g_tables = *new std::list<Table>;
 constexpr size_t RS_MAX_TABLES = 64;
 
 void free_tables(int device)          // (g_rs_mu held; device < 0: all)
@@ -236,8 +238,6 @@ void free_tables(int device)          // (g_rs_mu held; device < 0: all)
     for (auto it = g_tables.begin(); it != g_tables.end();) {
         if (device >= 0 && it->device != device) { ++it; continue; }
         (void)hipSetDevice(it->device);
-        (void)hipFree(it->d_first);
-        (void)hipFree(it->d_taps);
         it = g_tables.erase(it);
     }
 }
@@ -246,7 +246,7 @@ const Table* get_table(int device, int n_in, int n_out, int filter, std::string*
 {
     for (const Table& t : g_tables)
         if (t.device == device && t.n_in == n_in && t.n_out == n_out && t.filter == filter) return &t;
-    Table t{device, n_in, n_out, filter, 0, 0, {}, nullptr, nullptr};
+    Table t{device, n_in, n_out, filter, 0, 0, {}, {}, {}};
     std::vector<int16_t> taps;
     t.t = resize_build_taps(n_in, n_out, filter, t.first, taps);
     if (!t.t) { *err = "resize: bad axis"; return nullptr; }
@@ -254,14 +254,12 @@ const Table* get_table(int device, int n_in, int n_out, int filter, std::string*
     std::vector<int16_t> padded((size_t)n_out * t.pitch, 0);
     for (int d = 0; d < n_out; ++d) std::copy(taps.begin() + (size_t)d * t.t, taps.begin() + (size_t)(d + 1) * t.t, padded.begin() + (size_t)d * t.pitch);
     // synchronous copies: the table may be used from any stream as soon as this returns
-    hipError_t e = hipMalloc((void**)&t.d_first, (size_t)n_out * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&t.d_taps, padded.size() * 2);
+    hipError_t e = alloc_into(t.d_first, (size_t)n_out * 4);
+    if (e == hipSuccess) e = alloc_into(t.d_taps, padded.size() * 2);
     if (e == hipSuccess) e = hipMemcpy(t.d_first, t.first.data(), (size_t)n_out * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(t.d_taps, padded.data(), padded.size() * 2, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         *err = std::string("resize tables: ") + hipGetErrorString(e);
-        if (t.d_first) (void)hipFree(t.d_first);
-        if (t.d_taps) (void)hipFree(t.d_taps);
         return nullptr;
     }
     g_tables.push_back(std::move(t));

@@ -1,12 +1,16 @@
 // uva_rt.h -- what every translation unit with C ABI entries shares on the host: the error channel behind uva_last_error, the
-// HIP call wrappers, the growing buffers, the per-device tables' size and the one device check, and the fences that order a
+// HIP call wrappers, the makers of the handles of csrc/uva_own.h, the per-device tables and the one device check, and the fences that order a
 // stateless stage's stream between two nets.  No device code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <mutex>
 #include <string>
+#include <utility>
+
+#include "uva_own.h"
 
 struct uva_net;
 
@@ -24,34 +28,21 @@ inline int tryhip(hipError_t e, const char* what) { return e == hipSuccess ? 0 :
             return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                    \
     } while (0)
 
+// fills a handle: the buffer is made in a local and moved in once the copy is queued
 template <typename T>
-int upload(T** dst, const void* src, size_t bytes, hipStream_t st)
+int upload(DevPtr<T>& dst, const void* src, size_t bytes, hipStream_t st)
 {
-    HIP_TRY(hipMalloc((void**)dst, bytes));
-    HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st));
+    DevPtr<T> d;
+    HIP_TRY(alloc_into(d, bytes));
+    HIP_TRY(hipMemcpyAsync(d.get(), src, bytes, hipMemcpyHostToDevice, st));
+    dst = std::move(d);
     return 0;
 }
 
 template <typename T>
-int grow_dev(T** p, size_t* cap, size_t bytes)
-{
-    if (*cap >= bytes) return 0;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc((void**)p, bytes));
-    *cap = bytes;
-    return 0;
-}
-
-inline int grow_host(uint8_t** p, size_t* cap, size_t bytes)
-{
-    if (*cap >= bytes) return 0;
-    if (*p) HIP_TRY(hipHostFree(*p));
-    *p = nullptr; *cap = 0;
-    HIP_TRY(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
-    *cap = bytes;
-    return 0;
-}
+int grow_dev(DevBuf<T>& b, size_t bytes) { return tryhip((hipError_t)b.grow(bytes), "hipMalloc"); }
+template <typename T>
+int grow_host(HostBuf<T>& b, size_t bytes) { return tryhip((hipError_t)b.grow(bytes), "hipHostMalloc"); }
 
 inline bool is_pinned_host(const void* p)
 {
@@ -68,6 +59,38 @@ constexpr int kMaxDevices = 16;
 
 // makes `device` current for a stateless stage, or says why not: no device at all, or none of that index (in the tables)
 int select_device(int device);
+
+// The per-device contexts of a stateless stage.  Ctx holds handles and a `Stream stream`; the table itself lives in storage
+// that is never destroyed (`*new DeviceTable<Ctx>`: no HIP call at process exit).  The caller holds `mu` around every call.
+template <typename Ctx>
+struct DeviceTable {
+    std::mutex mu;
+    Ctx ctx[kMaxDevices];
+    bool used[kMaxDevices] = {};
+    Ctx& at(int device) { used[device] = true; return ctx[device]; }
+    // makes `device` current and its context's stream exist
+    int enter(int device, Ctx** out)
+    {
+        if (select_device(device)) return 1;
+        Ctx& c = at(device);
+        if (!c.stream) HIP_TRY(make_stream(c.stream));
+        *out = &c;
+        return 0;
+    }
+    // every used context: its device current, stream_of(device) -- where there is one -- waited for, the context reset
+    template <typename S>
+    void release_all(S stream_of)
+    {
+        for (int d = 0; d < kMaxDevices; ++d) {
+            if (!used[d]) continue;
+            (void)hipSetDevice(d);
+            if (hipStream_t s = stream_of(d)) (void)hipStreamSynchronize(s);
+            ctx[d] = Ctx();
+            used[d] = false;
+        }
+    }
+    void release_all() { release_all([this](int d) { return ctx[d].stream.get(); }); }
+};
 
 // the stages' teardown, every context of every device: uva_destroy_gpu_instance calls them in this order, after the nets
 // and before resize_release_all (csrc/uva_resize.h)
