@@ -62,6 +62,9 @@ extern "C" {
                                15 + deinterlacing: + uva_deint_check, uva_deint_frames, uva_deint_frames_device, uva_debug_deint_frames,
                                    uva_debug_deint_host, uva_deint_create, uva_deint_push, uva_deint_reset, uva_deint_destroy,
                                    UVA_DEINT_* (additive: nothing runs unless asked for)
+                               15 + inverse telecine: + uva_ivtc_check, uva_ivtc_metrics, uva_ivtc_metrics_device, uva_debug_ivtc_metrics,
+                                   uva_debug_ivtc_host, uva_debug_ivtc_decimate, uva_ivtc_create, uva_ivtc_push, uva_ivtc_reset,
+                                   uva_ivtc_stats, uva_ivtc_destroy, UVA_IVTC_* (additive: nothing runs unless asked for)
                                15 + live resources: + uva_debug_live_resources (additive: a test hook) */
 
 typedef struct uva_net uva_net;
@@ -84,7 +87,7 @@ int uva_get_gpu_pci_bus_id(int index, char* out, size_t out_len);
 void uva_destroy_gpu_instance(void);
 /* Test hook: the HIP resources the library holds at this moment -- counts[0] device buffers, [1] page-locked host buffers,
  * [2] streams, [3] events.  Memory from uva_host_alloc belongs to the caller and is not counted.  All four are zero before
- * the first call that uses a GPU, and again once every uva_deint and every net is destroyed and uva_destroy_gpu_instance
+ * the first call that uses a GPU, and again once every uva_deint, every uva_ivtc and every net is destroyed and uva_destroy_gpu_instance
  * has run. */
 void uva_debug_live_resources(long long counts[4]);
 
@@ -382,6 +385,59 @@ int uva_deint_create(int device, int fmt, int h, int w, int flags, uva_deint** o
 int uva_deint_push(uva_deint* d, const void* frame, void* out_a, void* out_b, int* produced);
 int uva_deint_reset(uva_deint* d);
 void uva_deint_destroy(uva_deint* d);
+
+/* ---- inverse telecine (csrc/uva_ivtc.hip, csrc/uva_ivtc_host.cpp) ---------------------------------
+ * NTSC film and anime DVDs are 24000/1001 film carried as 30000/1001 interlaced video by 2:3 pulldown: of five frames two mix
+ * the fields of two film frames and one repeats nothing new.  These entries give the film frames back: field matching, then
+ * decimation (the rule's definition for this project: tests/ivtc_ref.py; parity with ffmpeg's fieldmatch / decimate filters is
+ * unpinned).  Formats, planes, samples, the first field and NULL neighbours are those of the deinterlacing entries above.
+ * For a frame `cur` between `prev` and `next` the candidates c / p / n weave cur's first field (even rows unless UVA_IVTC_BFF)
+ * with the other rows of cur / prev / next, in every plane, byte for byte.  On plane 0 of a candidate (luma, or all of a packed
+ * BGR frame), for rows 1 ... ph - 2, a sample b between its vertical neighbours a and c is combed when b - a and b - c have the
+ * same sign, are non-zero and m = min(|b - a|, |b - c|) > T << (depth - 8); N counts them, M sums m.  stats is
+ * (N_c, M_c, N_p, M_p, N_n, M_n), exact.  The match is the candidate of the smallest M (ties: c, p, n); it is combed when
+ * N * 10^6 > L * (ph - 2) * (samples of a row), and then replaced by yadif's output A of the same three frames unless
+ * UVA_IVTC_KEEP_COMBED.  The frames so made are grouped in fives from the start of the stream; of a full five the one with the
+ * smallest sum of absolute differences to the frame before it (the first of a stream: 2^64 - 1) is dropped, ties the earliest,
+ * unless UVA_IVTC_KEEP_ALL.  T is on the 8-bit scale, 0 ... 255 (9 is the route's default); L is parts per million, 0 ... 10^6
+ * (1000 is the route's default, a guess: no telecined real material was at hand). */
+#define UVA_IVTC_BFF 1
+#define UVA_IVTC_KEEP_COMBED 2
+#define UVA_IVTC_KEEP_ALL 4
+typedef struct uva_ivtc uva_ivtc;
+/* Host only, no GPU needed.  Refused, never rounded, with uva_last_error set: what uva_deint_check refuses, T or L out of range,
+ * unknown flag bits.  Any w >= 1 is taken. */
+int uva_ivtc_check(int fmt, int h, int w, int flags, int T, int L);
+/* One frame, stateless: stats[6] <- the six sums on HIP device `device`.  Host frames, synchronous.  prev / next NULL mean cur.
+ * Everything is refused before a GPU is looked for. */
+int uva_ivtc_metrics(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T,
+                     unsigned long long* stats);
+/* The same for frames in `device`'s HBM, complete and at 16-byte aligned addresses (stats is host memory).  Synchronous. */
+int uva_ivtc_metrics_device(int device, const void* d_prev, const void* d_cur, const void* d_next, int fmt, int h, int w, int flags, int T,
+                            unsigned long long* stats);
+/* Test hook: uva_ivtc_metrics on a grid of at most max_groups workgroups (0: the kernel's own bound). */
+int uva_debug_ivtc_metrics(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T,
+                           unsigned long long* stats, int max_groups);
+/* Test hook, host only, no GPU needed: the scalar restatement in csrc/uva_ivtc_host.cpp.  stats[6] as above; woven (may be NULL)
+ * <- the three candidates c, p, n, a frame each; chosen (may be NULL) <- the frame the rule makes of cur; decision (may be NULL)
+ * <- {match 0 / 1 / 2, combed 0 / 1}. */
+int uva_debug_ivtc_host(const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T, int L,
+                        unsigned long long* stats, void* woven, void* chosen, int* decision);
+/* Test hook, host only: the decimator driven as uva_ivtc_push drives it over n frames with these diffs, then flushed:
+ * delivered[*n_delivered] (room for n) <- the numbers of the frames that leave, in order.  flags: UVA_IVTC_KEEP_ALL counts. */
+int uva_debug_ivtc_decimate(const unsigned long long* diffs, int n, int flags, long long* delivered, int* n_delivered);
+/* A stream, stateful, so that every frame is uploaded once: the handle keeps three source frames, a ring of the frames it has
+ * made, its sums and a stream of its own in `device`'s HBM.  uva_ivtc_push uploads `frame` and hands out at most one frame of the
+ * result: *produced is 0 or 1, and with 1 the frame is in `out` when the call returns.  frame NULL is a flush step: call it until
+ * it produces 0, after which the handle is as after uva_ivtc_reset, ready for another stream; a frame pushed in between is
+ * refused.  Which call delivers which frame is the implementation's business (a five is decided when it is complete); the
+ * sequence of delivered frames is the rule's: n frames in, n - n / 5 out. */
+int uva_ivtc_create(int device, int fmt, int h, int w, int flags, int T, int L, uva_ivtc** out);
+int uva_ivtc_push(uva_ivtc* d, const void* frame, void* out, int* produced);
+int uva_ivtc_reset(uva_ivtc* d);
+/* stats[7] <- since creation: frames in, frames out, matches c, p, n, frames found combed, frames dropped.  Host only. */
+int uva_ivtc_stats(uva_ivtc* d, unsigned long long* stats);
+void uva_ivtc_destroy(uva_ivtc* d);
 
 /* ---- the imwrite side on the device (csrc/uva_png.hip.h) -------------------------------- */
 

@@ -45,6 +45,9 @@ OPTIONAL_SYMBOLS += ["uva_crop_sums", "uva_crop_sums_device", "uva_debug_crop_su
 # 15 + deinterlacing (additive and optional in the same way: ncnn.deint_frames, ncnn.Deinterlacer and rawvideo's --deinterlace ask)
 OPTIONAL_SYMBOLS += ["uva_deint_check", "uva_deint_frames", "uva_deint_frames_device", "uva_debug_deint_frames", "uva_debug_deint_host",
                      "uva_deint_create", "uva_deint_push", "uva_deint_reset", "uva_deint_destroy"]
+# 15 + inverse telecine (additive and optional in the same way: ncnn.ivtc_metrics, ncnn.Detelecine and rawvideo's --detelecine ask)
+OPTIONAL_SYMBOLS += ["uva_ivtc_check", "uva_ivtc_metrics", "uva_ivtc_metrics_device", "uva_debug_ivtc_metrics", "uva_debug_ivtc_host",
+                     "uva_debug_ivtc_decimate", "uva_ivtc_create", "uva_ivtc_push", "uva_ivtc_reset", "uva_ivtc_stats", "uva_ivtc_destroy"]
 # 15 + live resources (additive and optional in the same way: a test hook, tests/test_gpu_live_resources.py asks)
 OPTIONAL_SYMBOLS += ["uva_debug_live_resources"]
 SYMBOLS += OPTIONAL_SYMBOLS
@@ -143,6 +146,17 @@ def load():
     decl("uva_deint_push", [c_p, c_p, c_p, c_p, pi])
     decl("uva_deint_reset", [c_p])
     decl("uva_deint_destroy", [c_p], "void")
+    decl("uva_ivtc_check", [c_i, c_i, c_i, c_i, c_i, c_i])
+    decl("uva_ivtc_metrics", [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p])
+    decl("uva_ivtc_metrics_device", [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p])
+    decl("uva_debug_ivtc_metrics", [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i])
+    decl("uva_debug_ivtc_host", [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, pi])
+    decl("uva_debug_ivtc_decimate", [c_p, c_i, c_i, pll, pi])
+    decl("uva_ivtc_create", [c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_p)])
+    decl("uva_ivtc_push", [c_p, c_p, c_p, pi])
+    decl("uva_ivtc_reset", [c_p])
+    decl("uva_ivtc_stats", [c_p, c_p])
+    decl("uva_ivtc_destroy", [c_p], "void")
     decl("uva_get_gpu_count", [])
     decl("uva_get_default_gpu_index", [])
     decl("uva_get_gpu_info", [c_i, pi, ctypes.c_char_p, c_sz])

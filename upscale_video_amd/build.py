@@ -20,7 +20,7 @@ SOURCES = {
                             "uva_model.h", "uva_pixfmt.h", "uva_plan.h", "uva_repeat.h", "uva_crop.h", "uva_submit.h", _UVA_H],
     "uva_denoise.hip": ["uva_denoise.hip.h", "uva_denoise16.hip.h", "uva_denoise16_tables.h", "uva_rt.h", "uva_own.h", _UVA_H],
     "uva_png.hip": ["uva_png.hip.h", "uva_png.h", "uva_pngread.h", "uva_rt.h", "uva_own.h", _UVA_H],
-    "uva_frames.hip": ["uva_pixfmt.h", "uva_resize.h", "uva_repeat.h", "uva_crop.h", "uva_deint.h", "uva_rt.h", "uva_own.h", _UVA_H],
+    "uva_frames.hip": ["uva_pixfmt.h", "uva_resize.h", "uva_repeat.h", "uva_crop.h", "uva_deint.h", "uva_ivtc.h", "uva_rt.h", "uva_own.h", _UVA_H],
     "uva_wino.hip": ["uva_wino.hip.h", "uva_wino.h", "uva_devutil.hip.h", "uva_plan.h"],
     "uva_sub5.hip": ["uva_sub5.hip.h", "uva_sub5.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
     "uva_sub10.hip": ["uva_sub10.hip.h", "uva_sub10_body.hip.h", "uva_sub10.h", "uva_devutil.hip.h", "uva_model.h", "uva_plan.h"],
@@ -32,6 +32,8 @@ SOURCES = {
     "uva_crop_host.cpp": ["uva_crop.h"],
     "uva_deint.hip": ["uva_deint.h", "uva_pixfmt.h"],
     "uva_deint_host.cpp": ["uva_deint.h"],
+    "uva_ivtc.hip": ["uva_ivtc.h", "uva_deint.h", "uva_pixfmt.h"],
+    "uva_ivtc_host.cpp": ["uva_ivtc.h", "uva_deint.h"],
     "uva_plan.cpp": ["uva_plan.h"],
     "uva_submit.cpp": ["uva_submit.h", "uva_crop.h", "uva_pixfmt.h"],
     "uva_model.cpp": ["uva_model.h"],

@@ -1,9 +1,10 @@
 // uva_frames.hip -- the stateless frame stages of the raw-video route outside a net: pixel formats, the resampler, repeated
-// frames, crop detection, the input window and deinterlacing.  Host code only: it calls the launchers of csrc/uva_pixfmt.hip,
-// csrc/uva_resize.hip, csrc/uva_repeat.hip, csrc/uva_crop.hip and csrc/uva_deint.hip on a per-device stream of its own.
+// frames, crop detection, the input window, deinterlacing and inverse telecine.  Host code only: it calls the launchers of csrc/uva_pixfmt.hip,
+// csrc/uva_resize.hip, csrc/uva_repeat.hip, csrc/uva_crop.hip, csrc/uva_deint.hip and csrc/uva_ivtc.hip on a per-device stream of its own.
 #include "../../include/uva.h"
 #include "uva_crop.h"
 #include "uva_deint.h"
+#include "uva_ivtc.h"
 #include "uva_pixfmt.h"
 #include "uva_repeat.h"
 #include "uva_resize.h"
@@ -529,6 +530,268 @@ int uva_deint_reset(uva_deint* d)
 }
 
 void uva_deint_destroy(uva_deint* d)
+{
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    delete d;
+}
+
+// ---- inverse telecine (csrc/uva_ivtc.hip, csrc/uva_ivtc_host.cpp) ------------------------------------
+struct uva_ivtc {
+    static constexpr int RING = 10;                        // two cycles: a cycle is delivered while the next one is built
+    int device = 0, fmt = 0, h = 0, w = 0, flags = 0, T = 0, L = 0;
+    size_t bytes = 0;
+    long long pushed = 0;                                  // source frames since the last reset
+    long long finals = 0;                                  // final frames built since the last reset
+    bool ended = false;                                    // a flush has closed the stream
+    IvtcDecimator dec;
+    unsigned long long counts[7] = {};                     // uva_ivtc_stats
+    DevPtr<uint8_t> d_frame[3];                            // source frame k lies in d_frame[k % 3]
+    DevPtr<uint8_t> d_final[RING];                         // final frame j lies in d_final[j % RING]
+    DevPtr<unsigned long long> d_stats;                    // the six sums, then a FrameDiffStats
+    Stream stream;
+};
+
+namespace {
+constexpr size_t IVTC_STATS_BYTES = 6 * sizeof(unsigned long long) + sizeof(FrameDiffStats);
+
+int ivtc_metrics_check(const void* cur, int fmt, int h, int w, int flags, int T, const unsigned long long* stats)
+{
+    if (const char* e = ivtc_error(fmt, h, w, flags, T, 0)) return fail(e);
+    if (!cur || !stats) return fail("null frame pointer");
+    return 0;
+}
+
+int ivtc_metrics_up(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T,
+                    unsigned long long* stats, int max_groups)
+{
+    if (ivtc_metrics_check(cur, fmt, h, w, flags, T, stats)) return 1;
+    std::lock_guard<std::mutex> lk(g_pix.mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    const size_t bytes = deint_format(fmt, h, w).frame_bytes, slot = (bytes + 15) & ~(size_t)15;
+    // prev, cur, next in d_in (every frame at a multiple of 16 bytes); the sums in d_sums
+    if (pix_grow(*c, c->d_in, 3 * slot)) return 1;
+    if (c->d_sums.cap() < 6 * sizeof(unsigned long long)) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (grow_dev(c->d_sums, 6 * sizeof(unsigned long long))) return 1;
+    }
+    const uint8_t *d_cur = c->d_in + slot, *d_prev = d_cur, *d_next = d_cur;
+    HIP_TRY(hipMemcpyAsync(c->d_in + slot, cur, bytes, hipMemcpyHostToDevice, c->stream));
+    if (prev && prev != cur) {
+        HIP_TRY(hipMemcpyAsync(c->d_in, prev, bytes, hipMemcpyHostToDevice, c->stream));
+        d_prev = c->d_in;
+    }
+    if (next && next != cur) {
+        HIP_TRY(hipMemcpyAsync(c->d_in + 2 * slot, next, bytes, hipMemcpyHostToDevice, c->stream));
+        d_next = c->d_in + 2 * slot;
+    }
+    HIP_TRY(launch_ivtc_metrics(c->stream, d_prev, d_cur, d_next, fmt, h, w, flags, T, c->d_sums, max_groups));
+    HIP_TRY(hipMemcpyAsync(stats, c->d_sums, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+void ivtc_clear(uva_ivtc* d)
+{
+    d->pushed = d->finals = 0;
+    d->ended = false;
+    d->dec.reset((d->flags & IVTC_KEEP_ALL) != 0);
+}
+
+// final frame k of the handle's stream (prev / next: source frames k -+ 1, or k itself at an end) into its ring slot, its diff
+// to the decimator; waited for
+int ivtc_finalize(uva_ivtc* d, long long k, bool has_next)
+{
+    const uint8_t* cur = d->d_frame[k % 3];
+    const uint8_t* prev = k > 0 ? d->d_frame[(k - 1) % 3] : cur;
+    const uint8_t* next = has_next ? d->d_frame[(k + 1) % 3] : cur;
+    unsigned long long st[6];
+    HIP_TRY(launch_ivtc_metrics(d->stream, prev, cur, next, d->fmt, d->h, d->w, d->flags, d->T, d->d_stats, 0));
+    HIP_TRY(hipMemcpyAsync(st, d->d_stats, sizeof st, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    const DeintFormat f = deint_format(d->fmt, d->h, d->w);
+    int rows = 0, match = IVTC_C;
+    long long samples = 0;
+    ivtc_metric_extent(f, &rows, &samples);
+    const bool combed = ivtc_choose(st, rows, samples, d->L, &match);
+    uint8_t* dst = d->d_final[k % uva_ivtc::RING];
+    if (combed && !(d->flags & IVTC_KEEP_COMBED))
+        HIP_TRY(launch_deint(d->stream, prev, cur, next, d->fmt, d->h, d->w, ivtc_deint_flags(d->flags), dst, nullptr, 0));
+    else
+        HIP_TRY(launch_ivtc_weave(d->stream, cur, match == IVTC_P ? prev : (match == IVTC_N ? next : cur), d->fmt, d->h, d->w, d->flags, dst));
+    unsigned long long diff = IVTC_FIRST_DIFF;
+    if (k > 0 && !(d->flags & IVTC_KEEP_ALL)) {
+        FrameDiffStats fd;
+        FrameDiffStats* d_fd = (FrameDiffStats*)(d->d_stats.get() + 6);
+        HIP_TRY(launch_frame_diff(d->stream, dst, d->d_final[(k - 1) % uva_ivtc::RING], d->bytes, d->fmt, 0, d_fd));
+        HIP_TRY(hipMemcpyAsync(&fd, d_fd, sizeof fd, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        diff = fd.sad;
+    }
+    d->dec.add(diff);
+    d->finals = k + 1;
+    ++d->counts[2 + match];
+    if (combed) ++d->counts[5];
+    return 0;
+}
+}  // namespace
+
+int uva_ivtc_check(int fmt, int h, int w, int flags, int T, int L)
+{
+    if (const char* e = ivtc_error(fmt, h, w, flags, T, L)) return fail(e);
+    return 0;
+}
+
+int uva_ivtc_metrics(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T,
+                     unsigned long long* stats)
+{
+    return ivtc_metrics_up(device, prev, cur, next, fmt, h, w, flags, T, stats, 0);
+}
+
+int uva_debug_ivtc_metrics(int device, const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T,
+                           unsigned long long* stats, int max_groups)
+{
+    if (max_groups < 0) return fail("uva_debug_ivtc_metrics: max_groups is 0 (the kernel's own bound) or a number of workgroups");
+    return ivtc_metrics_up(device, prev, cur, next, fmt, h, w, flags, T, stats, max_groups);
+}
+
+int uva_ivtc_metrics_device(int device, const void* d_prev, const void* d_cur, const void* d_next, int fmt, int h, int w, int flags, int T,
+                            unsigned long long* stats)
+{
+    if (ivtc_metrics_check(d_cur, fmt, h, w, flags, T, stats)) return 1;
+    if ((((uintptr_t)d_prev | (uintptr_t)d_cur | (uintptr_t)d_next) & 15) != 0)
+        return fail("uva_ivtc_metrics_device: the frames must start at 16-byte aligned addresses");
+    std::lock_guard<std::mutex> lk(g_pix.mu);
+    PixCtx* c = nullptr;
+    if (pix_ctx(device, &c)) return 1;
+    if (c->d_sums.cap() < 6 * sizeof(unsigned long long)) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (grow_dev(c->d_sums, 6 * sizeof(unsigned long long))) return 1;
+    }
+    HIP_TRY(launch_ivtc_metrics(c->stream, d_prev ? d_prev : d_cur, d_cur, d_next ? d_next : d_cur, fmt, h, w, flags, T, c->d_sums, 0));
+    HIP_TRY(hipMemcpyAsync(stats, c->d_sums, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int uva_debug_ivtc_host(const void* prev, const void* cur, const void* next, int fmt, int h, int w, int flags, int T, int L,
+                        unsigned long long* stats, void* woven, void* chosen, int* decision)
+{
+    if (const char* e = ivtc_error(fmt, h, w, flags, T, L)) return fail(e);
+    if (!cur || !stats) return fail("null frame pointer");
+    const uint8_t *c = (const uint8_t*)cur, *x[3] = {c, prev ? (const uint8_t*)prev : c, next ? (const uint8_t*)next : c};
+    ivtc_metrics_host(x[1], c, x[2], fmt, h, w, flags, T, stats);
+    const DeintFormat f = deint_format(fmt, h, w);
+    if (woven)
+        for (int k = 0; k < 3; ++k) ivtc_weave_host(c, x[k], fmt, h, w, flags, (uint8_t*)woven + (size_t)k * f.frame_bytes);
+    int rows = 0, match = IVTC_C;
+    long long samples = 0;
+    ivtc_metric_extent(f, &rows, &samples);
+    const bool combed = ivtc_choose(stats, rows, samples, L, &match);
+    if (decision) {
+        decision[0] = match;
+        decision[1] = combed ? 1 : 0;
+    }
+    if (chosen) {
+        if (combed && !(flags & IVTC_KEEP_COMBED)) deint_host(x[1], c, x[2], fmt, h, w, ivtc_deint_flags(flags), (uint8_t*)chosen, nullptr);
+        else ivtc_weave_host(c, x[match], fmt, h, w, flags, (uint8_t*)chosen);
+    }
+    return 0;
+}
+
+int uva_debug_ivtc_decimate(const unsigned long long* diffs, int n, int flags, long long* delivered, int* n_delivered)
+{
+    if (!diffs || !delivered || !n_delivered || n < 0) return fail("uva_debug_ivtc_decimate: null pointer");
+    if (flags & ~IVTC_FLAGS) return fail(ivtc_error(0, 4, 1, flags, 0, 0));
+    // as uva_ivtc_push drives it: one frame in, at most one out, then the flush steps
+    IvtcDecimator dec;
+    dec.reset((flags & IVTC_KEEP_ALL) != 0);
+    int out = 0;
+    long long j = 0;
+    for (int k = 0; k < n; ++k) {
+        dec.add(diffs[k]);
+        if (dec.pop(&j)) delivered[out++] = j;
+    }
+    dec.end();
+    while (dec.pop(&j)) delivered[out++] = j;
+    *n_delivered = out;
+    return 0;
+}
+
+int uva_ivtc_create(int device, int fmt, int h, int w, int flags, int T, int L, uva_ivtc** out)
+{
+    if (!out) return fail("uva_ivtc_create: null pointer");
+    *out = nullptr;
+    if (const char* e = ivtc_error(fmt, h, w, flags, T, L)) return fail(e);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail("no HIP device available: libuva has no CPU path");
+    if (device < 0 || device >= count) return fail("HIP device " + std::to_string(device) + " does not exist");
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<uva_ivtc> d(new uva_ivtc);
+    d->device = device; d->fmt = fmt; d->h = h; d->w = w; d->flags = flags; d->T = T; d->L = L;
+    d->bytes = deint_format(fmt, h, w).frame_bytes;
+    ivtc_clear(d.get());
+    hipError_t e = make_stream(d->stream);
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = alloc_into(d->d_frame[k], d->bytes);
+    for (int k = 0; k < uva_ivtc::RING && e == hipSuccess; ++k) e = alloc_into(d->d_final[k], d->bytes);
+    if (e == hipSuccess) e = alloc_into(d->d_stats, IVTC_STATS_BYTES);
+    if (e != hipSuccess) return fail(std::string("uva_ivtc_create: ") + hipGetErrorString(e));      // (nothing is queued yet)
+    *out = d.release();
+    return 0;
+}
+
+int uva_ivtc_push(uva_ivtc* d, const void* frame, void* out, int* produced)
+{
+    if (!d || !produced) return fail("uva_ivtc_push: null pointer");
+    *produced = 0;
+    if (!out) return fail("uva_ivtc_push: null output frame");
+    HIP_TRY(hipSetDevice(d->device));
+    if (frame) {
+        if (d->ended) return fail("uva_ivtc_push: the stream is being flushed: call with frame NULL until it produces 0");
+        // (source frame k - 3's slot is free: final frame k - 2, the last to read it, was waited for)
+        const long long k = d->pushed;
+        HIP_TRY(hipMemcpyAsync(d->d_frame[k % 3], frame, d->bytes, hipMemcpyHostToDevice, d->stream));
+        d->pushed = k + 1;
+        ++d->counts[0];
+        if (k == 0) HIP_TRY(hipStreamSynchronize(d->stream));       // (`frame` is the caller's again when the call returns)
+        else if (ivtc_finalize(d, k - 1, true)) return 1;
+    } else if (!d->ended) {                         // the first flush step: the last frame has no next
+        if (d->finals < d->pushed && ivtc_finalize(d, d->pushed - 1, false)) return 1;
+        d->dec.end();
+        d->ended = true;
+    }
+    long long j = 0;
+    if (d->dec.pop(&j)) {
+        HIP_TRY(hipMemcpyAsync(out, d->d_final[j % uva_ivtc::RING], d->bytes, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        *produced = 1;
+        ++d->counts[1];
+    } else if (!frame) {                            // flushed empty: as after reset
+        d->counts[6] += (unsigned long long)d->dec.dropped;
+        ivtc_clear(d);
+    }
+    return 0;
+}
+
+int uva_ivtc_reset(uva_ivtc* d)
+{
+    if (!d) return fail("uva_ivtc_reset: null pointer");
+    d->counts[6] += (unsigned long long)d->dec.dropped;
+    ivtc_clear(d);
+    return 0;
+}
+
+int uva_ivtc_stats(uva_ivtc* d, unsigned long long* stats)
+{
+    if (!d || !stats) return fail("uva_ivtc_stats: null pointer");
+    for (int k = 0; k < 7; ++k) stats[k] = d->counts[k];
+    stats[6] += (unsigned long long)d->dec.dropped;         // (the stream in progress)
+    return 0;
+}
+
+void uva_ivtc_destroy(uva_ivtc* d)
 {
     if (!d) return;
     (void)hipSetDevice(d->device);

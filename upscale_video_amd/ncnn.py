@@ -959,3 +959,137 @@ class Net:
         buf = np.empty(need.value, np.uint16)
         _lib.check(self._L.uva_net_debug_packed_weights(self._h, conv_idx, buf.ctypes.data, need.value, need))
         return buf
+
+
+# ---- inverse telecine (include/uva.h uva_ivtc_*) -------------------------------------------------------
+IVTC_COMBED = {"yadif": 0, "keep": 2}                # UVA_IVTC_KEEP_COMBED
+IVTC_BFF, IVTC_KEEP_ALL = 1, 4                       # UVA_IVTC_BFF, UVA_IVTC_KEEP_ALL
+IVTC_MATCHES = "cpn"
+IVTC_STATS = ("frames_in", "frames_out", "match_c", "match_p", "match_n", "combed", "dropped")
+
+
+def ivtc_flags(field_order="tff", combed="yadif", keep_all=False):
+    """the C ABI's flags argument: UVA_IVTC_BFF | UVA_IVTC_KEEP_COMBED | UVA_IVTC_KEEP_ALL"""
+    if field_order not in FIELD_ORDERS:
+        raise ValueError("unknown field order %r (%s)" % (field_order, ", ".join(FIELD_ORDERS)))
+    if combed not in IVTC_COMBED:
+        raise ValueError("unknown policy for combed frames %r (%s)" % (combed, ", ".join(IVTC_COMBED)))
+    return (IVTC_BFF if field_order == "bff" else 0) | IVTC_COMBED[combed] | (IVTC_KEEP_ALL if keep_all else 0)
+
+
+def ivtc_check(fmt, h, w, field_order="tff", thresh=9, combed="yadif", combed_limit=1000, keep_all=False):
+    """Raises UvaError with the reason if the library refuses to detelecine h x w frames of `fmt` (include/uva.h uva_ivtc_check;
+    no GPU needed)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    _lib.check(_crop_lib("uva_ivtc_check").uva_ivtc_check(PIX_FORMATS_ALL[fmt], int(h), int(w), ivtc_flags(field_order, combed, keep_all),
+                                                          int(thresh), int(combed_limit)))
+
+
+def ivtc_metrics(prev, cur, nxt, fmt, h, w, field_order="tff", thresh=9, gpu=0, device=False, host=False, max_groups=None,
+                 combed="yadif", combed_limit=1000):
+    """The comb metric of the three frames that weave the first field of the dense h x w frame `cur` of `fmt` with the second field
+    of cur, `prev` and `nxt` (None: cur), on HIP device `gpu` (include/uva.h uva_ivtc_metrics) ->
+    (N_c, M_c, N_p, M_p, N_n, M_n), exact integers.  device=True: the frames are raw device pointers (ints) of frames in that
+    GPU's HBM (uva_ivtc_metrics_device).  max_groups: the test hook uva_debug_ivtc_metrics.  host=True: the library's scalar
+    restatement, no GPU (uva_debug_ivtc_host) -> (stats, woven [3][frame bytes] for c / p / n, chosen frame, match, combed)."""
+    if fmt not in PIX_FORMATS_ALL:
+        raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+    flags = ivtc_flags(field_order, combed)
+    f, h, w, T = PIX_FORMATS_ALL[fmt], int(h), int(w), int(thresh)
+    st = (ctypes.c_ulonglong * 6)()
+    if device:
+        ptr = lambda v: None if v is None else ctypes.c_void_p(int(v))          # noqa: E731
+        _lib.check(_crop_lib("uva_ivtc_metrics_device").uva_ivtc_metrics_device(int(gpu), ptr(prev), ptr(cur), ptr(nxt), f, h, w, flags, T, st))
+        return tuple(int(v) for v in st)
+    _lib.check(_crop_lib("uva_ivtc_check").uva_ivtc_check(f, h, w, flags, T, int(combed_limit)))
+    frames = [None if v is None else _pix_frame(v, fmt, h, w, what) for v, what in ((prev, "prev"), (cur, "cur"), (nxt, "next"))]
+    p, c, n = (None if v is None else v.ctypes.data for v in frames)
+    if host:
+        nb = pix_frame_bytes(fmt, h, w)
+        woven, chosen, dec = np.empty((3, nb), np.uint8), np.empty(nb, np.uint8), (ctypes.c_int * 2)()
+        _lib.check(_crop_lib("uva_debug_ivtc_host").uva_debug_ivtc_host(p, c, n, f, h, w, flags, T, int(combed_limit), st, woven.ctypes.data,
+                                                                        chosen.ctypes.data, dec))
+        return tuple(int(v) for v in st), woven, chosen, int(dec[0]), bool(dec[1])
+    if max_groups is None:
+        _lib.check(_crop_lib("uva_ivtc_metrics").uva_ivtc_metrics(int(gpu), p, c, n, f, h, w, flags, T, st))
+    else:
+        _lib.check(_crop_lib("uva_debug_ivtc_metrics").uva_debug_ivtc_metrics(int(gpu), p, c, n, f, h, w, flags, T, st, int(max_groups)))
+    return tuple(int(v) for v in st)
+
+
+def ivtc_decimate(diffs, keep_all=False):
+    """The numbers of the final frames that the decimator delivers, in order, for these diffs (the library's state machine driven
+    as uva_ivtc_push drives it; uva_debug_ivtc_decimate, no GPU)."""
+    n = len(diffs)
+    d = (ctypes.c_ulonglong * max(1, n))(*[int(v) for v in diffs])
+    out, k = (ctypes.c_longlong * max(1, n))(), ctypes.c_int(0)
+    _lib.check(_crop_lib("uva_debug_ivtc_decimate").uva_debug_ivtc_decimate(d, n, IVTC_KEEP_ALL if keep_all else 0, out, ctypes.byref(k)))
+    return [int(out[i]) for i in range(k.value)]
+
+
+class Detelecine:
+    """A stream of dense h x w frames of `fmt` detelecined on HIP device `gpu`, every frame uploaded once (include/uva.h
+    uva_ivtc_create / uva_ivtc_push): field matching, yadif for frames that stay combed, and one frame of
+    every five dropped.  push(frame, out) hands a frame in and returns 1 if it wrote a frame of the result into `out`, else 0;
+    flush(out) is called until it returns 0 and leaves the object ready for another stream; reset() forgets the stream so far.
+    Which call delivers which frame is not part of the contract, the sequence of delivered frames is.  stats(): a dict of
+    IVTC_STATS since creation."""
+
+    def __init__(self, fmt, h, w, field_order="tff", thresh=9, combed="yadif", combed_limit=1000, keep_all=False, gpu=0):
+        if fmt not in PIX_FORMATS_ALL:
+            raise ValueError("unknown pixel format %r (%s)" % (fmt, ", ".join(PIX_FORMATS_ALL)))
+        self.fmt, self.h, self.w, self.gpu = fmt, int(h), int(w), int(gpu)
+        self.flags = ivtc_flags(field_order, combed, keep_all)
+        self.per_frame = 1
+        self.nbytes = pix_frame_bytes(fmt, self.h, self.w)
+        self._L = _crop_lib("uva_ivtc_create")
+        self._h = ctypes.c_void_p()
+        _lib.check(self._L.uva_ivtc_create(self.gpu, PIX_FORMATS_ALL[fmt], self.h, self.w, self.flags, int(thresh), int(combed_limit),
+                                           ctypes.byref(self._h)))
+
+    def _push(self, frame, out):
+        if self._h is None:
+            raise ValueError("the detelecine handle is closed")
+        if not out.flags.c_contiguous or out.nbytes != self.nbytes or not out.flags.writeable:
+            raise ValueError("the output must be a writable C-contiguous buffer of %d bytes" % self.nbytes)
+        n = ctypes.c_int(0)
+        src = None if frame is None else _pix_frame(frame, self.fmt, self.h, self.w, "frame")
+        _lib.check(self._L.uva_ivtc_push(self._h, None if src is None else src.ctypes.data, out.ctypes.data, ctypes.byref(n)))
+        return n.value
+
+    def push(self, frame, out):
+        if frame is None:
+            raise ValueError("push() takes a frame; flush() ends the stream")
+        return self._push(frame, out)
+
+    def flush(self, out):
+        return self._push(None, out)
+
+    def reset(self):
+        if self._h is not None:
+            _lib.check(self._L.uva_ivtc_reset(self._h))
+
+    def stats(self):
+        if self._h is None:
+            raise ValueError("the detelecine handle is closed")
+        st = (ctypes.c_ulonglong * 7)()
+        _lib.check(self._L.uva_ivtc_stats(self._h, st))
+        return dict(zip(IVTC_STATS, (int(v) for v in st)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._L.uva_ivtc_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass

@@ -56,6 +56,13 @@ in integers, so no ffmpeg `yadif` process has to sit in front of the pipe and th
 frame in; field: one per field, so twice the frames leave at twice the rate (give the encoder behind the pipe `-r` accordingly).
 --field-order tff|bff names the field that comes first in time (default tff).  --frames counts input frames.
 
+--detelecine takes film carried as interlaced video by 2:3 pulldown (NTSC film and anime DVDs): in the
+same place, every frame is matched with the field of itself, its predecessor or its successor that combs least, frames that
+stay combed go through yadif's rule (--detelecine-combed keep: they stay), and of every five frames the one closest to its
+predecessor, the repeat, is dropped: n frames in, n - n // 5 out, so tell the consumer 4/5 of the input's frame rate.  The nets
+see four film frames where the input has five.  The rule is this project's own (tests/ivtc_ref.py): parity with ffmpeg's
+fieldmatch / decimate filters is unpinned.  --detelecine-thresh T, --detelecine-combed-limit L, --detelecine-keep-all.
+
 The first net of a lane takes the input format and its last net produces the output format (Net.submit_pix: the
 conversions run on the net's stream around its kernels); nets in between pass u8 BGR (u16 BGR with --bit-depth 16).  A leading `-m n=K` stage converts
 its frames with uva_pix_convert; `-s 1` without a net converts every frame once, or copies it when the formats are equal.
@@ -391,6 +398,43 @@ class DeintSpec:
         return ncnn.Deinterlacer(fmt, h, w, self.mode, self.field_order, gpu=gpu)
 
 
+class DetelecineSpec:
+    """--detelecine: inverse telecine of 2:3 pulldown in front of everything else, where --deinterlace would sit
+    (ncnn.Detelecine; DESIGN.md section 7.15).  n input frames give n - n // 5 frames (keep_all: n).  The handles it opens add
+    their counters to `totals` when they close."""
+    per_frame = 1
+
+    def __init__(self, field_order="tff", thresh=9, combed="yadif", combed_limit=1000, keep_all=False):
+        ncnn.ivtc_flags(field_order, combed, keep_all)      # (checks the names)
+        if not 0 <= int(thresh) <= 255:
+            raise ValueError("the comb threshold T is 0 ... 255 on the 8-bit scale, not %d" % thresh)
+        if not 0 <= int(combed_limit) <= 1000000:
+            raise ValueError("the combed limit L is 0 ... 1000000 parts per million, not %d" % combed_limit)
+        self.field_order, self.thresh, self.combed, self.combed_limit, self.keep_all = field_order, int(thresh), combed, int(combed_limit), bool(keep_all)
+        self.totals = dict.fromkeys(ncnn.IVTC_STATS, 0)
+        self._lock = threading.Lock()
+
+    def out_frames(self, n):
+        return n if self.keep_all else n - n // 5
+
+    def open(self, fmt, h, w, gpu):
+        spec = self
+
+        class Handle(ncnn.Detelecine):
+            def close(self):
+                if getattr(self, "_h", None) is not None:
+                    with spec._lock:
+                        for k, v in self.stats().items():
+                            spec.totals[k] += v
+                super().close()
+        return Handle(fmt, h, w, self.field_order, self.thresh, self.combed, self.combed_limit, self.keep_all, gpu=gpu)
+
+    def summary(self):
+        t = self.totals
+        return ("detelecine: %d frames in, %d out; matches c/p/n %d/%d/%d, %d combed, %d dropped"
+                % (t["frames_in"], t["frames_out"], t["match_c"], t["match_p"], t["match_n"], t["combed"], t["dropped"]))
+
+
 def _lane_gpu(spec):
     """the HIP ordinal of a lane's first stage"""
     first = spec[0][0]
@@ -426,6 +470,32 @@ def deinterlaced(fin, di, raw, outs_for, max_frames=None, lead=False, trail=Fals
         yield produced(di.flush(outs_for()))
 
 
+def detelecined(fin, dt, raw, outs_for, max_frames=None, lead=False, trail=False):
+    """The reader with --detelecine, beside deinterlaced(): frames are read from fin into `raw` and pushed through the Detelecine
+    handle `dt`; yields 1 whenever a push or a flush step wrote a frame into the buffer outs_for()[0] named, else 0.  At the end
+    of the input it flushes until the handle is empty.  max_frames counts input frames.  A stream is never cut (its cycles of
+    five would have to align), so there are no context frames: lead / trail must be False."""
+    if lead or trail:
+        raise ValueError("--detelecine: a stream is not cut into segments")
+    view = memoryview(raw).cast("B")
+    n_read = 0
+    while max_frames is None or n_read < max_frames:
+        if not read_exact(fin, view):
+            break
+        n_read += 1
+        yield dt.push(raw, outs_for()[0])
+    while True:
+        k = dt.flush(outs_for()[0])
+        if not k:
+            return
+        yield k
+
+
+def _front_reader(spec):
+    """the generator that reads frames through what `spec` (DeintSpec / DetelecineSpec) opens"""
+    return detelecined if isinstance(spec, DetelecineSpec) else deinterlaced
+
+
 class DeintReader:
     """A byte stream of deinterlaced frames over the input `fin`, for the routes that read frames with read_exact and run no lane
     (copy_through): readinto() serves the outputs of deinterlaced() one after the other.  max_frames counts input frames."""
@@ -434,7 +504,7 @@ class DeintReader:
         self._di = deint.open(fmt, h, w, gpu)
         nb = ncnn.pix_frame_bytes(fmt, h, w)
         self._outs = [np.empty(nb, np.uint8) for _ in range(deint.per_frame)]
-        self._gen = deinterlaced(fin, self._di, np.empty(nb, np.uint8), lambda: self._outs, max_frames)
+        self._gen = _front_reader(deint)(fin, self._di, np.empty(nb, np.uint8), lambda: self._outs, max_frames)
         self._ready, self._pos = [], 0       # frames produced and not served yet; bytes served of the first
 
     def readinto(self, view):
@@ -479,7 +549,9 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
     deint (DeintSpec): every frame read goes through a Deinterlacer on the first lane's GPU first, and what comes out -- 0, 1 or 2
     frames of the input's format and size -- is dealt to the lanes as frames read from fin are without it; at the end of the
     input the deinterlacer is flushed.  max_frames counts input frames.  deint_lead / deint_trail: fin starts one frame before
-    the stream / holds the frame after max_frames, as context (stream_segments; deinterlaced())."""
+    the stream / holds the frame after max_frames, as context (stream_segments; deinterlaced()).  deint may also be a
+    DetelecineSpec (--detelecine): the same place, a Detelecine handle, and at the end of the input it is flushed until empty
+    (detelecined()); a push hands out at most one frame, so the ring is that of per_frame 1."""
     alloc = alloc or ncnn.pinned_empty
     pix = pix or BGR
     lanes_spec = nets_tiles if nets_tiles and isinstance(nets_tiles[0], list) else [nets_tiles]
@@ -559,8 +631,8 @@ def stream(fin, fout, h, w, nets_tiles, alloc=None, max_frames=None, write_threa
     try:
         if deint is not None:
             di = deint.open(pix.in_fmt, src_h, src_w, _lane_gpu(lanes_spec[0]))
-            for k in deinterlaced(fin, di, raw, lambda: [ins[(n_in + j) % len(ins)] for j in range(deint.per_frame)], max_frames,
-                                  deint_lead, deint_trail):
+            for k in _front_reader(deint)(fin, di, raw, lambda: [ins[(n_in + j) % len(ins)] for j in range(deint.per_frame)], max_frames,
+                                          deint_lead, deint_trail):
                 for _ in range(k):
                     lane = lanes[n_in % nl]
                     while lane.full():
@@ -680,6 +752,10 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
     stream of its own."""
     pix = pix or BGR
     per = deint.per_frame if deint is not None else 1          # output frames per input frame
+    ivtc = isinstance(deint, DetelecineSpec)
+    if ivtc and not isinstance(in_path, (list, tuple)):
+        raise ValueError("--detelecine: one input file is one stream and is not cut into segments (its cycles of five would have to "
+                         "align); give every -g entry an input file of its own, or deal the frames out round-robin")
     net_h, net_w = pix.net_size(h, w)      # (pix.crop: the lanes work on a window of the h x w frames in the file)
     fb_in, fb_out = pix.frame_bytes(h, w), pix.frame_bytes(*pix.result_size(net_h * scale_total, net_w * scale_total), out=True)
     nl = len(lanes_spec)
@@ -715,8 +791,9 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
         in_first = [0] * nl
         total = sum(counts)
     in_total = total                                            # input frames of the stream
-    out_first = [0] * nl if outs is not None else [sum(counts[:k]) * per for k in range(nl)]
-    total *= per                                                # (from here on: output frames)
+    out_counts = [deint.out_frames(c) if ivtc else c * per for c in counts]     # (--detelecine: every file loses its own repeats)
+    out_first = [0] * nl if outs is not None else [sum(out_counts[:k]) for k in range(nl)]
+    total = sum(out_counts)                                     # (from here on: output frames)
     created = [o for o in (outs if outs is not None else [out_path]) if not os.path.exists(o)]
     if outs is None:
         with opener(out_path, "wb") as f:       # the output exists at its full size before anybody writes into it
@@ -754,7 +831,7 @@ def stream_segments(in_path, out_path, h, w, lanes_spec, scale_total, max_frames
             with opener(in_path if ins is None else ins[k], "rb") as fin:
                 fin.seek((in_first[k] - (1 if lead else 0)) * fb_in)
                 if outs is None and mapped:
-                    with MappedSegment(opener(out_path, "r+b"), out_first[k] * fb_out, counts[k] * per * fb_out) as fout:
+                    with MappedSegment(opener(out_path, "r+b"), out_first[k] * fb_out, out_counts[k] * fb_out) as fout:
                         done[k] = stream(fin, fout, h, w, lanes_spec[k], alloc=alloc, max_frames=counts[k], pix=pix, **kw)
                 else:
                     with opener(out_path if outs is None else outs[k], "r+b" if outs is None else "wb") as fout:
@@ -881,7 +958,8 @@ def copy_through(fin, fout, h, w, max_frames=None, pix=None, gpu=0, deint=None):
     ends (pix): every frame is converted once on HIP device `gpu` (include/uva.h uva_pix_convert; with pix.bit_depth 16
     uva_pix_convert16, through u16 BGR).  With pix.out_size every frame is converted to BGR, resampled (include/uva.h uva_resize)
     and converted to the output format at the new size.  deint (DeintSpec): the frames are deinterlaced first, on the same
-    device (DeintReader; max_frames counts input frames) -- with equal formats at both ends a deinterlace-only run."""
+    device (DeintReader; max_frames counts input frames) -- with equal formats at both ends a deinterlace-only run; a
+    DetelecineSpec likewise: a detelecine-only run."""
     pix = pix or BGR
     if deint is not None:
         reader = DeintReader(fin, deint, pix.in_fmt, h, w, gpu=gpu, max_frames=max_frames)
@@ -1118,13 +1196,54 @@ def main(argv=None):
                          "field: one per field, twice the frames at twice the rate.  --frames counts input frames.  --crop auto "
                          "and --cropdetect keep sampling the source frames directly: bars are black in both fields")
     ap.add_argument("--field-order", default=None, metavar="tff|bff",
-                    help="with --deinterlace: which rows come first in time, tff (default: the even rows, top field first) or bff")
+                    help="with --deinterlace or --detelecine: which rows come first in time, tff (default: the even rows, top field "
+                         "first) or bff")
+    ap.add_argument("--detelecine", action="store_true",
+                    help="inverse telecine on the GPU in front of everything else: NTSC film and anime carried as interlaced video "
+                         "by 2:3 pulldown get their film frames back by field matching, and one frame of every five, the repeat, "
+                         "is dropped (DESIGN.md section 7.15; the rule is this project's own, parity with ffmpeg's fieldmatch / "
+                         "decimate is unpinned).  n input frames give n - n // 5 frames: tell the consumer a frame rate of 4/5 of "
+                         "the input's (24000/1001 for 30000/1001).  --frames counts input frames.  Not together with --deinterlace")
+    ap.add_argument("--detelecine-thresh", type=int, default=None, metavar="T",
+                    help="with --detelecine: a sample counts as combed when it differs from both vertical neighbours, in the same "
+                         "direction, by more than T on the 8-bit scale (0 ... 255, default 9)")
+    ap.add_argument("--detelecine-combed", default=None, metavar="yadif|keep",
+                    help="with --detelecine: a frame that stays combed after matching is deinterlaced by yadif's rule (default) or "
+                         "kept as matched")
+    ap.add_argument("--detelecine-combed-limit", type=int, default=None, metavar="L",
+                    help="with --detelecine: a matched frame is combed when more than L parts per million of its samples are "
+                         "(0 ... 1000000, default 1000: a guess, no telecined real material was at hand to set it; an option, "
+                         "not a tested bar)")
+    ap.add_argument("--detelecine-keep-all", action="store_true",
+                    help="with --detelecine: match fields but drop nothing (n frames out for n in, the repeats stay)")
     a = ap.parse_args(argv)
     if a.width <= 0 or a.height <= 0:
         ap.error("frame size must be positive")
     deint = None
-    if a.field_order is not None and a.deinterlace is None:
-        ap.error("--field-order needs --deinterlace frame|field")
+    if a.field_order is not None and a.deinterlace is None and not a.detelecine:
+        ap.error("--field-order needs --deinterlace frame|field or --detelecine")
+    if a.detelecine and a.deinterlace is not None:
+        ap.error("--detelecine and --deinterlace exclude each other: telecined film is matched, not interpolated (frames that stay "
+                 "combed go through yadif anyway, --detelecine-combed)")
+    if not a.detelecine:
+        for opt, val in (("--detelecine-thresh", a.detelecine_thresh), ("--detelecine-combed", a.detelecine_combed),
+                         ("--detelecine-combed-limit", a.detelecine_combed_limit), ("--detelecine-keep-all", a.detelecine_keep_all or None)):
+            if val is not None:
+                ap.error("%s needs --detelecine" % opt)
+    else:
+        if a.field_order is not None and a.field_order not in ncnn.FIELD_ORDERS:
+            ap.error("--field-order takes tff or bff, not %r" % a.field_order)
+        if a.detelecine_combed is not None and a.detelecine_combed not in ncnn.IVTC_COMBED:
+            ap.error("--detelecine-combed takes yadif or keep, not %r" % a.detelecine_combed)
+        if a.detelecine_thresh is not None and not 0 <= a.detelecine_thresh <= 255:
+            ap.error("--detelecine-thresh is 0 ... 255 on the 8-bit scale, not %d" % a.detelecine_thresh)
+        if a.detelecine_combed_limit is not None and not 0 <= a.detelecine_combed_limit <= 1000000:
+            ap.error("--detelecine-combed-limit is 0 ... 1000000 parts per million, not %d" % a.detelecine_combed_limit)
+        if a.height < 4:
+            ap.error("--detelecine: frames of fewer than 4 rows (-H %d) have no two rows of either field in every plane" % a.height)
+        deint = DetelecineSpec(a.field_order or "tff", 9 if a.detelecine_thresh is None else a.detelecine_thresh,
+                               a.detelecine_combed or "yadif", 1000 if a.detelecine_combed_limit is None else a.detelecine_combed_limit,
+                               a.detelecine_keep_all)
     if a.deinterlace is not None:
         if a.deinterlace not in ncnn.DEINT_MODES:
             ap.error("--deinterlace takes frame or field, not %r" % a.deinterlace)
@@ -1302,6 +1421,11 @@ def main(argv=None):
                          os.environ.get("UVA_RAW_TMPFS_SEGMENTS") != "1")
     segments = bool(nets) and (len(ins) > 1 or len(outs) > 1 or (len(nets) > 1 and not a.round_robin and not one_file_on_tmpfs and
                                                                   a.input != "-" and a.output != "-" and regular))
+    if isinstance(deint, DetelecineSpec) and segments and len(ins) == 1:
+        # one input file is one stream: its cycles of five would have to align with the segments' borders
+        print("--detelecine: one input file is not cut into segments; the %d -g entries take its frames round-robin" % len(nets),
+              file=sys.stderr)
+        segments = False
     summary = lambda n: "%d frames" % n                                               # noqa: E731
     if a.skip_repeats is not None and nets:
         if len(nets) > 1 and not segments:
@@ -1319,6 +1443,8 @@ def main(argv=None):
         n = stream_segments(ins if len(ins) > 1 else ins[0], outs if len(outs) > 1 else outs[0], a.height, a.width, nets, scale_total,
                             max_frames=a.frames, write_threads=wthreads, pix=pix, **({"deint": deint} if deint is not None else {}))
         print(summary(n), file=sys.stderr)
+        if isinstance(deint, DetelecineSpec):
+            print(deint.summary(), file=sys.stderr)
         ncnn.destroy_gpu_instance()
         return 0
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
@@ -1342,6 +1468,8 @@ def main(argv=None):
             if not ok and created and os.path.isfile(a.output):
                 os.remove(a.output)                # half a stream under the name of a whole one helps nobody
     print(summary(n), file=sys.stderr)
+    if isinstance(deint, DetelecineSpec):
+        print(deint.summary(), file=sys.stderr)
     ncnn.destroy_gpu_instance()
     return 0
 
